@@ -11,10 +11,14 @@ over the N ranks (vgposp_amd.sharded_placement over RCCL): the ranks factor Sigm
 (vgposp_amd.dist_cholesky: each large node of the recursive Cholesky has its panel TRSM and SYRK
 split over the ranks, shares all-gathered), each rank forms L^-1 only in its own candidate columns
 (1/N of the inverse), and per round all-reduces the pick's column of L^-1, all-gathers the delta
-slabs and all-reduces the pivot row.  Strong scaling (DESIGN.md §6).  The timed loop runs with the library's event timing OFF;
-the roofline numbers come from one more, profiled, step.
+slabs and all-reduces the pivot row.  Strong scaling.  The timed loop runs with the
+library's event timing OFF.
 
-Also reported: fp64 Cholesky GF/s (plain potrf of the same Sigma, N^3/3 flops); config C4 (the
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs if
+--dump-outputs DIR is given, and prints the headline line (metric, value, unit, ms_per_step, the
+config and the selections).  Everything below runs only with --full, after the timed steps, and adds
+its keys to that line: the roofline numbers from one more, profiled, step; whether the selections
+repeat and equal the committed CPU picks; fp64 Cholesky GF/s (plain potrf of the same Sigma, N^3/3 flops); config C4 (the
 128^3 local-kernel greedy, candidates sharded over the same ranks: where sharding pays); at N > 1
 the independent-splits throughput (one 64x32x32 split per rank) as a labelled extra; at N = 1 the
 C2 / C3 / C5 lines and a CPU baseline (the oracle timed on the host cores).
@@ -40,8 +44,17 @@ METRIC = "greedy sensor placements/sec + fp64 Cholesky GF/s on N=65k 3D grid"
 def parse():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=3)
+    p.add_argument("--steps", type=int, default=3, help="timed steps (at least 1)")
     p.add_argument("--warmup", type=int, default=1)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run everything else this file measures or "
+                        "checks (the profiled roofline step, potrf, C2 / C3 / C4 / C5, the grid "
+                        "sweep, the CPU baselines, the comparisons with the committed picks); the "
+                        "--no-* options below pick among those parts and mean nothing without it")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed (the selections, their deltas, "
+                        "the per-round evaluation counts, and on one GPU a seeded sample of the "
+                        "covariance buffer factored in place) as DIR/<name>.npy, float64")
     p.add_argument("--shape", type=int, nargs=3, default=[64, 32, 32])
     p.add_argument("--k", type=int, default=50)
     p.add_argument("--kernel", default="eq")
@@ -73,7 +86,36 @@ def parse():
                    help="(tests) every rank prints its rank / world size and exits before any GPU call")
     p.add_argument("--traffic", default=os.path.join(ROOT, "profiles", "traffic_r6.json"),
                    help="per-launch HBM bytes from a rocprofv3 PMC pass of this command")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_SAMPLE = 65536  # entries of the factored covariance buffer written by --dump-outputs
+
+
+def dump_outputs(path, g, Sigma, world):
+    """--dump-outputs: what a caller of the timed step holds after its last run, as float64 .npy
+    files under `path`: GreedyPlacement.result() (the selections in pick order, their deltas, the
+    evaluations each lazy round made) and, on one GPU, DUMP_SAMPLE entries of the caller's
+    covariance buffer, which the step factors in place (the same seeded positions in every run;
+    the whole buffer is 8 N^2 bytes).  With N > 1 ranks each rank holds only its part of the
+    inverse, so rank 0 writes the selections alone."""
+    import torch
+    sel, delta, evals = g.result()
+    arrays = {"selected": np.asarray(sel, dtype=np.float64),
+              "selected_delta": np.asarray(delta, dtype=np.float64),
+              "evaluations": np.asarray(evals, dtype=np.float64)}
+    if world == 1:
+        n = int(Sigma.shape[0])
+        rng = np.random.default_rng(0)
+        rows = torch.as_tensor(rng.integers(0, n, DUMP_SAMPLE), device=Sigma.device)
+        cols = torch.as_tensor(rng.integers(0, n, DUMP_SAMPLE), device=Sigma.device)
+        arrays["covariance_factored_sample"] = Sigma[rows, cols].cpu().numpy().astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cpu_threads():
@@ -894,6 +936,44 @@ def main():
     barrier()
     elapsed = maxtime(time.perf_counter() - t0)
     g.check()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, g, Sigma, world)
+
+    ms_per_step = elapsed / args.steps * 1e3
+    sel = [int(v) for v in selected.cpu()]
+    out = {
+        "metric": METRIC,
+        "value": k * args.steps / elapsed,
+        "unit": "placements/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": f"{shape[0]}x{shape[1]}x{shape[2]} jittered grid (N={N}), "
+                               f"{args.kernel.upper()} kernel amp=1 ls=2h noise={args.noise}+1e-6, "
+                               f"k={k} lazy-greedy MI placements, dense-exact, one problem"
+                               + (f" candidate-sharded over {world} ranks "
+                                  f"({'RCCL' if args.backend == 'nccl' else args.backend}), Cholesky "
+                                  "distributed (panel / SYRK shares all-gathered), inverse "
+                                  "partitioned" if world > 1 else ""),
+                   "N": N, "k": k, "parallelism": f"candidates{world}" if world > 1 else "single",
+                   "rccl_world_size": world if world > 1 and args.backend == "nccl" else None,
+                   "backend": args.backend if world > 1 else None},
+        "selected_head": sel[:8],
+        "selected": sel,
+    }
+    if not args.full:
+        # the plain run ends here: the headline figure and nothing that takes a run of its own
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     deterministic = bool(torch.equal(ref_sel, selected))
 
     # one more step with the library's per-launch event timing on: the roofline numbers
@@ -963,8 +1043,6 @@ def main():
             dist.destroy_process_group()
         return
 
-    ms_per_step = elapsed / args.steps * 1e3
-    value = k * args.steps / elapsed
     # dominant kernel by time in the profiled step
     dom = max(prof, key=lambda n: prof[n][0])
     ms, launches, flops, nbytes = prof[dom]
@@ -1014,29 +1092,7 @@ def main():
                                   v[3] / max(v[0], 1e-9) / 1e6),
                      "unit": "TFLOP/s" if n == "gemm_f64" else "GB/s"}
                  for n, v in prof.items() if v[1]}
-    out = {
-        "metric": METRIC,
-        "value": value,
-        "unit": "placements/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {"workload": f"{shape[0]}x{shape[1]}x{shape[2]} jittered grid (N={N}), "
-                               f"{args.kernel.upper()} kernel amp=1 ls=2h noise={args.noise}+1e-6, "
-                               f"k={k} lazy-greedy MI placements, dense-exact, one problem"
-                               + (f" candidate-sharded over {world} ranks "
-                                  f"({'RCCL' if args.backend == 'nccl' else args.backend}), Cholesky "
-                                  "distributed (panel / SYRK shares all-gathered), inverse "
-                                  "partitioned" if world > 1 else ""),
-                   "N": N, "k": k, "parallelism": f"candidates{world}" if world > 1 else "single",
-                   "rccl_world_size": world if world > 1 and args.backend == "nccl" else None,
-                   "backend": args.backend if world > 1 else None},
+    out.update({
         "cholesky_gflops": chol_gflops,
         "cholesky_note": ("plain single-GPU potrf of the same Sigma" if world == 1 else
                           f"distributed potrf over {world} ranks (max-over-ranks time), "
@@ -1053,7 +1109,7 @@ def main():
         "matches_committed_picks": (_committed("bench65k_cpu_picks.json", sel)
                                     if (shape == (64, 32, 32) and k == 50 and args.kernel == "eq"
                                         and args.noise == 1e-2) else None),
-    }
+    })
     if c4 is not None:
         out["c4"] = c4
     if sweep is not None:

@@ -8,6 +8,6 @@ for lib in default "$@"; do
   if [ $lib = default ]; then unset VGPOSP_LIB; else export VGPOSP_LIB=$PWD/tools/variants/$lib.so; fi
   echo "== $lib" >> $out
   timeout -k 10 300 python -u tools/gemm_layouts.py >> $out 2>&1
-  timeout -k 10 300 python -u bench.py --no-cpu --no-vgp --no-c2 --no-c4 --no-sweep --steps 2 --warmup 1 2>&1 | grep '^{' | cut -c1-160 >> $out
+  timeout -k 10 300 python -u bench.py --full --no-cpu --no-vgp --no-c2 --no-c4 --no-sweep --steps 2 --warmup 1 2>&1 | grep '^{' | cut -c1-160 >> $out
   echo ok $lib
 done

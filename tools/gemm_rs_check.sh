@@ -17,6 +17,6 @@ for rs in 0 1 2; do
   echo ok gemm rs=$rs
 done
 for rs in 1 2; do
-  VGPOSP_LIB=$R/tools/variants/lib_rs.so VGPOSP_GEMM_RS=$rs timeout -k 10 300 python -u bench.py --no-cpu --no-vgp --no-c2 --steps 2 --warmup 1 > $O/rs${rs}_bench.log 2>&1
+  VGPOSP_LIB=$R/tools/variants/lib_rs.so VGPOSP_GEMM_RS=$rs timeout -k 10 300 python -u bench.py --full --no-cpu --no-vgp --no-c2 --steps 2 --warmup 1 > $O/rs${rs}_bench.log 2>&1
   echo ok bench rs=$rs
 done

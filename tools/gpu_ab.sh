@@ -37,7 +37,7 @@ print(json.dumps(run(8192, 8192, 8192, 0, 1, False, 0.0, reps=5)))" >> "$out/lay
     echo "gemm ok $tag"
   fi
   if [[ $step == 1 ]]; then
-    timeout -k 10 400 python -u bench.py --no-cpu --no-vgp --no-c2 --no-c4 --no-sweep --steps 2 \
+    timeout -k 10 400 python -u bench.py --full --no-cpu --no-vgp --no-c2 --no-c4 --no-sweep --steps 2 \
       --warmup 1 > "$out/step_$tag.json" 2> "$out/step_$tag.err"
     echo "step ok $tag: $(cut -c1-160 "$out/step_$tag.json")"
   fi

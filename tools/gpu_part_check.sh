@@ -11,7 +11,7 @@ echo "tests: $(tail -1 $O/gpu_tests.log)"
 for i in 1 2; do
   for lib in default part2; do
     if [[ $lib == default ]]; then unset VGPOSP_LIB; else export VGPOSP_LIB=$PWD/tools/variants/lib_part2.so; fi
-    timeout -k 10 300 python -u bench.py --no-cpu --no-c2 --no-c4 --no-sweep --steps 1 --warmup 1 > $O/${lib}_$i.json 2> $O/${lib}_$i.err
+    timeout -k 10 300 python -u bench.py --full --no-cpu --no-c2 --no-c4 --no-sweep --steps 1 --warmup 1 > $O/${lib}_$i.json 2> $O/${lib}_$i.err
     python -c "import json; d=json.load(open('$O/${lib}_$i.json')); print('$lib', $i, round(d['value'],3), [round(d[k]['ms_per_step'],3) for k in ('vgp_c3','vgp_c5','vgp_c5_mixed')])"
   done
 done

@@ -9,7 +9,7 @@ tools/gpu_ab.sh $O --tests "tests/test_gpu_linalg.py tests/test_gpu_placement.py
 for i in 1 2; do
   for lib in head default; do
     if [[ $lib == default ]]; then unset VGPOSP_LIB; else export VGPOSP_LIB=$PWD/tools/variants/lib_head.so; fi
-    timeout -k 10 400 python -u bench.py --no-cpu --no-vgp --no-c2 --no-c4 --no-sweep --steps 2 --warmup 1 > $O/step_${lib}_$i.json 2> $O/step_${lib}_$i.err
+    timeout -k 10 400 python -u bench.py --full --no-cpu --no-vgp --no-c2 --no-c4 --no-sweep --steps 2 --warmup 1 > $O/step_${lib}_$i.json 2> $O/step_${lib}_$i.err
     echo "$lib $i $(cut -c1-140 $O/step_${lib}_$i.json)"
   done
 done

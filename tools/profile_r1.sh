@@ -10,7 +10,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-ARGS="--no-cpu --no-vgp --no-potrf --no-c2 --steps 1 --warmup 0"
+ARGS="--full --no-cpu --no-vgp --no-potrf --no-c2 --steps 1 --warmup 0"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_r1 -o bench -- python3 $R/bench.py $ARGS > $O/prof_r1.log 2>&1
 grep "^{" $O/prof_r1.log > $O/prof_r1_bench.json
 echo ok kernel-trace

@@ -9,7 +9,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-ARGS="--no-cpu --no-vgp --no-potrf --no-c2 --no-c4 --no-splits --steps 1 --warmup 0"
+ARGS="--full --no-cpu --no-vgp --no-potrf --no-c2 --no-c4 --no-splits --steps 1 --warmup 0"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_r2 -o bench -- python3 $R/bench.py $ARGS > $O/prof_r2.log 2>&1
 python3 $R/tools/rocprof_summary.py $O/prof_r2/bench_kernel_stats.csv $O/prof_r2_summary.txt > /dev/null
 echo ok placement

@@ -8,6 +8,6 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 mkdir -p $R/gpurun_out
 cd $R
 VGPOSP_BENCH_DEVICE=0 timeout -k 10 $LIMIT python -m torch.distributed.run --nnodes=1 --nproc-per-node $NP \
-  --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus $NP --backend gloo --shape 32 32 32 \
+  --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus $NP --backend gloo --shape 32 32 32 \
   --steps 1 --warmup 1 > gpurun_out/rehearse$NP.log 2>&1
 echo rc=$?

@@ -10,6 +10,6 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout
 echo ok tests
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 echo ok smoke
-timeout -k 10 600 python -u bench.py > $O/bench_final.log 2>&1
+timeout -k 10 600 python -u bench.py --full > $O/bench_final.log 2>&1
 grep "^{" $O/bench_final.log > $O/bench_final.json
 echo final
