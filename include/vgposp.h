@@ -119,6 +119,33 @@ int vgposp_gemm_splitk(int transa, int transb, int64_t m, int64_t n, int64_t k, 
                        double* C, int64_t ldc, int uplo_c, int tri_a, int tri_b, int splits,
                        void* ws, size_t ws_bytes, void* stream);
 
+/* Strassen form of vgposp_gemm for large plain products (full C, dense operands, C not
+ * overlapping A or B): up to `levels` (0..2) levels of the classic seven-product recursion in
+ * native fp64.  A level is taken while m, n and k are each a multiple of 256 and >= min_dim (the
+ * process-wide value below) and the operands are 16-byte aligned with even leading dimensions;
+ * every product is one launch that accumulates into all the quadrants of C it belongs to, the
+ * operand sums go through ws (vgposp_gemm_strassen_workspace_bytes).  Anything not eligible, and
+ * levels = 0, is vgposp_gemm's single launch, bit-identical.  Results are fp64-accurate in the
+ * norm-wise sense (Higham, Accuracy and Stability of Numerical Algorithms, §23.2.2),
+ * deterministic, and not bit-identical to vgposp_gemm.
+ * vgposp_potrf_set_strassen(min_dim, levels): process-wide; min_dim a multiple of 256, levels
+ * 0..2 (0 = off).  ON BY DEFAULT with min_dim 8192 and 2 levels (DESIGN.md §4 "Strassen": the
+ * 65k step 6.7 % faster).  vgposp_potrf_lower (single matrix) and vgposp_greedy_init run the
+ * plain products of the fused Cholesky + inverse with all dimensions >= min_dim this way, and
+ * vgposp_potrf_workspace_bytes / vgposp_greedy_workspace_bytes grow by the operand temporaries
+ * of the largest eligible product (none below n = 4 min_dim; 2.7 GB at n = 65,536).  Results
+ * at n >= 32,768 are therefore fp64-accurate but not bit-identical to the classical recursion;
+ * levels = 0 restores it exactly.  Same caveat as the split depth: change the setting only
+ * between a workspace query and its use, consistently.  Batched, sharded and slab
+ * factorizations stay classical. */
+int vgposp_potrf_set_strassen(int64_t min_dim, int levels);
+int vgposp_potrf_strassen(int64_t* min_dim, int* levels);
+size_t vgposp_gemm_strassen_workspace_bytes(int64_t m, int64_t n, int64_t k, int levels);
+int vgposp_gemm_strassen(int transa, int transb, int64_t m, int64_t n, int64_t k, double alpha,
+                         const double* A, int64_t lda, const double* B, int64_t ldb, double beta,
+                         double* C, int64_t ldc, int levels, void* ws, size_t ws_bytes,
+                         void* stream);
+
 /* Grouped vgposp_gemm: `count` independent products, problem g with flags[5g..5g+4] = (transa,
  * transb, uplo_c, tri_a, tri_b), dims[3g..3g+2] = (m, n, k), alpha[g], beta[g], A[g] (lda[g]),
  * B[g] (ldb[g]), C[g] (ldc[g]), all in ONE launch (problem on blockIdx.y) plus one grouped split-K

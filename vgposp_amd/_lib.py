@@ -72,6 +72,12 @@ SIGNATURES = {
     "vgposp_gemm_splitk": (_i32, [_i32, _i32, _i64, _i64, _i64, _f64, _c_void_p, _i64, _c_void_p,
                                   _i64, _f64, _c_void_p, _i64, _i32, _i32, _i32, _i32, _c_void_p,
                                   _size, _c_void_p]),
+    "vgposp_potrf_set_strassen": (_i32, [_i64, _i32]),
+    "vgposp_potrf_strassen": (_i32, [ctypes.POINTER(_i64), ctypes.POINTER(_i32)]),
+    "vgposp_gemm_strassen_workspace_bytes": (_size, [_i64, _i64, _i64, _i32]),
+    "vgposp_gemm_strassen": (_i32, [_i32, _i32, _i64, _i64, _i64, _f64, _c_void_p, _i64, _c_void_p,
+                                    _i64, _f64, _c_void_p, _i64, _i32, _c_void_p, _size,
+                                    _c_void_p]),
     "vgposp_kernel_matrix_matvec_workspace_bytes": (_size, [_i64, _i64]),
     "vgposp_kernel_matrix_matvec": (_i32, [_i32, _c_void_p, _i64, _c_void_p, _i64, _i32,
                                            _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p,
@@ -270,7 +276,8 @@ def query(name, *args):
 # source files whose compiled code each profiled kernel family runs (for matching PMC traffic
 # records to the build they were measured on)
 KERNEL_SOURCES = {
-    "gemm_f64": ["gemm.hip", "common.h", "Makefile"],
+    # potrf.hip decides the step's GEMM shapes (structured splits, Strassen routing)
+    "gemm_f64": ["gemm.hip", "potrf.hip", "common.h", "Makefile"],
     "greedy_trmv": ["greedy.hip", "common.h", "Makefile"],
     "greedy_colsq": ["greedy.hip", "common.h", "Makefile"],
     "kernel_matrix": ["kernel_matrix.hip", "psd.h", "common.h", "Makefile"],

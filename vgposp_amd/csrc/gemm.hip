@@ -56,6 +56,18 @@ struct GemmParams {
   const int* abort;
 };
 
+// Further destinations of one product (gemm_glds_multi_kernel, the Strassen products): besides
+// C = alpha acc + beta C the epilogue writes C[d] = alpha[d] acc + beta[d] C[d] for d < n.  A
+// product of one Strassen level lands in two quadrants of C, of two levels in four (1 + 3).
+// Kept out of GemmParams so that the kernels without extra destinations keep their arguments.
+constexpr int GEMM_XDST = 3;
+struct GemmExtra {
+  int n;
+  double* C[GEMM_XDST];
+  int64_t ld[GEMM_XDST];
+  double alpha[GEMM_XDST], beta[GEMM_XDST];
+};
+
 // Set by a factorization for the GEMMs it launches from this thread (gemm_abort_scope).
 thread_local const int* tl_gemm_abort = nullptr;
 
@@ -312,10 +324,13 @@ constexpr int glds_smem_elems() {
 
 // One workgroup of the fast kernel: workgroup `bid` of the launch's `nwg` for this problem, batch
 // element bz, LDS ring at smem (the kernel's own __shared__ array).
-template <bool TA, bool TB, bool TRIA, bool TRIB, int CFG>
+// MULTI: the epilogue also writes the extra destinations *x (plain products only: no triangular
+// operand, full C, no split-K); the K loop is the same code.
+template <bool TA, bool TB, bool TRIA, bool TRIB, int CFG, bool MULTI = false>
 __device__ __forceinline__ void gemm_glds_body(const GemmParams& p, int tiles_m, int tiles_n,
                                                const int bid, const int nwg, const int64_t bz,
-                                               double* smem) {
+                                               double* smem, const GemmExtra* xd = nullptr) {
+  static_assert(!MULTI || (!TRIA && !TRIB), "extra destinations: plain products only");
   if (p.abort != nullptr && *p.abort != 0) return;
   constexpr bool A_KC = !TA;
   constexpr bool B_KC = TB;
@@ -506,6 +521,17 @@ __device__ __forceinline__ void gemm_glds_body(const GemmParams& p, int tiles_m,
           double v = p.alpha * acc[i][j][r];
           if (p.beta != 0.0) v += p.beta * *c;
           *c = v;
+          if (MULTI) {
+#pragma unroll
+            for (int d = 0; d < GEMM_XDST; ++d) {
+              if (d < xd->n) {
+                double* c2 = xd->C[d] + row * xd->ld[d] + col;
+                double v2 = xd->alpha[d] * acc[i][j][r];
+                if (xd->beta[d] != 0.0) v2 += xd->beta[d] * *c2;
+                *c2 = v2;
+              }
+            }
+          }
         }
       }
     }
@@ -518,6 +544,15 @@ __global__ __launch_bounds__(64 * GemmCfg<CFG>::NW, GemmCfg<CFG>::OCC) void gemm
   __shared__ __attribute__((aligned(16))) double smem[glds_smem_elems<CFG>()];
   gemm_glds_body<TA, TB, TRIA, TRIB, CFG>(p, tiles_m, tiles_n, blockIdx.x, gridDim.x, blockIdx.y,
                                           smem);
+}
+
+// The plain product with extra destinations (gemm_strassen): same tiles, ring and K loop.
+template <bool TA, bool TB>
+__global__ __launch_bounds__(64 * GemmCfg<1>::NW, GemmCfg<1>::OCC) void gemm_glds_multi_kernel(
+    GemmParams p, GemmExtra x, int tiles_m, int tiles_n) {
+  __shared__ __attribute__((aligned(16))) double smem[glds_smem_elems<1>()];
+  gemm_glds_body<TA, TB, false, false, 1, true>(p, tiles_m, tiles_n, blockIdx.x, gridDim.x, 0,
+                                                smem, &x);
 }
 
 // Grouped launch: up to GROUP_MAX independent problems (each its own shape, operands, flags and
@@ -948,6 +983,215 @@ int gemm_launch_group(int count, const int* flags, const int64_t* dims, const do
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Strassen for large plain products: one or two levels of the classic seven-product form on
+// op(A) op(B), in native fp64.  With the quadrants X11 X12 / X21 X22:
+//   M1 = (A11 + A22)(B11 + B22)  -> C11 + , C22 +      M5 = (A11 + A12) B22  -> C11 - , C12 +
+//   M2 = (A21 + A22) B11         -> C21 + , C22 -      M6 = (A21 - A11)(B11 + B12)  -> C22 +
+//   M3 = A11 (B12 - B22)         -> C12 + , C22 +      M7 = (A12 - A22)(B21 + B22)  -> C11 +
+//   M4 = A22 (B21 - B11)         -> C11 + , C21 +
+// Each product is ONE launch whose epilogue accumulates into every quadrant it belongs to
+// (gemm_glds_multi_kernel), so there are no C-side temporaries or sums: the first product that
+// touches a quadrant carries the caller's beta, later ones beta = 1.  The ten operand sums of a
+// level go through one A-side and one B-side temporary (strassen_add_kernel).  A second level
+// splits each of the seven products again; its products then land in up to four places.
+// Everything is enqueued on one stream in a fixed order: results are deterministic.
+// Eligible: m, n, k multiples of 256 and >= min_dim, 16-byte aligned operands with even leading
+// dimensions.  Anything else is the single classical launch, bit-identical to gemm_launch.
+// ---------------------------------------------------------------------------------------------
+struct GemmDst {
+  double* C;
+  int64_t ld;
+  double alpha, beta;
+};
+
+// D = X + sgn Y on rows x cols (cols a multiple of 128), 16-byte accesses: a wave covers 1 KiB of
+// one row, a thread four rows (its loads issued together).
+__global__ __launch_bounds__(256) void strassen_add_kernel(int64_t rows, const double* X, int64_t ldx,
+                                                          const double* Y, int64_t ldy, double sgn,
+                                                          double* D, int64_t ldd, const int* abort) {
+  if (abort != nullptr && *abort != 0) return;
+  const int64_t c = ((int64_t)blockIdx.x * 64 + threadIdx.x) * 2;
+  const int64_t r0 = (int64_t)blockIdx.y * 16 + threadIdx.y;
+  double2 xv[4], yv[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int64_t r = min(r0 + 4 * u, rows - 1);
+    xv[u] = *reinterpret_cast<const double2*>(X + r * ldx + c);
+    yv[u] = *reinterpret_cast<const double2*>(Y + r * ldy + c);
+  }
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int64_t r = r0 + 4 * u;
+    if (r < rows)
+      *reinterpret_cast<double2*>(D + r * ldd + c) =
+          make_double2(xv[u].x + sgn * yv[u].x, xv[u].y + sgn * yv[u].y);
+  }
+}
+
+static int strassen_add(int64_t rows, int64_t cols, const double* X, int64_t ldx, const double* Y,
+                        int64_t ldy, double sgn, double* D, int64_t ldd, hipStream_t s) {
+  ProfScope ps("strassen_add", s, (double)rows * cols, 24.0 * (double)rows * cols);
+  hipLaunchKernelGGL(strassen_add_kernel, dim3((unsigned)(cols / 128), (unsigned)ceil_div(rows, 16)),
+                     dim3(64, 4), 0, s, rows, X, ldx, Y, ldy, sgn, D, ldd, tl_gemm_abort);
+  VG_LAUNCH_CHECK();
+  return 0;
+}
+
+// Process-wide Strassen setting of the fused Cholesky + inverse (vgposp_potrf_set_strassen) and
+// the size threshold of vgposp_gemm_strassen.  Like the split depth above: set explicitly, never
+// from the environment, and only between a workspace query and its use, consistently.
+// Defaults from the 65k step's A/B (DESIGN.md §4 "Strassen", profiles/strassen_ab.json): 8192 / 2
+// levels 2,862 ms, 8192 / 1 2,902, 16384 / 1 or 2 2,951, classical 3,067.
+static std::atomic<int64_t> g_strassen_min_dim{8192};
+static std::atomic<int> g_strassen_levels{2};
+
+static bool strassen_dims_ok(int64_t m, int64_t n, int64_t k, int64_t min_dim) {
+  return m % 256 == 0 && n % 256 == 0 && k % 256 == 0 && m >= min_dim && n >= min_dim &&
+         k >= min_dim && std::max({m, n, k}) / 32 <= 65535;  // (the add kernel's grid.y)
+}
+
+// Doubles of operand temporaries: one A-side and one B-side per level actually taken.
+int64_t gemm_strassen_ws_elems(int64_t m, int64_t n, int64_t k, int levels, int64_t min_dim) {
+  int64_t e = 0;
+  for (; levels > 0 && strassen_dims_ok(m, n, k, min_dim); --levels) {
+    m /= 2, n /= 2, k /= 2;
+    e += m * k + k * n;
+  }
+  return e;
+}
+
+// One classical launch of op(A) op(B) into nd destinations.
+static int gemm_launch_multi(int transa, int transb, int64_t m, int64_t n, int64_t k,
+                             const double* A, int64_t lda, const double* B, int64_t ldb,
+                             const GemmDst* d, int nd, hipStream_t stream) {
+  if (nd == 1)
+    return gemm_launch(transa, transb, m, n, k, d[0].alpha, A, lda, B, ldb, d[0].beta, d[0].C,
+                       d[0].ld, VGPOSP_FULL, 0, 0, stream);
+  GemmParams p{m, n, k, d[0].alpha, d[0].beta, A, lda, B, ldb, d[0].C, d[0].ld, VGPOSP_FULL, 0, 0,
+               1, 0, 0, nullptr, 0, 0, 0, 0, tl_gemm_abort};
+  GemmExtra x{};
+  x.n = nd - 1;
+  double outs = d[0].beta != 0.0 ? 2.0 : 1.0;
+  for (int i = 1; i < nd; ++i) {
+    x.C[i - 1] = d[i].C;
+    x.ld[i - 1] = d[i].ld;
+    x.alpha[i - 1] = d[i].alpha;
+    x.beta[i - 1] = d[i].beta;
+    outs += d[i].beta != 0.0 ? 2.0 : 1.0;
+  }
+  const int tm = (int)ceil_div(m, GBM), tn = (int)ceil_div(n, GBN);
+  const int64_t nblk = (int64_t)tm * tn;
+  // the flops of the launch actually made (a Strassen product is a smaller classical product)
+  ProfScope ps(gemm_class_name(transa, transb, 0, 0, nblk >= 512), stream,
+               2.0 * (double)m * (double)n * (double)k,
+               8.0 * ((double)m * k + (double)k * n + outs * (double)m * n));
+  const dim3 g1((unsigned)nblk), b1(64 * GemmCfg<1>::NW);
+  if (!transa && !transb) hipLaunchKernelGGL((gemm_glds_multi_kernel<false, false>), g1, b1, 0, stream, p, x, tm, tn);
+  else if (!transa) hipLaunchKernelGGL((gemm_glds_multi_kernel<false, true>), g1, b1, 0, stream, p, x, tm, tn);
+  else if (!transb) hipLaunchKernelGGL((gemm_glds_multi_kernel<true, false>), g1, b1, 0, stream, p, x, tm, tn);
+  else hipLaunchKernelGGL((gemm_glds_multi_kernel<true, true>), g1, b1, 0, stream, p, x, tm, tn);
+  VG_LAUNCH_CHECK();
+  return 0;
+}
+
+// An operand of a Strassen product: quadrant x, or quadrant x + sgn * quadrant y (y >= 0).
+struct StrassenOpnd {
+  int x, y;
+  double sgn;
+};
+struct StrassenProd {
+  StrassenOpnd a, b;
+  int nq;        // quadrants of C the product lands in
+  int q[2];      // 2 i + j
+  double s[2];   // its sign there
+};
+static const StrassenProd STRASSEN[7] = {
+    {{0, 3, 1.0}, {0, 3, 1.0}, 2, {0, 3}, {1.0, 1.0}},    // M1
+    {{2, 3, 1.0}, {0, -1, 0.0}, 2, {2, 3}, {1.0, -1.0}},  // M2
+    {{0, -1, 0.0}, {1, 3, -1.0}, 2, {1, 3}, {1.0, 1.0}},  // M3
+    {{3, -1, 0.0}, {2, 0, -1.0}, 2, {0, 2}, {1.0, 1.0}},  // M4
+    {{0, 1, 1.0}, {3, -1, 0.0}, 2, {0, 1}, {-1.0, 1.0}},  // M5
+    {{2, 0, -1.0}, {0, 1, 1.0}, 1, {3, 3}, {1.0, 0.0}},   // M6
+    {{1, 3, -1.0}, {2, 3, 1.0}, 1, {0, 0}, {1.0, 0.0}},   // M7
+};
+
+static int strassen_rec(int transa, int transb, int64_t m, int64_t n, int64_t k, const double* A,
+                        int64_t lda, const double* B, int64_t ldb, const GemmDst* dst, int nd,
+                        int levels, int64_t min_dim, double* ws, hipStream_t s) {
+  if (levels <= 0 || 2 * nd > 1 + GEMM_XDST || !strassen_dims_ok(m, n, k, min_dim))
+    return gemm_launch_multi(transa, transb, m, n, k, A, lda, B, ldb, dst, nd, s);
+  const int64_t m2 = m / 2, n2 = n / 2, k2 = k / 2;
+  // stored shapes of the operand quadrants (and of the temporaries, packed)
+  const int64_t ar = transa ? k2 : m2, ac = transa ? m2 : k2;
+  const int64_t br = transb ? n2 : k2, bc = transb ? k2 : n2;
+  double* const TA = ws;
+  double* const TB = TA + m2 * k2;
+  double* const next = TB + k2 * n2;
+  // quadrant (i, j) of op(X) sits at block (j, i) of a transposed store
+  auto Aq = [&](int q) {
+    const int i = q >> 1, j = q & 1;
+    return transa ? A + j * ar * lda + i * ac : A + i * ar * lda + j * ac;
+  };
+  auto Bq = [&](int q) {
+    const int i = q >> 1, j = q & 1;
+    return transb ? B + j * br * ldb + i * bc : B + i * br * ldb + j * bc;
+  };
+  bool touched[4] = {false, false, false, false};
+  for (const StrassenProd& pr : STRASSEN) {
+    int rc;
+    const double* a = Aq(pr.a.x);
+    int64_t la = lda;
+    if (pr.a.y >= 0) {
+      if ((rc = strassen_add(ar, ac, a, lda, Aq(pr.a.y), lda, pr.a.sgn, TA, ac, s))) return rc;
+      a = TA, la = ac;
+    }
+    const double* b = Bq(pr.b.x);
+    int64_t lb = ldb;
+    if (pr.b.y >= 0) {
+      if ((rc = strassen_add(br, bc, b, ldb, Bq(pr.b.y), ldb, pr.b.sgn, TB, bc, s))) return rc;
+      b = TB, lb = bc;
+    }
+    GemmDst sub[1 + GEMM_XDST];
+    int ns = 0;
+    for (int d = 0; d < nd; ++d)
+      for (int t = 0; t < pr.nq; ++t) {
+        const int q = pr.q[t];
+        sub[ns++] = GemmDst{dst[d].C + (q >> 1) * m2 * dst[d].ld + (q & 1) * n2, dst[d].ld,
+                            pr.s[t] * dst[d].alpha, touched[q] ? 1.0 : dst[d].beta};
+      }
+    for (int t = 0; t < pr.nq; ++t) touched[pr.q[t]] = true;
+    if ((rc = strassen_rec(transa, transb, m2, n2, k2, a, la, b, lb, sub, ns, levels - 1, min_dim,
+                           next, s)))
+      return rc;
+  }
+  return 0;
+}
+
+// C = alpha op(A) op(B) + beta C (full C, dense operands) with up to `levels` Strassen levels on
+// the products whose m, n and k are all >= min_dim; ws holds gemm_strassen_ws_elems doubles (a
+// smaller one means fewer levels).  C must not overlap A or B.
+int gemm_strassen(int transa, int transb, int64_t m, int64_t n, int64_t k, double alpha,
+                  const double* A, int64_t lda, const double* B, int64_t ldb, double beta, double* C,
+                  int64_t ldc, int levels, int64_t min_dim, double* ws, int64_t ws_elems,
+                  hipStream_t stream) {
+  levels = std::min(levels, 2);
+  while (levels > 0 && (ws == nullptr || gemm_strassen_ws_elems(m, n, k, levels, min_dim) > ws_elems))
+    --levels;
+  const bool ok = levels > 0 && strassen_dims_ok(m, n, k, min_dim) && aligned16(A, lda) &&
+                  aligned16(B, ldb) && aligned16(C, ldc) && aligned16(ws, 2);
+  if (!ok)
+    return gemm_launch(transa, transb, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, VGPOSP_FULL, 0,
+                       0, stream);
+  const GemmDst d{C, ldc, alpha, beta};
+  return strassen_rec(transa, transb, m, n, k, A, lda, B, ldb, &d, 1, levels, min_dim, ws, stream);
+}
+
+void gemm_strassen_config(int64_t* min_dim, int* levels) {
+  *min_dim = g_strassen_min_dim.load(std::memory_order_relaxed);
+  *levels = g_strassen_levels.load(std::memory_order_relaxed);
+}
+
 void gemm_set_abort(const int* flag) { tl_gemm_abort = flag; }
 
 int gemm_auto_splits(int64_t m, int64_t n, int64_t k, int uplo_c, int transa) {
@@ -1025,6 +1269,59 @@ extern "C" int vgposp_gemm(int transa, int transb, int64_t m, int64_t n, int64_t
   VG_CHECK_ARG(uplo_c == VGPOSP_FULL || (uplo_c == VGPOSP_LOWER && m == n), 14);
   return gemm_launch(transa, transb, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, uplo_c, tri_a,
                      tri_b, as_stream(stream));
+}
+
+extern "C" int vgposp_potrf_set_strassen(int64_t min_dim, int levels) {
+  using namespace vgposp;
+  clear_error();
+  VG_CHECK_ARG(min_dim >= 256 && min_dim % 256 == 0, 1);
+  VG_CHECK_ARG(levels >= 0 && levels <= 2, 2);
+  g_strassen_min_dim.store(min_dim, std::memory_order_relaxed);
+  g_strassen_levels.store(levels, std::memory_order_relaxed);
+  return 0;
+}
+
+extern "C" int vgposp_potrf_strassen(int64_t* min_dim, int* levels) {
+  using namespace vgposp;
+  clear_error();
+  VG_CHECK_ARG(min_dim != nullptr, 1);
+  VG_CHECK_ARG(levels != nullptr, 2);
+  gemm_strassen_config(min_dim, levels);
+  return 0;
+}
+
+extern "C" size_t vgposp_gemm_strassen_workspace_bytes(int64_t m, int64_t n, int64_t k,
+                                                       int levels) {
+  using namespace vgposp;
+  if (m <= 0 || n <= 0 || k <= 0 || levels <= 0) return 0;
+  return 8 * (size_t)gemm_strassen_ws_elems(m, n, k, std::min(levels, 2),
+                                            g_strassen_min_dim.load(std::memory_order_relaxed));
+}
+
+extern "C" int vgposp_gemm_strassen(int transa, int transb, int64_t m, int64_t n, int64_t k,
+                                    double alpha, const double* A, int64_t lda, const double* B,
+                                    int64_t ldb, double beta, double* C, int64_t ldc, int levels,
+                                    void* ws, size_t ws_bytes, void* stream) {
+  using namespace vgposp;
+  clear_error();
+  VG_CHECK_ARG(m >= 0, 3);
+  VG_CHECK_ARG(n >= 0, 4);
+  VG_CHECK_ARG(k >= 0, 5);
+  VG_CHECK_ARG(A != nullptr || m == 0 || k == 0, 7);
+  VG_CHECK_ARG(lda >= (transa ? (m > 0 ? m : 1) : (k > 0 ? k : 1)), 8);
+  VG_CHECK_ARG(B != nullptr || n == 0 || k == 0, 9);
+  VG_CHECK_ARG(ldb >= (transb ? (k > 0 ? k : 1) : (n > 0 ? n : 1)), 10);
+  VG_CHECK_ARG(C != nullptr || m == 0 || n == 0, 12);
+  VG_CHECK_ARG(ldc >= (n > 0 ? n : 1), 13);
+  VG_CHECK_ARG(levels >= 0 && levels <= 2, 14);
+  const size_t need = vgposp_gemm_strassen_workspace_bytes(m, n, k, levels);
+  if (need > 0 && (ws == nullptr || ws_bytes < need)) {
+    set_error("vgposp_gemm_strassen: workspace %zu < %zu bytes", ws_bytes, need);
+    return VGPOSP_E_WS;
+  }
+  return gemm_strassen(transa, transb, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, levels,
+                       g_strassen_min_dim.load(std::memory_order_relaxed),
+                       static_cast<double*>(ws), (int64_t)(ws_bytes / 8), as_stream(stream));
 }
 
 extern "C" size_t vgposp_gemm_batched_workspace_bytes(int64_t m, int64_t n, int64_t k, int uplo_c,

@@ -23,7 +23,7 @@
 namespace vgposp {
 
 int potrf_one(double* A, int64_t n, int64_t lda, int invert, double* diag_out, int* info,
-              void* ws, hipStream_t stream, bool early = false);
+              void* ws, hipStream_t stream, bool early = false, bool strassen = true);
 size_t potrf_ws_bytes(int64_t n);
 int partial_inverse(double* A, int64_t n, int64_t lda, int64_t c0, int64_t c1, double* tmp,
                     void* ws, hipStream_t s);
@@ -675,8 +675,9 @@ extern "C" int vgposp_greedy_init_slab(double* Sigma, int64_t n, int64_t lda, in
                                  ws_bytes, stream);
   if (rc) return rc;
   GreedyWS w = greedy_layout(ws, n, kmax);
+  // (the slab path stays classical, like the sharded factorization it stands in for)
   if ((rc = potrf_one(Sigma, n, lda, /*invert=*/0, nullptr, info, greedy_fact_ws(ws, w, n),
-                      as_stream(stream))))
+                      as_stream(stream), /*early=*/false, /*strassen=*/false)))
     return rc;
   return vgposp_greedy_finish_slab(Sigma, n, lda, kmax, c0, c1, tmp, tmp_bytes, ws, ws_bytes,
                                    stream);

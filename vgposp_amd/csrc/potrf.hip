@@ -16,6 +16,8 @@
 // (gp_functions.py:166-172, main.py:105) and, through L^-1, the per-candidate SVD pinv of
 // placement_algorithm2.denominator (placement_algorithm2.py:399-413).
 // The strictly upper triangle is never read or written.
+#include <algorithm>
+
 #include "common.h"
 
 namespace vgposp {
@@ -31,6 +33,12 @@ int gemm_launch_batched(int transa, int transb, int64_t m, int64_t n, int64_t k,
                         int64_t sB, double beta, double* C, int64_t ldc, int64_t sC, int uplo_c,
                         int tri_a, int tri_b, int nsplit, double* part, int64_t sP, int batch,
                         hipStream_t stream);
+int gemm_strassen(int transa, int transb, int64_t m, int64_t n, int64_t k, double alpha,
+                  const double* A, int64_t lda, const double* B, int64_t ldb, double beta, double* C,
+                  int64_t ldc, int levels, int64_t min_dim, double* ws, int64_t ws_elems,
+                  hipStream_t stream);
+int64_t gemm_strassen_ws_elems(int64_t m, int64_t n, int64_t k, int levels, int64_t min_dim);
+void gemm_strassen_config(int64_t* min_dim, int* levels);
 
 constexpr int NB = 128;        // leaf size (== GEMM tile, so trsm leaves are in place)
 
@@ -345,6 +353,11 @@ struct Fact {
   // stop early on a failed pivot: every later leaf / GEMM launch reads `info` on the device and
   // exits once it is set (no host synchronisation)
   bool early = false;
+  // Strassen scratch (potrf_one only; null = every product classical): str_elems doubles, up to
+  // str_levels levels on plain products whose dimensions are all >= str_min
+  double* str_ws = nullptr;
+  int64_t str_elems = 0, str_min = 0;
+  int str_levels = 0;
   double* leaf(int64_t col0) const { return linv_all + (col0 / NB) * NB * NB; }
   double* xblk(int64_t col0) const { return xinv + col0 * NBI; }
   int64_t stride(const void* p) const {
@@ -371,6 +384,10 @@ constexpr int64_t PART_ELEMS_BATCHED = 2 << 20;
 static int pgemm(const Fact& f, int transa, int transb, int64_t m, int64_t n, int64_t k,
                  double alpha, const double* A, int64_t lda, const double* B, int64_t ldb,
                  double beta, double* C, int64_t ldc, int uplo_c, int tri_a, int tri_b) {
+  if (f.str_ws != nullptr && f.batch == 1 && uplo_c == VGPOSP_FULL && !tri_a && !tri_b &&
+      gemm_strassen_ws_elems(m, n, k, 1, f.str_min) > 0)
+    return gemm_strassen(transa, transb, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, f.str_levels,
+                         f.str_min, f.str_ws, f.str_elems, f.s);
   int sp = f.part ? gemm_auto_splits(m, n, k, uplo_c, transa) : 1;
   while (sp > 1 && (int64_t)sp * m * n > f.part_elems) --sp;
   if (f.batch > 1)
@@ -379,6 +396,58 @@ static int pgemm(const Fact& f, int transa, int transb, int64_t m, int64_t n, in
                                sp > 1 ? f.part : nullptr, f.sW, f.batch, f.s);
   return gemm_launch_split(transa, transb, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, uplo_c,
                            tri_a, tri_b, sp, sp > 1 ? f.part : nullptr, f.s);
+}
+
+// With Strassen scratch, a structured product whose plain part would be eligible is split once
+// into two half-size structured products and that plain product (half of its flops), and so on
+// down: the plain parts then go through gemm_strassen.  Without scratch, or below the threshold,
+// each is the single structured launch.
+static bool split_plain(const Fact& f, int64_t m, int64_t n, int64_t k) {
+  return f.str_ws != nullptr && f.batch == 1 && gemm_strassen_ws_elems(m, n, k, 1, f.str_min) > 0;
+}
+
+// C (n x n, lower) = alpha A A^T + beta C,  A n x k
+static int psyrk(const Fact& f, int64_t n, int64_t k, double alpha, const double* A, int64_t lda,
+                 double beta, double* C, int64_t ldc) {
+  const int64_t h = n / 2;
+  if (n % 2 != 0 || !split_plain(f, h, h, k))
+    return pgemm(f, 0, 1, n, n, k, alpha, A, lda, A, lda, beta, C, ldc, VGPOSP_LOWER, 0, 0);
+  int rc;
+  if ((rc = psyrk(f, h, k, alpha, A, lda, beta, C, ldc))) return rc;
+  if ((rc = pgemm(f, 0, 1, h, h, k, alpha, A + h * lda, lda, A, lda, beta, C + h * ldc, ldc,
+                  VGPOSP_FULL, 0, 0)))
+    return rc;
+  return psyrk(f, h, k, alpha, A + h * lda, lda, beta, C + h * ldc + h, ldc);
+}
+
+// W (m x n) = alpha L X + beta W,  X n x n lower (stored [k][j]), L m x n
+static int ptrmm_b(const Fact& f, int64_t m, int64_t n, double alpha, const double* L, int64_t ldl,
+                   const double* X, int64_t ldx, double beta, double* W, int64_t ldw) {
+  const int64_t h = n / 2;
+  if (n % 2 != 0 || !split_plain(f, m, h, h))
+    return pgemm(f, 0, 0, m, n, n, alpha, L, ldl, X, ldx, beta, W, ldw, VGPOSP_FULL, 0, 1);
+  int rc;
+  // W1 = L1 Xa + L2 Xb,  W2 = L2 Xc
+  if ((rc = ptrmm_b(f, m, h, alpha, L, ldl, X, ldx, beta, W, ldw))) return rc;
+  if ((rc = pgemm(f, 0, 0, m, h, h, alpha, L + h, ldl, X + h * ldx, ldx, 1.0, W, ldw, VGPOSP_FULL,
+                  0, 0)))
+    return rc;
+  return ptrmm_b(f, m, h, alpha, L + h, ldl, X + h * ldx + h, ldx, beta, W + h, ldw);
+}
+
+// Y (m x n) = alpha X W + beta Y,  X m x m lower (stored [i][k]), W m x n
+static int ptrmm_a(const Fact& f, int64_t m, int64_t n, double alpha, const double* X, int64_t ldx,
+                   const double* W, int64_t ldw, double beta, double* Y, int64_t ldy) {
+  const int64_t h = m / 2;
+  if (m % 2 != 0 || !split_plain(f, h, n, h))
+    return pgemm(f, 0, 0, m, n, m, alpha, X, ldx, W, ldw, beta, Y, ldy, VGPOSP_FULL, 1, 0);
+  int rc;
+  // Y1 = Xa W1,  Y2 = Xc W2 + Xb W1
+  if ((rc = ptrmm_a(f, h, n, alpha, X, ldx, W, ldw, beta, Y, ldy))) return rc;
+  if ((rc = ptrmm_a(f, h, n, alpha, X + h * ldx + h, ldx, W + h * ldw, ldw, beta, Y + h * ldy, ldy)))
+    return rc;
+  return pgemm(f, 0, 0, h, n, h, alpha, X + h * ldx, ldx, W, ldw, 1.0, Y + h * ldy, ldy,
+               VGPOSP_FULL, 0, 0);
 }
 
 // dst (n x n lower, ldd) <- src (lower, lds); zero_upper: also zero dst's strict upper triangle
@@ -465,10 +534,9 @@ static int trtri_rec(const Fact& f, double* A, int64_t lda, int64_t n, int64_t c
   if ((rc = trtri_rec(f, A, lda, n1, col0, blocks, done))) return rc;
   if ((rc = trtri_rec(f, A22, lda, n2, col0 + n1, blocks, done))) return rc;
   // W = L21 X11   (X11 lower, stored [k][j])
-  if ((rc = pgemm(f, 0, 0, n2, n1, n1, 1.0, A21, lda, A, lda, 0.0, f.work, n1, VGPOSP_FULL, 0, 1)))
-    return rc;
+  if ((rc = ptrmm_b(f, n2, n1, 1.0, A21, lda, A, lda, 0.0, f.work, n1))) return rc;
   // X21 = -X22 W  (X22 lower, stored [i][k])
-  return pgemm(f, 0, 0, n2, n1, n2, -1.0, A22, lda, f.work, n1, 0.0, A21, lda, VGPOSP_FULL, 1, 0);
+  return ptrmm_a(f, n2, n1, -1.0, A22, lda, f.work, n1, 0.0, A21, lda);
 }
 
 // Level-batched inverse of the small subtrees (single matrix, n = NBI 2^j): every node of order s
@@ -534,9 +602,7 @@ static int potrf_rec(const Fact& f, double* A, int64_t n, int64_t col0, bool blo
   const bool sub = blocks && !whole;  // inside a block the leaf-level path is used
   if ((rc = potrf_rec(f, A, n1, col0, sub))) return rc;
   if ((rc = trsm_rec(f, A21, n2, f.lda, A, n1, col0, sub))) return rc;
-  if ((rc = pgemm(f, 0, 1, n2, n2, n1, -1.0, A21, f.lda, A21, f.lda, 1.0, A22, f.lda,
-                  VGPOSP_LOWER, 0, 0)))
-    return rc;
+  if ((rc = psyrk(f, n2, n1, -1.0, A21, f.lda, 1.0, A22, f.lda))) return rc;
   if ((rc = potrf_rec(f, A22, n2, col0 + n1, sub))) return rc;
   if (!whole) return 0;
   // this block's inverse: X <- L (zero above the diagonal), then the leaf-level trtri in place
@@ -545,12 +611,80 @@ static int potrf_rec(const Fact& f, double* A, int64_t n, int64_t col0, bool blo
   return trtri_rec(f, X, NBI, n, col0, false);
 }
 
-size_t potrf_ws_bytes(int64_t n) {
+// The workspace every entry point lays out (make_fact): leaf inverses | trtri scratch | block
+// inverses + TRSM scratch | split-K partials.
+static size_t potrf_ws_base(int64_t n) {
   const int64_t leaves = (n + NB - 1) / NB;
   const int64_t n1 = n > NB ? split_point(n) : 0;
   const int64_t blk = n > NBI ? 2 * n * NBI : 0;  // xinv + tmp
   const int64_t part = n > NB ? PART_ELEMS : 0;
   return (size_t)(leaves * NB * NB + n1 * (n - n1) + blk + part + 64) * sizeof(double);
+}
+
+// Strassen scratch of potrf_one, appended AFTER that layout (the sharded entry points and the
+// slab finish read fixed places in it): the largest operand-temporary need over the plain
+// products that potrf_rec / trsm_rec / psyrk and trtri_rec / ptrmm_b / ptrmm_a launch for this n
+// (a walk over the same splits, a few hundred nodes at n = 65,536).  0 when no product is
+// eligible: nothing is appended then and every launch is the classical one.
+struct StrassenNeed {
+  int64_t min_dim;
+  int levels;
+  int64_t need = 0;
+  bool split(int64_t m, int64_t n, int64_t k) const {
+    return gemm_strassen_ws_elems(m, n, k, 1, min_dim) > 0;
+  }
+  void plain(int64_t m, int64_t n, int64_t k) {
+    need = std::max(need, gemm_strassen_ws_elems(m, n, k, levels, min_dim));
+  }
+  void syrk(int64_t n, int64_t k) {
+    const int64_t h = n / 2;
+    if (n % 2 != 0 || !split(h, h, k)) return;
+    plain(h, h, k);
+    syrk(h, k);
+  }
+  void trmm_b(int64_t m, int64_t n) {
+    const int64_t h = n / 2;
+    if (n % 2 != 0 || !split(m, h, h)) return;
+    plain(m, h, h);
+    trmm_b(m, h);
+  }
+  void trmm_a(int64_t m, int64_t n) {
+    const int64_t h = m / 2;
+    if (m % 2 != 0 || !split(h, n, h)) return;
+    plain(h, n, h);
+    trmm_a(h, n);
+  }
+  void trsm(int64_t m, int64_t nL) {
+    if (nL <= NBI) return;
+    const int64_t a = split_point(nL), b = nL - a;
+    plain(m, b, a);
+    trsm(m, a);
+    if (b != a) trsm(m, b);
+  }
+  void node(int64_t n) {  // potrf_rec and trtri_rec of an order-n diagonal block
+    if (n <= NBI || n < 2 * min_dim) return;  // (every product below has a dimension < min_dim)
+    const int64_t n1 = split_point(n), n2 = n - n1;
+    trsm(n2, n1);
+    syrk(n2, n1);
+    trmm_b(n2, n1);
+    trmm_a(n2, n1);
+    node(n1);
+    if (n2 != n1) node(n2);
+  }
+};
+
+static int64_t potrf_strassen_elems(int64_t n, int64_t min_dim, int levels) {
+  if (levels <= 0 || n <= NBI) return 0;
+  StrassenNeed s{min_dim, levels};
+  s.node(n);
+  return s.need;
+}
+
+size_t potrf_ws_bytes(int64_t n) {
+  int64_t min_dim;
+  int levels;
+  gemm_strassen_config(&min_dim, &levels);
+  return potrf_ws_base(n) + (size_t)potrf_strassen_elems(n, min_dim, levels) * sizeof(double);
 }
 
 static int ensure_leaf_attr() {
@@ -590,7 +724,7 @@ static Fact make_fact(int64_t n, int64_t lda, void* ws, double* diag_out, int* i
 // partials per matrix would not fit).
 size_t potrf_ws_bytes_opt(int64_t n, bool use_part) {
   const int64_t part = n > NB ? (use_part ? PART_ELEMS_BATCHED : 0) : 0;
-  return potrf_ws_bytes(n) - (size_t)((n > NB ? PART_ELEMS : 0) - part) * sizeof(double);
+  return potrf_ws_base(n) - (size_t)((n > NB ? PART_ELEMS : 0) - part) * sizeof(double);
 }
 
 int potrf_batched(double* A, int64_t n, int64_t lda, int64_t sA, int batch, int invert,
@@ -621,11 +755,22 @@ int potrf_batched(double* A, int64_t n, int64_t lda, int64_t sA, int batch, int 
 }
 
 int potrf_one(double* A, int64_t n, int64_t lda, int invert, double* diag_out, int* info,
-              void* ws, hipStream_t stream, bool early) {
+              void* ws, hipStream_t stream, bool early, bool strassen) {
   if (int rc = ensure_leaf_attr()) return rc;
   const bool blocks = n > NBI;
   Fact f = make_fact(n, lda, ws, diag_out, info, stream);
   f.early = early;
+  if (strassen) {  // the setting is read once: scratch size, threshold and levels belong together
+    int64_t min_dim;
+    int levels;
+    gemm_strassen_config(&min_dim, &levels);
+    if (const int64_t se = potrf_strassen_elems(n, min_dim, levels)) {
+      f.str_ws = static_cast<double*>(ws) + potrf_ws_base(n) / sizeof(double);
+      f.str_elems = se;
+      f.str_min = min_dim;
+      f.str_levels = levels;
+    }
+  }
   AbortScope scope(early ? info : nullptr);
   int rc = potrf_rec(f, A, n, 0, blocks);
   if (rc || !invert) return rc;
@@ -843,7 +988,11 @@ extern "C" size_t vgposp_potrf_workspace_bytes(int64_t n) {
 }
 
 extern "C" size_t vgposp_potrf_batched_workspace_bytes(int64_t n, int batch) {
-  return n > 0 && batch > 0 ? (size_t)batch * vgposp::potrf_ws_bytes(n) : 0;
+  // one recursion over the batch at the per-matrix stride of potrf_batched (16 MiB of split-K
+  // partials each, never Strassen scratch); never less than one single-matrix workspace
+  return n > 0 && batch > 0 ? std::max((size_t)batch * vgposp::potrf_ws_bytes_opt(n, true),
+                                       vgposp::potrf_ws_bytes(n))
+                            : 0;
 }
 
 extern "C" int vgposp_potrf_lower(double* A, int64_t n, int64_t lda, int64_t stride, int batch,
@@ -879,11 +1028,11 @@ extern "C" int vgposp_potrf_lower(double* A, int64_t n, int64_t lda, int64_t str
     VG_LAUNCH_CHECK();
     return 0;
   }
-  if (batch > 1 && ws_bytes >= (size_t)batch * potrf_ws_bytes(n))
+  if (batch > 1 && ws_bytes >= vgposp_potrf_batched_workspace_bytes(n, (int)batch))
     return potrf_batched(A, n, lda, stride, batch, invert, diag_out, info, ws, s, true);
   for (int b = 0; b < batch; ++b) {
     int rc = potrf_one(A + b * stride, n, lda, invert, diag_out ? diag_out + (int64_t)b * n : nullptr,
-                       info + b, ws, s, false);
+                       info + b, ws, s, false, true);
     if (rc) return rc;
   }
   return 0;
