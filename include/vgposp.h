@@ -114,6 +114,12 @@ size_t vgposp_gemm_splitk_workspace_bytes(int64_t m, int64_t n, int64_t k, int u
  * workspace must see the same value.  Not read from the environment. */
 int vgposp_gemm_set_split_depth(int min_k);
 int vgposp_gemm_split_depth(void);
+/* Process-wide choice of the fast GEMM kernels' K loop for products with transa = 0 (every
+ * entry point that launches them, grouped launches excepted): 0 = the compiler-scheduled C++
+ * loop, 1 = the hand-scheduled loop for the K-tiles that need no mask.  Both give bit-identical
+ * results.  Read at launch; not read from the environment. */
+int vgposp_gemm_set_kloop(int kloop);
+int vgposp_gemm_kloop(void);
 int vgposp_gemm_splitk(int transa, int transb, int64_t m, int64_t n, int64_t k, double alpha,
                        const double* A, int64_t lda, const double* B, int64_t ldb, double beta,
                        double* C, int64_t ldc, int uplo_c, int tri_a, int tri_b, int splits,

@@ -322,15 +322,188 @@ constexpr int glds_smem_elems() {
   return GemmCfg<CFG>::NST * (GemmCfg<CFG>::NSUB + 1) * OPND_ELEMS;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Hand-scheduled interior K-tiles (vgposp_gemm_set_kloop(1); TA = false, 2-stage ring).  One asm
+// statement (kloop_pair) takes two K-tiles, the first in ring stage 0 and the second in stage 1,
+// so that both stages are immediates.  Each K-tile t, out of stage S, leaves tile t + 1 ready:
+//   reads(1) wait MFMA(0) [P1: A pieces] reads(2) wait MFMA(1) [P1: B pieces] reads(3) wait MFMA(2)
+//   vmcnt(0) lgkmcnt(0) s_barrier [P0: pieces] reads(0 of t + 1) [P2: pieces] MFMA(3)
+// reads(s) = the slice's fragment reads, issued one slice ahead into the other of two fragment
+// buffers and retired by counted lgkmcnt waits; MFMA(s) = the 16 MFMAs of slice s, in the C++
+// loop's (i, j) order, so every accumulator sees the same products in the same k order and the
+// result is bit-identical to the C++ loop.  The one barrier sits before the last slice's MFMAs:
+// that slice's fragments are in registers by then, so behind it stage S is free (for tile t + 2)
+// and stage S^1 holds tile t + 1.
+// The statement's registers are fixed, because it names sub-registers of vector operands:
+//   v[208:215] per-lane source offsets of this wave's 8 pieces (A 0..3, B 0..3), constant
+//   v[216:223] per-lane LDS fragment bases: A k-slice 0..3, then B k-slice 0..3 (stored n x k)
+//              or B fragments {0, 2} / {1, 3} (stored k x n, where the k-slice is an immediate)
+//   v[224:239] fragment buffer 0 (a0..a3, b0..b3): slice 0 on entry, slice 0 of tile t + 1 on exit
+//   v[240:255] fragment buffer 1 (clobbered)
+// The A and B source bases of the tile to load are scalar operands, advanced by a uniform stride
+// per K-tile in the C++ around the statement (scalar adds); the pieces need no clamp selects
+// (interior tiles have no k clamp, the row clamp is folded into the constant offsets).
+// Stage, fragment and row group are immediate offset fields; M0 is saved and restored.
+// VGPOSP_KLOOP_PIECES places the next LDS-DMA pieces (measured: DESIGN.md §4 "Hand-scheduled K
+// loop"; 1 is the fastest on every layout):
+//   0  all eight directly behind the barrier, for tile t + 2 (one tile further ahead)
+//   1  four behind slice 0's MFMAs and four behind slice 1's, for tile t + 1
+//   2  all eight behind the barrier and tile t + 1's slice-0 reads, for tile t + 2
+// VGPOSP_KLOOP_DEFAULT is the setting a process starts with.
+// ---------------------------------------------------------------------------------------------
+#ifndef VGPOSP_KLOOP_PIECES
+#define VGPOSP_KLOOP_PIECES 1
+#endif
+constexpr int KLOOP_PIECES = VGPOSP_KLOOP_PIECES;
+#ifndef VGPOSP_KLOOP_DEFAULT
+#define VGPOSP_KLOOP_DEFAULT 1
+#endif
+static_assert(KLOOP_PIECES >= 0 && KLOOP_PIECES <= 2, "piece placement 0, 1 or 2");
+
+typedef double dbl8 __attribute__((ext_vector_type(8)));
+typedef unsigned int u32x8 __attribute__((ext_vector_type(8)));
+
+#define KL_M(A, B, C) "v_mfma_f64_16x16x4_f64 %[" #C "], v[" A "], v[" B "], %[" #C "]\n\t"
+#define KL_M4(A, I, B0, B1, B2, B3) \
+  KL_M(A, B0, c##I##0) KL_M(A, B1, c##I##1) KL_M(A, B2, c##I##2) KL_M(A, B3, c##I##3)
+#define KL_MFMA_F0                                               \
+  KL_M4("224:225", 0, "232:233", "234:235", "236:237", "238:239") \
+  KL_M4("226:227", 1, "232:233", "234:235", "236:237", "238:239") \
+  KL_M4("228:229", 2, "232:233", "234:235", "236:237", "238:239") \
+  KL_M4("230:231", 3, "232:233", "234:235", "236:237", "238:239")
+#define KL_MFMA_F1                                               \
+  KL_M4("240:241", 0, "248:249", "250:251", "252:253", "254:255") \
+  KL_M4("242:243", 1, "248:249", "250:251", "252:253", "254:255") \
+  KL_M4("244:245", 2, "248:249", "250:251", "252:253", "254:255") \
+  KL_M4("246:247", 3, "248:249", "250:251", "252:253", "254:255")
+// four fragments of a k-contiguous image: rows 16 apart are 4 x 512 bytes apart (U: the stage's
+// and the operand's offset in 512-byte units)
+#define KL_RKC(D0, D1, BASE, U)                                                   \
+  "ds_read2st64_b64 v[" D0 "], v" BASE " offset0:" U "+0 offset1:" U "+4\n\t" \
+  "ds_read2st64_b64 v[" D1 "], v" BASE " offset0:" U "+8 offset1:" U "+12\n\t"
+// four fragments of B stored k x n: fragments {0, 2} and {1, 3} are 256 bytes apart from their
+// bases (the swizzle exchanges 0/1 and 2/3 on odd k), a k-slice 4096 bytes (SB: stage bytes)
+#define KL_RMC(D0, D1, D2, D3, KS, SB)                                        \
+  "ds_read_b64 v[" D0 "], v220 offset:" SB "+16384+" #KS "*4096\n\t"      \
+  "ds_read_b64 v[" D1 "], v221 offset:" SB "+16384+" #KS "*4096\n\t"      \
+  "ds_read_b64 v[" D2 "], v220 offset:" SB "+16384+" #KS "*4096+256\n\t"  \
+  "ds_read_b64 v[" D3 "], v221 offset:" SB "+16384+" #KS "*4096+256\n\t"
+// slice KS of the tile at stage symbol SR (512-byte units) / SB (bytes) into buffer 0 or 1
+#define KL_RD0_NT(KS, SR, SB) \
+  KL_RKC("224:227", "228:231", KL_LA##KS, SR) KL_RKC("232:235", "236:239", KL_LB##KS, SR "+32")
+#define KL_RD1_NT(KS, SR, SB) \
+  KL_RKC("240:243", "244:247", KL_LA##KS, SR) KL_RKC("248:251", "252:255", KL_LB##KS, SR "+32")
+#define KL_RD0_NN(KS, SR, SB)                  \
+  KL_RKC("224:227", "228:231", KL_LA##KS, SR) \
+  KL_RMC("232:233", "234:235", "236:237", "238:239", KS, SB)
+#define KL_RD1_NN(KS, SR, SB)                  \
+  KL_RKC("240:243", "244:247", KL_LA##KS, SR) \
+  KL_RMC("248:249", "250:251", "252:253", "254:255", KS, SB)
+#define KL_LA0 "216"
+#define KL_LA1 "217"
+#define KL_LA2 "218"
+#define KL_LA3 "219"
+#define KL_LB0 "220"
+#define KL_LB1 "221"
+#define KL_LB2 "222"
+#define KL_LB3 "223"
+// piece Q of operand O into the stage at PD bytes: M0 = the wave's LDS destination, source =
+// base SG + this lane's offset
+#define KL_PIECE(O, Q, V, PD, SG)                                          \
+  "s_add_u32 m0, %[lds], " PD "+" #O "*16384+" #Q "*1024\n\ts_nop 0\n\t" \
+  "global_load_lds_dwordx4 v" V ", " SG "\n\t"
+#define KL_PIECES_A(PD, GA)                                    \
+  KL_PIECE(0, 0, "208", PD, GA) KL_PIECE(0, 1, "209", PD, GA) \
+  KL_PIECE(0, 2, "210", PD, GA) KL_PIECE(0, 3, "211", PD, GA)
+#define KL_PIECES_B(PD, GB)                                    \
+  KL_PIECE(1, 0, "212", PD, GB) KL_PIECE(1, 1, "213", PD, GB) \
+  KL_PIECE(1, 2, "214", PD, GB) KL_PIECE(1, 3, "215", PD, GB)
+#if VGPOSP_KLOOP_PIECES == 1
+#define KL_P_S0(PD, GA, GB) KL_PIECES_A(PD, GA)
+#define KL_P_S1(PD, GA, GB) KL_PIECES_B(PD, GB)
+#define KL_P_BAR(PD, GA, GB) ""
+#define KL_P_RD(PD, GA, GB) ""
+#elif VGPOSP_KLOOP_PIECES == 0
+#define KL_P_S0(PD, GA, GB) ""
+#define KL_P_S1(PD, GA, GB) ""
+#define KL_P_BAR(PD, GA, GB) KL_PIECES_A(PD, GA) KL_PIECES_B(PD, GB)
+#define KL_P_RD(PD, GA, GB) ""
+#else
+#define KL_P_S0(PD, GA, GB) ""
+#define KL_P_S1(PD, GA, GB) ""
+#define KL_P_BAR(PD, GA, GB) ""
+#define KL_P_RD(PD, GA, GB) KL_PIECES_A(PD, GA) KL_PIECES_B(PD, GB)
+#endif
+// L = NT | NN, NRD = fragment-read instructions per slice (a wait for slice s leaves slice s + 1's
+// NRD reads in flight), P_* = the pieces at each of the four places ("" = none there), SR / SB =
+// the tile's stage in 512-byte units / bytes, NR / NB = the next tile's, PD = the pieces'
+#define KL_TILE(L, NRD, P_S0, P_S1, P_BAR, P_RD, SR, SB, NR, NB)          \
+  KL_RD1_##L(1, SR, SB) "s_waitcnt lgkmcnt(" #NRD ")\n\t" KL_MFMA_F0 P_S0 \
+  KL_RD0_##L(2, SR, SB) "s_waitcnt lgkmcnt(" #NRD ")\n\t" KL_MFMA_F1 P_S1 \
+  KL_RD1_##L(3, SR, SB) "s_waitcnt lgkmcnt(" #NRD ")\n\t" KL_MFMA_F0      \
+  "s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier\n\t"                      \
+  P_BAR KL_RD0_##L(0, NR, NB) P_RD KL_MFMA_F1
+#define KL_T0(L, NRD, PD)                                                              \
+  KL_TILE(L, NRD, KL_P_S0(PD, "%[ga0]", "%[gb0]"), KL_P_S1(PD, "%[ga0]", "%[gb0]"),       \
+          KL_P_BAR(PD, "%[ga0]", "%[gb0]"), KL_P_RD(PD, "%[ga0]", "%[gb0]"), "0", "0", "64", \
+          "32768")
+#define KL_T1(L, NRD, PD)                                                              \
+  KL_TILE(L, NRD, KL_P_S0(PD, "%[ga1]", "%[gb1]"), KL_P_S1(PD, "%[ga1]", "%[gb1]"),       \
+          KL_P_BAR(PD, "%[ga1]", "%[gb1]"), KL_P_RD(PD, "%[ga1]", "%[gb1]"), "64", "32768", \
+          "0", "0")
+#define KL_T1_NOISSUE(L, NRD) KL_TILE(L, NRD, "", "", "", "", "64", "32768", "0", "0")
+#if VGPOSP_KLOOP_PIECES == 1  // tile t's pieces go to the other stage, tile t + 2's to its own
+#define KL_PD0 "32768"
+#define KL_PD1 "0"
+#else
+#define KL_PD0 "0"
+#define KL_PD1 "32768"
+#endif
+
+// K-tiles t (even: ring stage 0) and t + 1 (stage 1) in one statement, so that both stages are
+// immediates.  LAST = true: the second tile issues no pieces (the end of a run under placements
+// 0 and 2: its successor's successor is loaded by the C++ loop).  ga0 / gb0 and ga1 / gb1 are
+// the source bases of the tiles that the first and the second tile load.
+template <bool TB, bool LAST>
+__device__ __forceinline__ void kloop_pair(dbl4 (&acc)[4][4], u32x8& vo, u32x8& lb, dbl8& f0,
+                                           uint64_t ga0, uint64_t gb0, uint64_t ga1, uint64_t gb1,
+                                           unsigned lds) {
+  unsigned keep;
+#define KL_OPERANDS                                                                              \
+  : [c00] "+v"(acc[0][0]), [c01] "+v"(acc[0][1]), [c02] "+v"(acc[0][2]), [c03] "+v"(acc[0][3]),  \
+    [c10] "+v"(acc[1][0]), [c11] "+v"(acc[1][1]), [c12] "+v"(acc[1][2]), [c13] "+v"(acc[1][3]),  \
+    [c20] "+v"(acc[2][0]), [c21] "+v"(acc[2][1]), [c22] "+v"(acc[2][2]), [c23] "+v"(acc[2][3]),  \
+    [c30] "+v"(acc[3][0]), [c31] "+v"(acc[3][1]), [c32] "+v"(acc[3][2]), [c33] "+v"(acc[3][3]),  \
+    "+{v[208:215]}"(vo), "+{v[216:223]}"(lb), "+{v[224:239]}"(f0), [keep] "=&s"(keep)            \
+  : [ga0] "s"(ga0), [gb0] "s"(gb0), [ga1] "s"(ga1), [gb1] "s"(gb1), [lds] "s"(lds)               \
+  : "memory", "v240", "v241", "v242", "v243", "v244", "v245", "v246", "v247", "v248",            \
+    "v249", "v250", "v251", "v252", "v253", "v254", "v255"
+#define KL_SAVE "s_mov_b32 %[keep], m0\n\t"
+#define KL_RESTORE "s_mov_b32 m0, %[keep]\n\t"
+#define KL_PAIR(L, NRD, T1) asm volatile(KL_SAVE KL_T0(L, NRD, KL_PD0) T1 KL_RESTORE KL_OPERANDS)
+  if constexpr (TB) {
+    if constexpr (LAST) KL_PAIR(NT, 4, KL_T1_NOISSUE(NT, 4));
+    else KL_PAIR(NT, 4, KL_T1(NT, 4, KL_PD1));
+  } else {
+    if constexpr (LAST) KL_PAIR(NN, 6, KL_T1_NOISSUE(NN, 6));
+    else KL_PAIR(NN, 6, KL_T1(NN, 6, KL_PD1));
+  }
+#undef KL_PAIR
+#undef KL_OPERANDS
+}
+
 // One workgroup of the fast kernel: workgroup `bid` of the launch's `nwg` for this problem, batch
 // element bz, LDS ring at smem (the kernel's own __shared__ array).
 // MULTI: the epilogue also writes the extra destinations *x (plain products only: no triangular
 // operand, full C, no split-K); the K loop is the same code.
-template <bool TA, bool TB, bool TRIA, bool TRIB, int CFG, bool MULTI = false>
+// KL: the first run of K-tiles that need no mask and have a successor goes through kloop_pair;
+// every other K-tile, the prologue and the epilogue are the C++ below.
+template <bool TA, bool TB, bool TRIA, bool TRIB, int CFG, bool MULTI = false, bool KL = false>
 __device__ __forceinline__ void gemm_glds_body(const GemmParams& p, int tiles_m, int tiles_n,
                                                const int bid, const int nwg, const int64_t bz,
                                                double* smem, const GemmExtra* xd = nullptr) {
   static_assert(!MULTI || (!TRIA && !TRIB), "extra destinations: plain products only");
+  static_assert(!KL || (!TA && CFG == 1 && STAGES == 2), "hand-scheduled K loop: TA = false");
   if (p.abort != nullptr && *p.abort != 0) return;
   constexpr bool A_KC = !TA;
   constexpr bool B_KC = TB;
@@ -410,14 +583,15 @@ __device__ __forceinline__ void gemm_glds_body(const GemmParams& p, int tiles_m,
   // stage layout: [A sub-tile 0 | ... | A sub-tile NSUB-1 | B].  Every wave issues PO pieces of
   // each operand, with no branches (measured: splitting the waves into A-loaders and B-loaders
   // cost 10% on 8192^3).  Piece q (0 .. PPW-1) of this wave for K-tile t: q / PO = operand.
+  int ln = lane;  // the lane as the K loop sees it
   auto issue_piece = [&](int t, int q) {
     double* st = smem + (t % NST) * SE;
     const int64_t k0 = kbeg + (int64_t)t * GBK;
     const int op = q / PO, j = wave * PO + q % PO;
     if (op < NSUB)
-      glds_piece<A_KC>(gA, p.lda, m0 + GBM * op, k0, p.m, p.k, st + op * OPND_ELEMS, j, lane);
+      glds_piece<A_KC>(gA, p.lda, m0 + GBM * op, k0, p.m, p.k, st + op * OPND_ELEMS, j, KL ? ln : lane);
     else
-      glds_piece<B_KC>(gB, p.ldb, n0, k0, p.n, p.k, st + NSUB * OPND_ELEMS, j, lane);
+      glds_piece<B_KC>(gB, p.ldb, n0, k0, p.n, p.k, st + NSUB * OPND_ELEMS, j, KL ? ln : lane);
   };
   auto issue = [&](int t) {
 #pragma unroll
@@ -428,7 +602,79 @@ __device__ __forceinline__ void gemm_glds_body(const GemmParams& p, int tiles_m,
   for (int s = 0; s < NST - 1; ++s)
     if (s < T) issue(s);
 
+  // [f0, f1): the first run of unmasked K-tiles, each with a successor (KL)
+  int f0 = 0, f1 = 0;
+  if constexpr (KL) {
+    auto masked = [&](int t) {
+      const int64_t k0 = kbeg + (int64_t)t * GBK;
+      return (partial_last && t == T - 1) || (TRIA && k0 < m0 + TBM && k0 + GBK > m0) ||
+             (TRIB && k0 < n0 + GBN && k0 + GBK > n0);
+    };
+    // 32-bit per-lane source offsets: 128 rows of a leading dimension below 2^21
+    if (p.lda < (1 << 21) && p.ldb < (1 << 21)) {
+      while (f0 < T - 1 && masked(f0)) ++f0;
+      f0 += f0 & 1;  // pairs of K-tiles: the run starts at ring stage 0 and has an even length
+      f1 = f0;
+      while (f1 + 2 <= T - 1 && !masked(f1) && !masked(f1 + 1)) f1 += 2;
+      // the run loads tile f1 without a k clamp: not the partial last tile
+      if (partial_last && f1 == T - 1 && f1 > f0) f1 -= 2;
+    }
+  }
+
   for (int t = 0; t < T; ++t) {
+    if constexpr (KL) {
+      if (t == f0 && f0 < f1) {
+        // tile t has landed and every wave is done with the other stage
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        // the run's first tile loads tile t + AHEAD
+        constexpr int AHEAD = KLOOP_PIECES == 1 ? 1 : 2;
+        if (AHEAD == 2) issue(t + 1);
+        const unsigned lds0 = (unsigned)(uintptr_t)(lds_ptr_t)smem;
+        const unsigned ldsw = __builtin_amdgcn_readfirstlane(lds0 + wave * (PO * 1024));
+        u32x8 vo, lb;
+        dbl8 fr0;
+        const double* As = smem + (t % NST) * SE;
+        const double* Bs = As + OPND_ELEMS;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int j = wave * PO + q;  // piece of the operand tile: glds_piece's addresses
+          const int row = 8 * j + (lane >> 3);
+          const int kp = (lane & 7) ^ ((row & 15) >> 1);
+          vo[q] = (unsigned)((min(m0 + row, p.m - 1) - m0) * p.lda * 8 + kp * 16);
+          if (TB) {
+            vo[4 + q] = (unsigned)((min(n0 + row, p.n - 1) - n0) * p.ldb * 8 + kp * 16);
+          } else {
+            const int pp = lane ^ ((j & 1) << 3);
+            vo[4 + q] = (unsigned)(j * p.ldb * 8 + (min(n0 + 2 * pp, p.n - 2) - n0) * 8);
+          }
+          lb[q] = lds0 + 8 * frag_off<true>(wm * 64 + fr, q * 4 + fk);
+          if (TB) lb[4 + q] = lds0 + 8 * frag_off<true>(wn * 64 + fr, q * 4 + fk);
+          else lb[4 + q] = q < 2 ? lds0 + 8 * frag_off<false>(wn * 64 + q * 16 + fr, fk) : 0u;
+          fr0[q] = As[frag_off<true>(wm * 64 + q * 16 + fr, fk)];
+          fr0[4 + q] = Bs[frag_off<B_KC>(wn * 64 + q * 16 + fr, fk)];
+        }
+        const int64_t kn = kbeg + (int64_t)(t + AHEAD) * GBK;
+        uint64_t ga = (uint64_t)(uintptr_t)(gA + m0 * p.lda + kn);
+        uint64_t gb = (uint64_t)(uintptr_t)(TB ? gB + n0 * p.ldb + kn : gB + kn * p.ldb + n0);
+        const uint64_t stride_b = TB ? GBK * 8u : (uint64_t)(GBK * 8 * p.ldb);
+        int u = t;
+        for (; u + 2 < f1; u += 2) {
+          kloop_pair<TB, false>(acc, vo, lb, fr0, ga, gb, ga + GBK * 8, gb + stride_b, ldsw);
+          ga += 2 * GBK * 8;
+          gb += 2 * stride_b;
+        }
+        kloop_pair<TB, AHEAD == 2>(acc, vo, lb, fr0, ga, gb, ga + GBK * 8, gb + stride_b, ldsw);
+        // the last MFMAs' results, before anything but an accumulating MFMA touches them
+        asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");
+        t = f1;  // < T: the C++ tile below redoes tile f1's wait and barrier, which is harmless
+      }
+    }
+    // KL: the lane is opaque per C++ tile, so that what the tile derives from it (fragment
+    // offsets, piece addresses) is recomputed here and not kept in registers across kloop_pair
+    if constexpr (KL) asm volatile("" : "+v"(ln));
+    const int tfr = KL ? ln & 15 : fr, tfk = KL ? ln >> 4 : fk;
     const int after = min(T - 1 - t, NST - 2);  // tiles that may stay in flight
     static_assert(PPW == 8 || PPW == 12 || PPW == 6, "counted waits: 6, 8 or 12 pieces");
     if (after == 0) {
@@ -462,28 +708,28 @@ __device__ __forceinline__ void gemm_glds_body(const GemmParams& p, int tiles_m,
                       (TRIB && k0 < n0 + GBN && k0 + GBK > n0);
 #pragma unroll
     for (int ks = 0; ks < GBK / 4; ++ks) {
-      const int k = ks * 4 + fk;
+      const int k = ks * 4 + tfk;
       double a[FI], b[4];
 #pragma unroll
       for (int i = 0; i < FI; ++i) {
-        const int r = (wm * WROWS) % GBM + i * 16 + fr;  // row within the sub-tile
+        const int r = (wm * WROWS) % GBM + i * 16 + tfr;  // row within the sub-tile
         a[i] = As[frag_off<A_KC>(r, k)];
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const int c = wn * 64 + j * 16 + fr;
+        const int c = wn * 64 + j * 16 + tfr;
         b[j] = Bs[frag_off<B_KC>(c, k)];
       }
       if (mask) {
         const int64_t gk = k0 + k;
 #pragma unroll
         for (int i = 0; i < FI; ++i) {
-          const int64_t gm = m0 + wm * WROWS + i * 16 + fr;
+          const int64_t gm = m0 + wm * WROWS + i * 16 + tfr;
           if (gk >= kend || (TRIA && (TA ? gm > gk : gk > gm))) a[i] = 0.0;
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const int64_t gn = n0 + wn * 64 + j * 16 + fr;
+          const int64_t gn = n0 + wn * 64 + j * 16 + tfr;
           if (gk >= kend || (TRIB && (TB ? gk > gn : gn > gk))) b[j] = 0.0;
         }
       }
@@ -502,16 +748,22 @@ __device__ __forceinline__ void gemm_glds_body(const GemmParams& p, int tiles_m,
     }
   }
 
+  // KL: the epilogue derives its lane and wave indices afresh, so that they do not occupy
+  // registers across kloop_pair
+  int et = threadIdx.x;
+  if constexpr (KL) asm volatile("" : "+v"(et));
+  const int efr = KL ? et & 15 : fr, efk = KL ? (et & 63) >> 4 : fk;
+  const int ewm = KL ? et >> 7 : wm, ewn = KL ? (et >> 6) & 1 : wn;
   const bool lower = p.uplo_c == VGPOSP_LOWER;
 #pragma unroll
   for (int i = 0; i < FI; ++i) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int64_t col = n0 + wn * 64 + (B_IL ? 32 * (j >> 1) + 2 * fr + (j & 1) : j * 16 + fr);
+      const int64_t col = n0 + ewn * 64 + (B_IL ? 32 * (j >> 1) + 2 * efr + (j & 1) : j * 16 + efr);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int x = fk + 4 * r;
-        const int64_t row = m0 + wm * WROWS + (A_IL ? 32 * (i >> 1) + 2 * x + (i & 1) : i * 16 + x);
+        const int x = efk + 4 * r;
+        const int64_t row = m0 + ewm * WROWS + (A_IL ? 32 * (i >> 1) + 2 * x + (i & 1) : i * 16 + x);
         if (row < p.m && col < p.n && (!lower || col <= row)) {
           if (p.nsplit > 1) {
             p.part[bz * p.sP + (int64_t)zsplit * p.m * p.n + row * p.n + col] = p.alpha * acc[i][j][r];
@@ -538,21 +790,21 @@ __device__ __forceinline__ void gemm_glds_body(const GemmParams& p, int tiles_m,
   }
 }
 
-template <bool TA, bool TB, bool TRIA, bool TRIB, int CFG>
+template <bool TA, bool TB, bool TRIA, bool TRIB, int CFG, bool KL = false>
 __global__ __launch_bounds__(64 * GemmCfg<CFG>::NW, GemmCfg<CFG>::OCC) void gemm_glds_kernel(
     GemmParams p, int tiles_m, int tiles_n) {
   __shared__ __attribute__((aligned(16))) double smem[glds_smem_elems<CFG>()];
-  gemm_glds_body<TA, TB, TRIA, TRIB, CFG>(p, tiles_m, tiles_n, blockIdx.x, gridDim.x, blockIdx.y,
-                                          smem);
+  gemm_glds_body<TA, TB, TRIA, TRIB, CFG, false, KL>(p, tiles_m, tiles_n, blockIdx.x, gridDim.x,
+                                                     blockIdx.y, smem);
 }
 
 // The plain product with extra destinations (gemm_strassen): same tiles, ring and K loop.
-template <bool TA, bool TB>
+template <bool TA, bool TB, bool KL = false>
 __global__ __launch_bounds__(64 * GemmCfg<1>::NW, GemmCfg<1>::OCC) void gemm_glds_multi_kernel(
     GemmParams p, GemmExtra x, int tiles_m, int tiles_n) {
   __shared__ __attribute__((aligned(16))) double smem[glds_smem_elems<1>()];
-  gemm_glds_body<TA, TB, false, false, 1, true>(p, tiles_m, tiles_n, blockIdx.x, gridDim.x, 0,
-                                                smem, &x);
+  gemm_glds_body<TA, TB, false, false, 1, true, KL>(p, tiles_m, tiles_n, blockIdx.x, gridDim.x, 0,
+                                                    smem, &x);
 }
 
 // Grouped launch: up to GROUP_MAX independent problems (each its own shape, operands, flags and
@@ -586,8 +838,20 @@ __global__ __launch_bounds__(256, 2) void gemm_group_kernel(GemmGroup gg) {
 #undef VG_GROUP_CASE
 }
 
+// K loop of the TA = false fast kernels (vgposp_gemm_set_kloop): 0 = the C++ loop, 1 = the
+// hand-scheduled interior K-tiles (kloop_pair).  Process-wide, read at launch.  Bit-identical
+// results either way.  Default from the 65k step's A/B (DESIGN.md §4 "Hand-scheduled K loop").
+static std::atomic<int> g_kloop{VGPOSP_KLOOP_DEFAULT};
+
 template <int CFG, bool TA, bool TB, bool TRIA, bool TRIB>
 static void launch_one(dim3 g1, hipStream_t stream, const GemmParams& p, int tm, int tn) {
+  if constexpr (!TA && CFG == 1) {
+    if (g_kloop.load(std::memory_order_relaxed) != 0) {
+      hipLaunchKernelGGL((gemm_glds_kernel<TA, TB, TRIA, TRIB, CFG, true>), g1,
+                         dim3(64 * GemmCfg<CFG>::NW), 0, stream, p, tm, tn);
+      return;
+    }
+  }
   hipLaunchKernelGGL((gemm_glds_kernel<TA, TB, TRIA, TRIB, CFG>), g1, dim3(64 * GemmCfg<CFG>::NW),
                      0, stream, p, tm, tn);
 }
@@ -1087,7 +1351,10 @@ static int gemm_launch_multi(int transa, int transb, int64_t m, int64_t n, int64
                2.0 * (double)m * (double)n * (double)k,
                8.0 * ((double)m * k + (double)k * n + outs * (double)m * n));
   const dim3 g1((unsigned)nblk), b1(64 * GemmCfg<1>::NW);
-  if (!transa && !transb) hipLaunchKernelGGL((gemm_glds_multi_kernel<false, false>), g1, b1, 0, stream, p, x, tm, tn);
+  const bool kl = g_kloop.load(std::memory_order_relaxed) != 0;
+  if (!transa && !transb && kl) hipLaunchKernelGGL((gemm_glds_multi_kernel<false, false, true>), g1, b1, 0, stream, p, x, tm, tn);
+  else if (!transa && kl) hipLaunchKernelGGL((gemm_glds_multi_kernel<false, true, true>), g1, b1, 0, stream, p, x, tm, tn);
+  else if (!transa && !transb) hipLaunchKernelGGL((gemm_glds_multi_kernel<false, false>), g1, b1, 0, stream, p, x, tm, tn);
   else if (!transa) hipLaunchKernelGGL((gemm_glds_multi_kernel<false, true>), g1, b1, 0, stream, p, x, tm, tn);
   else if (!transb) hipLaunchKernelGGL((gemm_glds_multi_kernel<true, false>), g1, b1, 0, stream, p, x, tm, tn);
   else hipLaunchKernelGGL((gemm_glds_multi_kernel<true, true>), g1, b1, 0, stream, p, x, tm, tn);
@@ -1209,6 +1476,16 @@ extern "C" int vgposp_gemm_set_split_depth(int min_k) {
 }
 
 extern "C" int vgposp_gemm_split_depth(void) { return vgposp::g_split_min_k.load(); }
+
+extern "C" int vgposp_gemm_set_kloop(int kloop) {
+  using namespace vgposp;
+  clear_error();
+  VG_CHECK_ARG(kloop == 0 || kloop == 1, 1);
+  g_kloop.store(kloop, std::memory_order_relaxed);
+  return 0;
+}
+
+extern "C" int vgposp_gemm_kloop(void) { return vgposp::g_kloop.load(); }
 
 extern "C" size_t vgposp_gemm_splitk_workspace_bytes(int64_t m, int64_t n, int64_t k, int uplo_c,
                                                      int splits) {
