@@ -61,8 +61,8 @@ def test_gemm(L, ta, tb, m, n, k):
                                                (1, 1, 0, 0), (0, 0, 1, 0), (0, 0, 0, 1),
                                                (0, 1, 0, 1), (1, 0, 1, 1)])
 def test_gemm_many_tiles(L, ta, tb, tri_a, tri_b):
-    """Enough output tiles (>= 512 of 256x128) for the wide-tile kernel when it is enabled
-    (VGPOSP_GEMM_BMW=2); ragged m / n / k exercise the clamped loads and masks."""
+    """Many output tiles (34 x 33 of 128x128: more than two per CU, several per XCD range); ragged
+    m / n / k exercise the clamped loads and masks."""
     m, n, k = 4352, 4224, 200
     if tri_a or tri_b:
         k = m if tri_a else n
@@ -337,11 +337,14 @@ GROUP_CASES = [(0, 0, 0, 0, 0, 512, 512, 512), (1, 0, 0, 0, 0, 512, 512, 512),
                (1, 1, 0, 0, 0, 64, 96, 2048), (0, 0, 0, 0, 0, 129, 1, 77)]
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("order", [0, 1])
-def test_gemm_group_matches_numpy(L, order):
-    cases = GROUP_CASES if order == 0 else GROUP_CASES[::-1]
-    rng = np.random.default_rng(11 + order)
+# every (transa, transb, tri_a, tri_b) combination the grouped kernel dispatches on, at the smallest
+# shape with several K-tiles (13), a partial last K-tile (200 = 12 * 16 + 8) and, for a triangular
+# operand, K-tiles that straddle the diagonal of a 128-wide tile
+GROUP_FLAG_CASES = [(f & 1, (f >> 1) & 1, (f >> 2) & 1, (f >> 3) & 1, 0, 256, 256, 200)
+                    for f in range(16)]
+
+
+def _check_group(L, cases, rng):
     specs, refs, C0s = [], [], []
     for ta, tb, tri_a, tri_b, lower, m, n, k in cases:
         A = rng.standard_normal((k, m) if ta else (m, k))
@@ -363,3 +366,23 @@ def test_gemm_group_matches_numpy(L, order):
             np.testing.assert_array_equal(Ch[np.triu_indices(m, 1)], C0[np.triu_indices(m, 1)])
         else:
             np.testing.assert_allclose(Ch, ref, rtol=1e-11, atol=1e-10)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("order", [0, 1])
+def test_gemm_group_matches_numpy(L, order):
+    from vgposp_amd import _lib
+    cases = GROUP_CASES if order == 0 else GROUP_CASES[::-1]
+    rng = np.random.default_rng(11 + order)
+    _check_group(L, cases, rng)
+    # all 16 flag combinations, eight problems (one grouped launch's worth) at a time: split over
+    # K (the default: two K-tiles per workgroup) and unsplit (all 13 K-tiles in one workgroup)
+    flag_cases = GROUP_FLAG_CASES if order == 0 else GROUP_FLAG_CASES[::-1]
+    depth = _lib.load().vgposp_gemm_split_depth()
+    try:
+        for d in (depth, 256):
+            _lib.call("vgposp_gemm_set_split_depth", d)
+            _check_group(L, flag_cases[:8], rng)
+            _check_group(L, flag_cases[8:], rng)
+    finally:
+        _lib.call("vgposp_gemm_set_split_depth", depth)

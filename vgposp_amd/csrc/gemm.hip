@@ -3,11 +3,10 @@
 //
 //   C = alpha * op(A) * op(B) + beta * C        (row-major, fp64)
 //
-// Three kernels share the 128x128x16 tile geometry (4 waves in a 2x2 grid, 64x64 = 4x4 MFMA
+// Two kernels share the 128x128x16 tile geometry (4 waves in a 2x2 grid, 64x64 = 4x4 MFMA
 // fragments per wave):
 //   gemm_glds_kernel (default)  LDS-DMA staging (global_load_lds), 2-stage ring, 2 WG per CU,
 //                               XOR-swizzled lane-linear LDS images; described above the kernel.
-//   gemm_rs_kernel (opt-in)     one wave per SIMD, register-staged, 256 AGPR accumulators.
 //   gemm_ref_kernel (fallback)  odd sizes / unaligned operands: register staging into padded
 //                               images, bank-conflict-free for the fragment reads (lane l reads
 //                               row l&15, k = l>>4):
@@ -247,8 +246,8 @@ __global__ __launch_bounds__(256) void gemm_ref_kernel(GemmParams p, int vec_a, 
 
 // ---------------------------------------------------------------------------------------------
 // Fast path: operands streamed HBM -> LDS with global_load_lds_dwordx4 (no VGPR staging) through
-// a STAGES-deep ring, counted vmcnt waits and raw barriers, so STAGES-1 K-tiles are in flight
-// while one is multiplied.  Two stages (64 KiB of LDS) let two workgroups share a CU, i.e. two
+// a two-stage ring, vmcnt waits and raw barriers, so the next K-tile is in flight while one is
+// multiplied.  Two stages (64 KiB of LDS) let two workgroups share a CU, i.e. two
 // waves per SIMD: one wave's barrier / LDS-latency bubbles are filled by the other's MFMAs.
 // Measured on 8192^3 NT: 4 stages x 1 WG/CU 57 TF/s, 3 x 1 61, 2 x 1 62, 2 x 2 69 TF/s.  The LDS images are lane-linear (as glds requires) and the XOR swizzle
 // is applied on the per-lane SOURCE address and on the fragment read (conflict-free reads):
@@ -262,10 +261,20 @@ __global__ __launch_bounds__(256) void gemm_ref_kernel(GemmParams p, int vec_a, 
 constexpr int STAGES = 2;      // LDS ring depth (3 and 4 stages at one workgroup per CU: slower)
 constexpr int GEMM_GROUP = 4;  // row tiles per XCD band (1, 2, 8, 16 measured: DESIGN.md §4)
 constexpr int GEMM_OCC = 2;    // workgroups per CU (the launch bound)
-// 2-stage ring: the next K-tile's pieces spread over the first SPREAD2 k-slices, after each
-// slice's fragment reads (0 = all issued right after the barrier)
-constexpr int SPREAD2 = 2;
+constexpr int GEMM_WAVES = 4;  // 2 x 2 waves of 64 x 64 (4 x 4 MFMA fragments each)
+// LDS-DMA pieces per wave per stage: 4 of A, then 4 of B.  Every wave issues its share of both
+// operands, with no branches (measured: splitting the waves into A-loaders and B-loaders cost
+// 10% on 8192^3).
+constexpr int WAVE_PIECES = 8;
+// The next K-tile's pieces are spread over the first two k-slices, each slice's share after its
+// fragment reads: the reads do not wait behind the piece issue after the barrier (measured
+// against all eight issued right after the barrier: 65k step 16.10 -> 16.23 placements/s over
+// three interleaved repeats).
+constexpr int SPREAD_SLICES = 2;
 constexpr int OPND_ELEMS = GBM * GBK;        // 2048 doubles = 16 KiB per operand per stage
+// LDS of one workgroup (doubles): the ring of stages, each [A tile | B tile]
+constexpr int GLDS_SMEM_ELEMS = STAGES * 2 * OPND_ELEMS;
+static_assert(STAGES == 2, "the K loop loads one tile ahead and waits for all of it: 2-stage ring");
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
@@ -304,30 +313,15 @@ __device__ __forceinline__ int tri_root(int64_t id) {
   return (int)t;
 }
 
-// Tile configuration: 128x128 tiles, 4 waves of 64x64 (4x4 fragments), a STAGES-deep ring, 2
-// workgroups per CU.  (The 256x128 configurations measured against it live in
-// tools/variants/gemm_experiments.hip.)
-template <int CFG> struct GemmCfg {
-  static_assert(CFG == 1, "only the 128x128 configuration is built into the library");
-  static constexpr int NSUB = 1;              // 128-row A sub-tiles
-  static constexpr int NW = 4;                // waves
-  static constexpr int FI = 4;                // 16-row fragments per wave
-  static constexpr int NST = STAGES;          // ring depth
-  static constexpr int OCC = GEMM_OCC;  // workgroups per CU (launch bound)
-};
-
-// LDS of one workgroup of the fast kernel (doubles): the STAGES-deep ring of A sub-tiles | B.
-template <int CFG>
-constexpr int glds_smem_elems() {
-  return GemmCfg<CFG>::NST * (GemmCfg<CFG>::NSUB + 1) * OPND_ELEMS;
-}
+// (The 256x128 tile configurations and the register-staged kernel measured against this one
+// live in tools/variants.)
 
 // ---------------------------------------------------------------------------------------------
 // Hand-scheduled interior K-tiles (vgposp_gemm_set_kloop(1); TA = false, 2-stage ring).  One asm
 // statement (kloop_pair) takes two K-tiles, the first in ring stage 0 and the second in stage 1,
 // so that both stages are immediates.  Each K-tile t, out of stage S, leaves tile t + 1 ready:
-//   reads(1) wait MFMA(0) [P1: A pieces] reads(2) wait MFMA(1) [P1: B pieces] reads(3) wait MFMA(2)
-//   vmcnt(0) lgkmcnt(0) s_barrier [P0: pieces] reads(0 of t + 1) [P2: pieces] MFMA(3)
+//   reads(1) wait MFMA(0) [A pieces] reads(2) wait MFMA(1) [B pieces] reads(3) wait MFMA(2)
+//   vmcnt(0) lgkmcnt(0) s_barrier reads(0 of t + 1) MFMA(3)
 // reads(s) = the slice's fragment reads, issued one slice ahead into the other of two fragment
 // buffers and retired by counted lgkmcnt waits; MFMA(s) = the 16 MFMAs of slice s, in the C++
 // loop's (i, j) order, so every accumulator sees the same products in the same k order and the
@@ -344,21 +338,15 @@ constexpr int glds_smem_elems() {
 // per K-tile in the C++ around the statement (scalar adds); the pieces need no clamp selects
 // (interior tiles have no k clamp, the row clamp is folded into the constant offsets).
 // Stage, fragment and row group are immediate offset fields; M0 is saved and restored.
-// VGPOSP_KLOOP_PIECES places the next LDS-DMA pieces (measured: DESIGN.md §4 "Hand-scheduled K
-// loop"; 1 is the fastest on every layout):
-//   0  all eight directly behind the barrier, for tile t + 2 (one tile further ahead)
-//   1  four behind slice 0's MFMAs and four behind slice 1's, for tile t + 1
-//   2  all eight behind the barrier and tile t + 1's slice-0 reads, for tile t + 2
+// The next LDS-DMA pieces, for tile t + 1, go four behind slice 0's MFMAs and four behind slice
+// 1's.  Two other placements, all eight for tile t + 2 directly behind the barrier or behind
+// tile t + 1's slice-0 reads, were slower on every layout (DESIGN.md §4 "Hand-scheduled K loop";
+// they were build switches of commit cb6bc49, which git history keeps).
 // VGPOSP_KLOOP_DEFAULT is the setting a process starts with.
 // ---------------------------------------------------------------------------------------------
-#ifndef VGPOSP_KLOOP_PIECES
-#define VGPOSP_KLOOP_PIECES 1
-#endif
-constexpr int KLOOP_PIECES = VGPOSP_KLOOP_PIECES;
 #ifndef VGPOSP_KLOOP_DEFAULT
 #define VGPOSP_KLOOP_DEFAULT 1
 #endif
-static_assert(KLOOP_PIECES >= 0 && KLOOP_PIECES <= 2, "piece placement 0, 1 or 2");
 
 typedef double dbl8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x8 __attribute__((ext_vector_type(8)));
@@ -418,53 +406,24 @@ typedef unsigned int u32x8 __attribute__((ext_vector_type(8)));
 #define KL_PIECES_B(PD, GB)                                    \
   KL_PIECE(1, 0, "212", PD, GB) KL_PIECE(1, 1, "213", PD, GB) \
   KL_PIECE(1, 2, "214", PD, GB) KL_PIECE(1, 3, "215", PD, GB)
-#if VGPOSP_KLOOP_PIECES == 1
-#define KL_P_S0(PD, GA, GB) KL_PIECES_A(PD, GA)
-#define KL_P_S1(PD, GA, GB) KL_PIECES_B(PD, GB)
-#define KL_P_BAR(PD, GA, GB) ""
-#define KL_P_RD(PD, GA, GB) ""
-#elif VGPOSP_KLOOP_PIECES == 0
-#define KL_P_S0(PD, GA, GB) ""
-#define KL_P_S1(PD, GA, GB) ""
-#define KL_P_BAR(PD, GA, GB) KL_PIECES_A(PD, GA) KL_PIECES_B(PD, GB)
-#define KL_P_RD(PD, GA, GB) ""
-#else
-#define KL_P_S0(PD, GA, GB) ""
-#define KL_P_S1(PD, GA, GB) ""
-#define KL_P_BAR(PD, GA, GB) ""
-#define KL_P_RD(PD, GA, GB) KL_PIECES_A(PD, GA) KL_PIECES_B(PD, GB)
-#endif
 // L = NT | NN, NRD = fragment-read instructions per slice (a wait for slice s leaves slice s + 1's
-// NRD reads in flight), P_* = the pieces at each of the four places ("" = none there), SR / SB =
-// the tile's stage in 512-byte units / bytes, NR / NB = the next tile's, PD = the pieces'
-#define KL_TILE(L, NRD, P_S0, P_S1, P_BAR, P_RD, SR, SB, NR, NB)          \
-  KL_RD1_##L(1, SR, SB) "s_waitcnt lgkmcnt(" #NRD ")\n\t" KL_MFMA_F0 P_S0 \
-  KL_RD0_##L(2, SR, SB) "s_waitcnt lgkmcnt(" #NRD ")\n\t" KL_MFMA_F1 P_S1 \
-  KL_RD1_##L(3, SR, SB) "s_waitcnt lgkmcnt(" #NRD ")\n\t" KL_MFMA_F0      \
-  "s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier\n\t"                      \
-  P_BAR KL_RD0_##L(0, NR, NB) P_RD KL_MFMA_F1
-#define KL_T0(L, NRD, PD)                                                              \
-  KL_TILE(L, NRD, KL_P_S0(PD, "%[ga0]", "%[gb0]"), KL_P_S1(PD, "%[ga0]", "%[gb0]"),       \
-          KL_P_BAR(PD, "%[ga0]", "%[gb0]"), KL_P_RD(PD, "%[ga0]", "%[gb0]"), "0", "0", "64", \
-          "32768")
-#define KL_T1(L, NRD, PD)                                                              \
-  KL_TILE(L, NRD, KL_P_S0(PD, "%[ga1]", "%[gb1]"), KL_P_S1(PD, "%[ga1]", "%[gb1]"),       \
-          KL_P_BAR(PD, "%[ga1]", "%[gb1]"), KL_P_RD(PD, "%[ga1]", "%[gb1]"), "64", "32768", \
-          "0", "0")
-#define KL_T1_NOISSUE(L, NRD) KL_TILE(L, NRD, "", "", "", "", "64", "32768", "0", "0")
-#if VGPOSP_KLOOP_PIECES == 1  // tile t's pieces go to the other stage, tile t + 2's to its own
-#define KL_PD0 "32768"
-#define KL_PD1 "0"
-#else
-#define KL_PD0 "0"
-#define KL_PD1 "32768"
-#endif
+// NRD reads in flight), GA / GB = the source bases of the next tile's pieces, PD = the bytes of
+// the stage they go to, SR / SB = the tile's stage in 512-byte units / bytes, NR / NB = the next
+// tile's
+#define KL_TILE(L, NRD, PD, GA, GB, SR, SB, NR, NB)                                        \
+  KL_RD1_##L(1, SR, SB) "s_waitcnt lgkmcnt(" #NRD ")\n\t" KL_MFMA_F0 KL_PIECES_A(PD, GA) \
+  KL_RD0_##L(2, SR, SB) "s_waitcnt lgkmcnt(" #NRD ")\n\t" KL_MFMA_F1 KL_PIECES_B(PD, GB) \
+  KL_RD1_##L(3, SR, SB) "s_waitcnt lgkmcnt(" #NRD ")\n\t" KL_MFMA_F0                     \
+  "s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier\n\t"                                     \
+  KL_RD0_##L(0, NR, NB) KL_MFMA_F1
+// a tile's pieces go to the other stage
+#define KL_T0(L, NRD) KL_TILE(L, NRD, "32768", "%[ga0]", "%[gb0]", "0", "0", "64", "32768")
+#define KL_T1(L, NRD) KL_TILE(L, NRD, "0", "%[ga1]", "%[gb1]", "64", "32768", "0", "0")
 
 // K-tiles t (even: ring stage 0) and t + 1 (stage 1) in one statement, so that both stages are
-// immediates.  LAST = true: the second tile issues no pieces (the end of a run under placements
-// 0 and 2: its successor's successor is loaded by the C++ loop).  ga0 / gb0 and ga1 / gb1 are
-// the source bases of the tiles that the first and the second tile load.
-template <bool TB, bool LAST>
+// immediates.  ga0 / gb0 and ga1 / gb1 are the source bases of the tiles that the first and the
+// second tile load.
+template <bool TB>
 __device__ __forceinline__ void kloop_pair(dbl4 (&acc)[4][4], u32x8& vo, u32x8& lb, dbl8& f0,
                                            uint64_t ga0, uint64_t gb0, uint64_t ga1, uint64_t gb1,
                                            unsigned lds) {
@@ -480,14 +439,9 @@ __device__ __forceinline__ void kloop_pair(dbl4 (&acc)[4][4], u32x8& vo, u32x8& 
     "v249", "v250", "v251", "v252", "v253", "v254", "v255"
 #define KL_SAVE "s_mov_b32 %[keep], m0\n\t"
 #define KL_RESTORE "s_mov_b32 m0, %[keep]\n\t"
-#define KL_PAIR(L, NRD, T1) asm volatile(KL_SAVE KL_T0(L, NRD, KL_PD0) T1 KL_RESTORE KL_OPERANDS)
-  if constexpr (TB) {
-    if constexpr (LAST) KL_PAIR(NT, 4, KL_T1_NOISSUE(NT, 4));
-    else KL_PAIR(NT, 4, KL_T1(NT, 4, KL_PD1));
-  } else {
-    if constexpr (LAST) KL_PAIR(NN, 6, KL_T1_NOISSUE(NN, 6));
-    else KL_PAIR(NN, 6, KL_T1(NN, 6, KL_PD1));
-  }
+#define KL_PAIR(L, NRD) asm volatile(KL_SAVE KL_T0(L, NRD) KL_T1(L, NRD) KL_RESTORE KL_OPERANDS)
+  if constexpr (TB) KL_PAIR(NT, 4);
+  else KL_PAIR(NN, 6);
 #undef KL_PAIR
 #undef KL_OPERANDS
 }
@@ -498,25 +452,15 @@ __device__ __forceinline__ void kloop_pair(dbl4 (&acc)[4][4], u32x8& vo, u32x8& 
 // operand, full C, no split-K); the K loop is the same code.
 // KL: the first run of K-tiles that need no mask and have a successor goes through kloop_pair;
 // every other K-tile, the prologue and the epilogue are the C++ below.
-template <bool TA, bool TB, bool TRIA, bool TRIB, int CFG, bool MULTI = false, bool KL = false>
+template <bool TA, bool TB, bool TRIA, bool TRIB, bool MULTI = false, bool KL = false>
 __device__ __forceinline__ void gemm_glds_body(const GemmParams& p, int tiles_m, int tiles_n,
                                                const int bid, const int nwg, const int64_t bz,
                                                double* smem, const GemmExtra* xd = nullptr) {
   static_assert(!MULTI || (!TRIA && !TRIB), "extra destinations: plain products only");
-  static_assert(!KL || (!TA && CFG == 1 && STAGES == 2), "hand-scheduled K loop: TA = false");
+  static_assert(!KL || !TA, "hand-scheduled K loop: TA = false");
   if (p.abort != nullptr && *p.abort != 0) return;
   constexpr bool A_KC = !TA;
   constexpr bool B_KC = TB;
-  constexpr int NSUB = GemmCfg<CFG>::NSUB, NW = GemmCfg<CFG>::NW, FI = GemmCfg<CFG>::FI;
-  constexpr int NST = GemmCfg<CFG>::NST;
-  constexpr int TBM = GBM * NSUB;                      // rows per tile
-  constexpr int WROWS = 16 * FI;                       // rows per wave
-  constexpr int SE = (NSUB + 1) * OPND_ELEMS;          // doubles per stage: A subs | B
-  constexpr int PO = 16 / NW;                          // pieces per operand per wave
-  constexpr int PPW = PO * (NSUB + 1);                 // pieces per wave per stage (8, 12 or 6)
-  constexpr bool SPREAD = NST >= 3 || SPREAD2 > 0;     // next-tile loads between the MFMAs
-  constexpr bool A_IL = false, B_IL = false;  // plain fragment order
-  static_assert(NST * SE == glds_smem_elems<CFG>(), "LDS ring size");
 
   // Tile order.  Uniform-K launches: XCD-aware bijective remap (each XCD walks a contiguous range
   // of tiles, so neighbours share A rows / B columns in its L2).  A lower-triangular A (K range
@@ -546,7 +490,7 @@ __device__ __forceinline__ void gemm_glds_body(const GemmParams& p, int tiles_m,
     tj = local / gsize;
     if (TRIA && !TA) ti = tiles_m - 1 - ti;  // longest K ranges first
   }
-  const int64_t m0 = (int64_t)ti * TBM, n0 = (int64_t)tj * GBN;
+  const int64_t m0 = (int64_t)ti * GBM, n0 = (int64_t)tj * GBN;
   const double* const gA = p.A + bz * p.sA;
   const double* const gB = p.B + bz * p.sB;
 
@@ -559,7 +503,7 @@ __device__ __forceinline__ void gemm_glds_body(const GemmParams& p, int tiles_m,
   int64_t kbeg = 0, kend = p.k;
   if (TRIA) {
     if (TA) kbeg = max(kbeg, m0);        // stored A[k][i], zero for i > k
-    else kend = min(kend, m0 + TBM);     // stored A[i][k], zero for k > i
+    else kend = min(kend, m0 + GBM);     // stored A[i][k], zero for k > i
   }
   if (TRIB) {
     if (TB) kend = min(kend, n0 + GBN);  // stored B[j][k], zero for k > j
@@ -574,40 +518,37 @@ __device__ __forceinline__ void gemm_glds_body(const GemmParams& p, int tiles_m,
   const int T = (int)((kend - kbeg + GBK - 1) / GBK);
   const bool partial_last = ((kend - kbeg) % GBK) != 0;
 
-  dbl4 acc[FI][4];
+  dbl4 acc[4][4];
 #pragma unroll
-  for (int i = 0; i < FI; ++i)
+  for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = dbl4{0.0, 0.0, 0.0, 0.0};
 
-  // stage layout: [A sub-tile 0 | ... | A sub-tile NSUB-1 | B].  Every wave issues PO pieces of
-  // each operand, with no branches (measured: splitting the waves into A-loaders and B-loaders
-  // cost 10% on 8192^3).  Piece q (0 .. PPW-1) of this wave for K-tile t: q / PO = operand.
+  // stage layout: [A tile | B tile].  Piece q (0 .. WAVE_PIECES - 1) of this wave for K-tile t:
+  // the first half are pieces of A, the second half of B.
   int ln = lane;  // the lane as the K loop sees it
   auto issue_piece = [&](int t, int q) {
-    double* st = smem + (t % NST) * SE;
+    double* st = smem + (t % STAGES) * 2 * OPND_ELEMS;
     const int64_t k0 = kbeg + (int64_t)t * GBK;
-    const int op = q / PO, j = wave * PO + q % PO;
-    if (op < NSUB)
-      glds_piece<A_KC>(gA, p.lda, m0 + GBM * op, k0, p.m, p.k, st + op * OPND_ELEMS, j, KL ? ln : lane);
+    const int j = wave * (WAVE_PIECES / 2) + q % (WAVE_PIECES / 2);  // piece of the operand tile
+    if (q < WAVE_PIECES / 2)
+      glds_piece<A_KC>(gA, p.lda, m0, k0, p.m, p.k, st, j, KL ? ln : lane);
     else
-      glds_piece<B_KC>(gB, p.ldb, n0, k0, p.n, p.k, st + NSUB * OPND_ELEMS, j, KL ? ln : lane);
-  };
-  auto issue = [&](int t) {
-#pragma unroll
-    for (int q = 0; q < PPW; ++q) issue_piece(t, q);
+      glds_piece<B_KC>(gB, p.ldb, n0, k0, p.n, p.k, st + OPND_ELEMS, j, KL ? ln : lane);
   };
 
+  if (T > 0) {
 #pragma unroll
-  for (int s = 0; s < NST - 1; ++s)
-    if (s < T) issue(s);
+    for (int q = 0; q < WAVE_PIECES; ++q) issue_piece(0, q);
+  }
 
   // [f0, f1): the first run of unmasked K-tiles, each with a successor (KL)
   int f0 = 0, f1 = 0;
   if constexpr (KL) {
+    // the C++ tile's `mask` below, which it must agree with (see there why it is written twice)
     auto masked = [&](int t) {
       const int64_t k0 = kbeg + (int64_t)t * GBK;
-      return (partial_last && t == T - 1) || (TRIA && k0 < m0 + TBM && k0 + GBK > m0) ||
+      return (partial_last && t == T - 1) || (TRIA && k0 < m0 + GBM && k0 + GBK > m0) ||
              (TRIB && k0 < n0 + GBN && k0 + GBK > n0);
     };
     // 32-bit per-lane source offsets: 128 rows of a leading dimension below 2^21
@@ -628,18 +569,15 @@ __device__ __forceinline__ void gemm_glds_body(const GemmParams& p, int tiles_m,
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        // the run's first tile loads tile t + AHEAD
-        constexpr int AHEAD = KLOOP_PIECES == 1 ? 1 : 2;
-        if (AHEAD == 2) issue(t + 1);
         const unsigned lds0 = (unsigned)(uintptr_t)(lds_ptr_t)smem;
-        const unsigned ldsw = __builtin_amdgcn_readfirstlane(lds0 + wave * (PO * 1024));
+        const unsigned ldsw = __builtin_amdgcn_readfirstlane(lds0 + wave * (WAVE_PIECES / 2 * 1024));
         u32x8 vo, lb;
         dbl8 fr0;
-        const double* As = smem + (t % NST) * SE;
+        const double* As = smem + (t % STAGES) * 2 * OPND_ELEMS;
         const double* Bs = As + OPND_ELEMS;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          const int j = wave * PO + q;  // piece of the operand tile: glds_piece's addresses
+          const int j = wave * (WAVE_PIECES / 2) + q;  // piece of the operand tile: glds_piece's addresses
           const int row = 8 * j + (lane >> 3);
           const int kp = (lane & 7) ^ ((row & 15) >> 1);
           vo[q] = (unsigned)((min(m0 + row, p.m - 1) - m0) * p.lda * 8 + kp * 16);
@@ -655,17 +593,17 @@ __device__ __forceinline__ void gemm_glds_body(const GemmParams& p, int tiles_m,
           fr0[q] = As[frag_off<true>(wm * 64 + q * 16 + fr, fk)];
           fr0[4 + q] = Bs[frag_off<B_KC>(wn * 64 + q * 16 + fr, fk)];
         }
-        const int64_t kn = kbeg + (int64_t)(t + AHEAD) * GBK;
+        const int64_t kn = kbeg + (int64_t)(t + 1) * GBK;  // the run's first tile loads tile t + 1
         uint64_t ga = (uint64_t)(uintptr_t)(gA + m0 * p.lda + kn);
         uint64_t gb = (uint64_t)(uintptr_t)(TB ? gB + n0 * p.ldb + kn : gB + kn * p.ldb + n0);
         const uint64_t stride_b = TB ? GBK * 8u : (uint64_t)(GBK * 8 * p.ldb);
         int u = t;
         for (; u + 2 < f1; u += 2) {
-          kloop_pair<TB, false>(acc, vo, lb, fr0, ga, gb, ga + GBK * 8, gb + stride_b, ldsw);
+          kloop_pair<TB>(acc, vo, lb, fr0, ga, gb, ga + GBK * 8, gb + stride_b, ldsw);
           ga += 2 * GBK * 8;
           gb += 2 * stride_b;
         }
-        kloop_pair<TB, AHEAD == 2>(acc, vo, lb, fr0, ga, gb, ga + GBK * 8, gb + stride_b, ldsw);
+        kloop_pair<TB>(acc, vo, lb, fr0, ga, gb, ga + GBK * 8, gb + stride_b, ldsw);
         // the last MFMAs' results, before anything but an accumulating MFMA touches them
         asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");
         t = f1;  // < T: the C++ tile below redoes tile f1's wait and barrier, which is harmless
@@ -675,44 +613,32 @@ __device__ __forceinline__ void gemm_glds_body(const GemmParams& p, int tiles_m,
     // offsets, piece addresses) is recomputed here and not kept in registers across kloop_pair
     if constexpr (KL) asm volatile("" : "+v"(ln));
     const int tfr = KL ? ln & 15 : fr, tfk = KL ? ln >> 4 : fk;
-    const int after = min(T - 1 - t, NST - 2);  // tiles that may stay in flight
-    static_assert(PPW == 8 || PPW == 12 || PPW == 6, "counted waits: 6, 8 or 12 pieces");
-    if (after == 0) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else if (PPW == 8) {
-      if (after >= 2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    } else if (PPW == 12) {
-      if (after >= 2) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    } else {
-      if (after >= 2) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    }
+    // Tile t has landed: it is the only one in flight, so the wait is always vmcnt(0) and the
+    // other branch is never taken.  The test stays, and `mask` below stays written out instead of
+    // sharing the run finder's lambda, because only with both does the compiler peel the last
+    // K-tile off this loop, which leaves the loop proper without the `more` and partial-tile
+    // branches.  With either one simplified it keeps a single copy of the body and the kernels
+    // that run this loop end to end lose 2% (16384^3 TN 66.5 -> 65.2, TT 67.4 -> 66.3 TF/s).
+    if (min(T - 1 - t, STAGES - 2) == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    // 3-stage ring: the next K-tile's pieces are spread over the k-slices below, between MFMAs
-    // (issued back to back they park the wave for their issue cost; 8192^3 NT 63.3 -> 65.7 TF/s).
-    // 2-stage ring: spread over the first SPREAD2 k-slices, each after that slice's fragment reads
-    // (the reads no longer wait behind the piece issue after the barrier; 65k step 16.10 ->
-    // 16.23 placements/s over three interleaved repeats); SPREAD2 = 0 issues them all here.
-    const bool more = t + NST - 1 < T;
-    if (!SPREAD && more) issue(t + NST - 1);
+    const bool more = t + 1 < T;  // its pieces go between the MFMAs below (SPREAD_SLICES)
 
-    const double* As = smem + (t % NST) * SE + ((wm * WROWS) / GBM) * OPND_ELEMS;
-    const double* Bs = smem + (t % NST) * SE + NSUB * OPND_ELEMS;
+    const double* As = smem + (t % STAGES) * 2 * OPND_ELEMS;
+    const double* Bs = As + OPND_ELEMS;
     const int64_t k0 = kbeg + (int64_t)t * GBK;
     // masks only where needed: the last partial K-tile, and K-tiles that straddle the diagonal
     // of a triangular operand (k0 within 128 of the tile's first row / column)
-    const bool mask = (partial_last && t == T - 1) || (TRIA && k0 < m0 + TBM && k0 + GBK > m0) ||
+    const bool mask = (partial_last && t == T - 1) || (TRIA && k0 < m0 + GBM && k0 + GBK > m0) ||
                       (TRIB && k0 < n0 + GBN && k0 + GBK > n0);
 #pragma unroll
     for (int ks = 0; ks < GBK / 4; ++ks) {
       const int k = ks * 4 + tfk;
-      double a[FI], b[4];
+      double a[4], b[4];
 #pragma unroll
-      for (int i = 0; i < FI; ++i) {
-        const int r = (wm * WROWS) % GBM + i * 16 + tfr;  // row within the sub-tile
+      for (int i = 0; i < 4; ++i) {
+        const int r = wm * 64 + i * 16 + tfr;
         a[i] = As[frag_off<A_KC>(r, k)];
       }
 #pragma unroll
@@ -723,8 +649,8 @@ __device__ __forceinline__ void gemm_glds_body(const GemmParams& p, int tiles_m,
       if (mask) {
         const int64_t gk = k0 + k;
 #pragma unroll
-        for (int i = 0; i < FI; ++i) {
-          const int64_t gm = m0 + wm * WROWS + i * 16 + tfr;
+        for (int i = 0; i < 4; ++i) {
+          const int64_t gm = m0 + wm * 64 + i * 16 + tfr;
           if (gk >= kend || (TRIA && (TA ? gm > gk : gk > gm))) a[i] = 0.0;
         }
 #pragma unroll
@@ -733,15 +659,13 @@ __device__ __forceinline__ void gemm_glds_body(const GemmParams& p, int tiles_m,
           if (gk >= kend || (TRIB && (TB ? gk > gn : gn > gk))) b[j] = 0.0;
         }
       }
-      if (SPREAD && more) {
-        constexpr int NS = NST >= 3 ? 4 : (SPREAD2 > 0 ? SPREAD2 : 4);
-        if (ks < NS) {
+      if (more && ks < SPREAD_SLICES) {
 #pragma unroll
-          for (int q = (ks * PPW) / NS; q < ((ks + 1) * PPW) / NS; ++q) issue_piece(t + NST - 1, q);
-        }
+        for (int q = 0; q < WAVE_PIECES / SPREAD_SLICES; ++q)
+          issue_piece(t + 1, ks * (WAVE_PIECES / SPREAD_SLICES) + q);
       }
 #pragma unroll
-      for (int i = 0; i < FI; ++i)
+      for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
@@ -756,14 +680,13 @@ __device__ __forceinline__ void gemm_glds_body(const GemmParams& p, int tiles_m,
   const int ewm = KL ? et >> 7 : wm, ewn = KL ? (et >> 6) & 1 : wn;
   const bool lower = p.uplo_c == VGPOSP_LOWER;
 #pragma unroll
-  for (int i = 0; i < FI; ++i) {
+  for (int i = 0; i < 4; ++i) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int64_t col = n0 + ewn * 64 + (B_IL ? 32 * (j >> 1) + 2 * efr + (j & 1) : j * 16 + efr);
+      const int64_t col = n0 + ewn * 64 + j * 16 + efr;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int x = efk + 4 * r;
-        const int64_t row = m0 + ewm * WROWS + (A_IL ? 32 * (i >> 1) + 2 * x + (i & 1) : i * 16 + x);
+        const int64_t row = m0 + ewm * 64 + i * 16 + efk + 4 * r;
         if (row < p.m && col < p.n && (!lower || col <= row)) {
           if (p.nsplit > 1) {
             p.part[bz * p.sP + (int64_t)zsplit * p.m * p.n + row * p.n + col] = p.alpha * acc[i][j][r];
@@ -790,21 +713,21 @@ __device__ __forceinline__ void gemm_glds_body(const GemmParams& p, int tiles_m,
   }
 }
 
-template <bool TA, bool TB, bool TRIA, bool TRIB, int CFG, bool KL = false>
-__global__ __launch_bounds__(64 * GemmCfg<CFG>::NW, GemmCfg<CFG>::OCC) void gemm_glds_kernel(
+template <bool TA, bool TB, bool TRIA, bool TRIB, bool KL = false>
+__global__ __launch_bounds__(64 * GEMM_WAVES, GEMM_OCC) void gemm_glds_kernel(
     GemmParams p, int tiles_m, int tiles_n) {
-  __shared__ __attribute__((aligned(16))) double smem[glds_smem_elems<CFG>()];
-  gemm_glds_body<TA, TB, TRIA, TRIB, CFG, false, KL>(p, tiles_m, tiles_n, blockIdx.x, gridDim.x,
-                                                     blockIdx.y, smem);
+  __shared__ __attribute__((aligned(16))) double smem[GLDS_SMEM_ELEMS];
+  gemm_glds_body<TA, TB, TRIA, TRIB, false, KL>(p, tiles_m, tiles_n, blockIdx.x, gridDim.x,
+                                                blockIdx.y, smem);
 }
 
 // The plain product with extra destinations (gemm_strassen): same tiles, ring and K loop.
 template <bool TA, bool TB, bool KL = false>
-__global__ __launch_bounds__(64 * GemmCfg<1>::NW, GemmCfg<1>::OCC) void gemm_glds_multi_kernel(
+__global__ __launch_bounds__(64 * GEMM_WAVES, GEMM_OCC) void gemm_glds_multi_kernel(
     GemmParams p, GemmExtra x, int tiles_m, int tiles_n) {
-  __shared__ __attribute__((aligned(16))) double smem[glds_smem_elems<1>()];
-  gemm_glds_body<TA, TB, false, false, 1, true, KL>(p, tiles_m, tiles_n, blockIdx.x, gridDim.x, 0,
-                                                    smem, &x);
+  __shared__ __attribute__((aligned(16))) double smem[GLDS_SMEM_ELEMS];
+  gemm_glds_body<TA, TB, false, false, true, KL>(p, tiles_m, tiles_n, blockIdx.x, gridDim.x, 0,
+                                                 smem, &x);
 }
 
 // Grouped launch: up to GROUP_MAX independent problems (each its own shape, operands, flags and
@@ -817,17 +740,17 @@ struct GemmGroup {
   int flags[GROUP_MAX];  // bit 0 transa, 1 transb, 2 tri_a, 3 tri_b
 };
 
-__global__ __launch_bounds__(256, 2) void gemm_group_kernel(GemmGroup gg) {
-  __shared__ __attribute__((aligned(16))) double smem[glds_smem_elems<1>()];
+__global__ __launch_bounds__(64 * GEMM_WAVES, GEMM_OCC) void gemm_group_kernel(GemmGroup gg) {
+  __shared__ __attribute__((aligned(16))) double smem[GLDS_SMEM_ELEMS];
   const int g = blockIdx.y;
   const int bid = blockIdx.x, nwg = gg.nwg[g];
   if (bid >= nwg) return;
   const GemmParams& p = gg.p[g];
   const int tm = gg.tiles_m[g], tn = gg.tiles_n[g];
-#define VG_GROUP_CASE(F)                                                                         \
-  case F:                                                                                      \
-    gemm_glds_body<(F & 1) != 0, (F & 2) != 0, (F & 4) != 0, (F & 8) != 0, 1>(p, tm, tn, bid,   \
-                                                                             nwg, 0, smem);    \
+#define VG_GROUP_CASE(F)                                                                      \
+  case F:                                                                                   \
+    gemm_glds_body<(F & 1) != 0, (F & 2) != 0, (F & 4) != 0, (F & 8) != 0>(p, tm, tn, bid,   \
+                                                                          nwg, 0, smem);    \
     break;
   switch (gg.flags[g]) {
     VG_GROUP_CASE(0) VG_GROUP_CASE(1) VG_GROUP_CASE(2) VG_GROUP_CASE(3)
@@ -843,37 +766,22 @@ __global__ __launch_bounds__(256, 2) void gemm_group_kernel(GemmGroup gg) {
 // results either way.  Default from the 65k step's A/B (DESIGN.md §4 "Hand-scheduled K loop").
 static std::atomic<int> g_kloop{VGPOSP_KLOOP_DEFAULT};
 
-template <int CFG, bool TA, bool TB, bool TRIA, bool TRIB>
-static void launch_one(dim3 g1, hipStream_t stream, const GemmParams& p, int tm, int tn) {
-  if constexpr (!TA && CFG == 1) {
-    if (g_kloop.load(std::memory_order_relaxed) != 0) {
-      hipLaunchKernelGGL((gemm_glds_kernel<TA, TB, TRIA, TRIB, CFG, true>), g1,
-                         dim3(64 * GemmCfg<CFG>::NW), 0, stream, p, tm, tn);
-      return;
-    }
-  }
-  hipLaunchKernelGGL((gemm_glds_kernel<TA, TB, TRIA, TRIB, CFG>), g1, dim3(64 * GemmCfg<CFG>::NW),
-                     0, stream, p, tm, tn);
-}
-
-// every (transa, transb, tri_a, tri_b) combination: the kernel's K-range and mask logic is
-// generic in the four flags.
-template <int CFG, bool TA, bool TB>
-static void launch_tri(dim3 g1, hipStream_t stream, const GemmParams& p, int tm, int tn, int tri_a,
-                       int tri_b) {
-  if (CFG != 1 || (!tri_a && !tri_b)) return launch_one<CFG, TA, TB, false, false>(g1, stream, p, tm, tn);
-  if (tri_a && tri_b) return launch_one<1, TA, TB, true, true>(g1, stream, p, tm, tn);
-  if (tri_a) return launch_one<1, TA, TB, true, false>(g1, stream, p, tm, tn);
-  launch_one<1, TA, TB, false, true>(g1, stream, p, tm, tn);
-}
-
-template <int CFG>
+// The kernel of a launch: every (transa, transb, tri_a, tri_b) combination has its C++-loop
+// kernel (the K-range and mask logic is generic in the four flags); the TA = false ones also
+// have a hand-scheduled one, taken when g_kloop is set.
 static void launch_glds(dim3 g1, hipStream_t stream, const GemmParams& p, int tm, int tn,
                         int transa, int transb, int tri_a, int tri_b) {
-  if (!transa && !transb) launch_tri<CFG, false, false>(g1, stream, p, tm, tn, tri_a, tri_b);
-  else if (!transa) launch_tri<CFG, false, true>(g1, stream, p, tm, tn, tri_a, tri_b);
-  else if (!transb) launch_tri<CFG, true, false>(g1, stream, p, tm, tn, tri_a, tri_b);
-  else launch_tri<CFG, true, true>(g1, stream, p, tm, tn, tri_a, tri_b);
+  using Kernel = void (*)(GemmParams, int, int);
+#define VG_TRI(TA, TB, KL)                                                                \
+  gemm_glds_kernel<TA, TB, false, false, KL>, gemm_glds_kernel<TA, TB, true, false, KL>, \
+      gemm_glds_kernel<TA, TB, false, true, KL>, gemm_glds_kernel<TA, TB, true, true, KL>
+  static const Kernel cxx[16] = {VG_TRI(false, false, false), VG_TRI(false, true, false),
+                                 VG_TRI(true, false, false), VG_TRI(true, true, false)};
+  static const Kernel kl[8] = {VG_TRI(false, false, true), VG_TRI(false, true, true)};
+#undef VG_TRI
+  const int f = (transa ? 8 : 0) + (transb ? 4 : 0) + (tri_b ? 2 : 0) + (tri_a ? 1 : 0);
+  const bool hand = !transa && g_kloop.load(std::memory_order_relaxed) != 0;
+  hipLaunchKernelGGL(hand ? kl[f] : cxx[f], g1, dim3(64 * GEMM_WAVES), 0, stream, p, tm, tn);
 }
 
 // C = sum_z part[z] + beta * C over the (lower) output, fixed summation order.
@@ -1101,7 +1009,7 @@ int gemm_launch_batched(int transa, int transb, int64_t m, int64_t n, int64_t k,
     ProfScope ps(gemm_class_name(transa, transb, tri_a, tri_b, nblk * p.nsplit * batch >= 512),
                  stream, fl, by);
     dim3 g1((unsigned)(nblk * p.nsplit), (unsigned)batch);
-    launch_glds<1>(g1, stream, p, tm, tn, transa, transb, tri_a, tri_b);
+    launch_glds(g1, stream, p, tm, tn, transa, transb, tri_a, tri_b);
     VG_LAUNCH_CHECK();
     if (p.nsplit > 1) {
       hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3((unsigned)ceil_div(m * n, 256), (unsigned)batch),
@@ -1350,14 +1258,15 @@ static int gemm_launch_multi(int transa, int transb, int64_t m, int64_t n, int64
   ProfScope ps(gemm_class_name(transa, transb, 0, 0, nblk >= 512), stream,
                2.0 * (double)m * (double)n * (double)k,
                8.0 * ((double)m * k + (double)k * n + outs * (double)m * n));
-  const dim3 g1((unsigned)nblk), b1(64 * GemmCfg<1>::NW);
-  const bool kl = g_kloop.load(std::memory_order_relaxed) != 0;
-  if (!transa && !transb && kl) hipLaunchKernelGGL((gemm_glds_multi_kernel<false, false, true>), g1, b1, 0, stream, p, x, tm, tn);
-  else if (!transa && kl) hipLaunchKernelGGL((gemm_glds_multi_kernel<false, true, true>), g1, b1, 0, stream, p, x, tm, tn);
-  else if (!transa && !transb) hipLaunchKernelGGL((gemm_glds_multi_kernel<false, false>), g1, b1, 0, stream, p, x, tm, tn);
-  else if (!transa) hipLaunchKernelGGL((gemm_glds_multi_kernel<false, true>), g1, b1, 0, stream, p, x, tm, tn);
-  else if (!transb) hipLaunchKernelGGL((gemm_glds_multi_kernel<true, false>), g1, b1, 0, stream, p, x, tm, tn);
-  else hipLaunchKernelGGL((gemm_glds_multi_kernel<true, true>), g1, b1, 0, stream, p, x, tm, tn);
+  using Kernel = void (*)(GemmParams, GemmExtra, int, int);
+  static const Kernel cxx[4] = {gemm_glds_multi_kernel<false, false>, gemm_glds_multi_kernel<false, true>,
+                                gemm_glds_multi_kernel<true, false>, gemm_glds_multi_kernel<true, true>};
+  static const Kernel kl[2] = {gemm_glds_multi_kernel<false, false, true>,
+                               gemm_glds_multi_kernel<false, true, true>};
+  const int f = (transa ? 2 : 0) + (transb ? 1 : 0);
+  const bool hand = !transa && g_kloop.load(std::memory_order_relaxed) != 0;
+  hipLaunchKernelGGL(hand ? kl[f] : cxx[f], dim3((unsigned)nblk), dim3(64 * GEMM_WAVES), 0, stream,
+                     p, x, tm, tn);
   VG_LAUNCH_CHECK();
   return 0;
 }
