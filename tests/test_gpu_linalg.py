@@ -275,6 +275,29 @@ def test_cholesky_batched_one_recursion(L, n, invert):
         np.testing.assert_allclose(ld[b].cpu().numpy(), np.diag(Lref), rtol=1e-12)
 
 
+@pytest.mark.parametrize("n", [5, 128])
+@pytest.mark.parametrize("invert", [False, True])
+def test_cholesky_batched_leaf(L, n, invert):
+    """B > 1 matrices of n <= 128 are one launch, one workgroup per matrix: each good member's
+    factor / inverse and diagonal land in its own slot, and a member that is not positive
+    definite sets only its own status."""
+    rng = np.random.default_rng(7 * n + invert)
+    S = np.stack([_spd(n, rng) * (1.0 + 0.5 * b) for b in range(3)])
+    S[1, n // 2, n // 2] = -1.0
+    A = L.as_device(S.copy())
+    A, ld, info = L.cholesky_(A, invert=invert, check=False)
+    info = info.cpu().numpy()
+    assert info[0] == 0 and info[2] == 0 and info[1] == n // 2 + 1
+    il = np.tril_indices(n)
+    for b in (0, 2):
+        Lref = np.linalg.cholesky(S[b])
+        ref = np.linalg.inv(Lref) if invert else Lref
+        np.testing.assert_allclose(A[b].cpu().numpy()[il], ref[il], rtol=1e-9,
+                                   atol=1e-10 * np.abs(ref).max())
+        np.testing.assert_array_equal(np.triu(A[b].cpu().numpy(), 1), np.triu(S[b], 1))
+        np.testing.assert_allclose(ld[b].cpu().numpy(), np.diag(Lref), rtol=1e-12)
+
+
 @pytest.mark.parametrize("ta,tb,tri_a,tri_b,lower", [(0, 0, 0, 0, 0), (1, 0, 1, 1, 0),
                                                      (0, 1, 0, 0, 1), (0, 0, 1, 0, 0),
                                                      (1, 1, 0, 0, 0)])

@@ -24,6 +24,15 @@ void clear_error();
     }                                                                                 \
   } while (0)
 
+#define VG_CHECK_WS(have, need)                                                       \
+  do {                                                                                \
+    const size_t _need = (need);                                                      \
+    if ((have) < _need) {                                                             \
+      ::vgposp::set_error("%s: workspace %zu < %zu bytes", __func__, (size_t)(have), _need); \
+      return VGPOSP_E_WS;                                                             \
+    }                                                                                 \
+  } while (0)
+
 #define VG_HIP(expr)                                                                  \
   do {                                                                                \
     hipError_t _e = (expr);                                                           \

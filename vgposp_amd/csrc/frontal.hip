@@ -21,19 +21,10 @@
 //   front_diag:       diag(Q_PP) scattered to the pivots' grid indices
 #include <cmath>
 
-#include "common.h"
+#include "dense.h"
 #include "psd.h"
 
 namespace vgposp {
-
-int gemm_launch_batched(int transa, int transb, int64_t m, int64_t n, int64_t k, double alpha,
-                        const double* A, int64_t lda, int64_t sA, const double* B, int64_t ldb,
-                        int64_t sB, double beta, double* C, int64_t ldc, int64_t sC, int uplo_c,
-                        int tri_a, int tri_b, int nsplit, double* part, int64_t sP, int batch,
-                        hipStream_t stream);
-int potrf_batched(double* A, int64_t n, int64_t lda, int64_t sA, int batch, int invert,
-                  double* diag_out, int* info, void* ws, hipStream_t stream, bool use_part);
-size_t potrf_ws_bytes_opt(int64_t n, bool use_part);
 
 struct TaperArgs {
   const double* X;
@@ -236,10 +227,7 @@ extern "C" int vgposp_front_factor(double* PP, double* UP, double* UU, int64_t p
   VG_CHECK_ARG(nf >= 1 && nf <= 65535, 6);
   VG_CHECK_ARG(info != nullptr, 7);
   VG_CHECK_ARG(ws != nullptr, 8);
-  if (ws_bytes < front_factor_ws(p, u, nf)) {
-    set_error("vgposp_front_factor: workspace %zu < %zu bytes", ws_bytes, front_factor_ws(p, u, nf));
-    return VGPOSP_E_WS;
-  }
+  VG_CHECK_WS(ws_bytes, front_factor_ws(p, u, nf));
   hipStream_t s = as_stream(stream);
   VG_HIP(vg_memset(info, 0, sizeof(int) * nf, s));
   const bool part = front_use_part(nf);

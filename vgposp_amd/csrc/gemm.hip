@@ -17,7 +17,7 @@
 #include <atomic>
 #include <type_traits>
 
-#include "common.h"
+#include "dense.h"
 
 namespace vgposp {
 
@@ -945,6 +945,41 @@ static const char* gemm_class_name(int ta, int tb, int tra, int trb, bool wide) 
   return names[(lay * 4 + tri) * 2 + (wide ? 0 : 1)];
 }
 
+// The launch plan of one problem (a batch of `batch` at p's strides): which kernel takes it, the
+// fast kernel's tile grid, and the algorithmic flops / bytes recorded for it.
+struct GemmPlan {
+  int va, vb;           // A / B readable with 16-byte loads (aligned, even ld and batch stride)
+  bool fast;            // the fast kernel takes it: both of those, and m, n, k even with k > 0
+  int tm, tn;           // output tiles per column / row
+  int64_t nblk;         // output tiles in all (lower: of the triangle)
+  double outs;          // output elements per matrix
+  double flops, bytes;  // a triangular operand halves the useful products
+};
+
+// Also fills p's split-K fields when the fast kernel takes p split (nsplit > 1, partials at part).
+static GemmPlan gemm_plan(GemmParams& p, int batch, int nsplit, double* part) {
+  GemmPlan pl{};
+  pl.va = aligned16(p.A, p.lda) && (batch == 1 || p.sA % 2 == 0);
+  pl.vb = aligned16(p.B, p.ldb) && (batch == 1 || p.sB % 2 == 0);
+  pl.fast = pl.va && pl.vb && (p.m % 2 == 0) && (p.n % 2 == 0) && (p.k % 2 == 0) && p.k > 0;
+  const bool lower = p.uplo_c == VGPOSP_LOWER;
+  const double m = (double)p.m, n = (double)p.n, k = (double)p.k;
+  pl.tm = (int)ceil_div(p.m, GBM);
+  pl.tn = (int)ceil_div(p.n, GBN);
+  pl.nblk = lower ? (int64_t)pl.tm * (pl.tm + 1) / 2 : (int64_t)pl.tm * pl.tn;
+  pl.outs = lower ? 0.5 * m * (double)(p.m + 1) : m * n;
+  pl.flops = 2.0 * batch * k * pl.outs *
+             ((p.tri_a && p.tri_b) ? (1.0 / 3.0) : (p.tri_a || p.tri_b) ? 0.5 : 1.0);
+  pl.bytes = 8.0 * batch * (m * k + k * n + (p.beta != 0.0 ? 2.0 : 1.0) * pl.outs);
+  if (pl.fast && nsplit > 1 && part != nullptr) {
+    p.nblk = (int)pl.nblk;
+    p.kchunk = ceil_div(ceil_div(p.k, nsplit), GBK) * GBK;
+    p.nsplit = (int)ceil_div(p.k, p.kchunk);
+    p.part = part;
+  }
+  return pl;
+}
+
 int gemm_launch_batched(int transa, int transb, int64_t m, int64_t n, int64_t k, double alpha,
                         const double* A, int64_t lda, int64_t sA, const double* B, int64_t ldb,
                         int64_t sB, double beta, double* C, int64_t ldc, int64_t sC, int uplo_c,
@@ -988,28 +1023,13 @@ int gemm_launch_batched(int transa, int transb, int64_t m, int64_t n, int64_t k,
   }
   GemmParams p{m, n, k, alpha, beta, A, lda, B, ldb, C, ldc, uplo_c, tri_a, tri_b, 1, 0, 0, nullptr,
                sA, sB, sC, sP, tl_gemm_abort};
-  const int va = aligned16(A, lda) && (batch == 1 || sA % 2 == 0);
-  const int vb = aligned16(B, ldb) && (batch == 1 || sB % 2 == 0);
-  const bool even = (m % 2 == 0) && (n % 2 == 0) && (k % 2 == 0) && k > 0;
-  if (va && vb && even) {
-    const int tm = (int)ceil_div(m, GBM), tn = (int)ceil_div(n, GBN);
-    const int64_t nblk = (uplo_c == VGPOSP_LOWER) ? (int64_t)tm * (tm + 1) / 2 : (int64_t)tm * tn;
-    const double outs = (uplo_c == VGPOSP_LOWER) ? 0.5 * (double)m * (double)(m + 1) : (double)m * n;
-    // algorithmic flops: a triangular operand halves the useful products
-    const double fl = 2.0 * batch * (double)k * outs * ((tri_a && tri_b) ? (1.0 / 3.0) : (tri_a || tri_b) ? 0.5 : 1.0);
-    if (nsplit > 1 && part != nullptr) {
-      p.nblk = (int)nblk;
-      p.kchunk = ceil_div(ceil_div(k, nsplit), GBK) * GBK;
-      p.nsplit = (int)ceil_div(k, p.kchunk);
-      p.part = part;
-    }
-    const double by =
-        8.0 * batch * ((double)m * k + (double)k * n + (beta != 0.0 ? 2.0 : 1.0) * outs);
+  const GemmPlan pl = gemm_plan(p, batch, nsplit, part);
+  if (pl.fast) {
     // recorded under its layout class; vgposp_prof_query("gemm_f64") sums the classes
-    ProfScope ps(gemm_class_name(transa, transb, tri_a, tri_b, nblk * p.nsplit * batch >= 512),
-                 stream, fl, by);
-    dim3 g1((unsigned)(nblk * p.nsplit), (unsigned)batch);
-    launch_glds(g1, stream, p, tm, tn, transa, transb, tri_a, tri_b);
+    ProfScope ps(gemm_class_name(transa, transb, tri_a, tri_b, pl.nblk * p.nsplit * batch >= 512),
+                 stream, pl.flops, pl.bytes);
+    dim3 g1((unsigned)(pl.nblk * p.nsplit), (unsigned)batch);
+    launch_glds(g1, stream, p, pl.tm, pl.tn, transa, transb, tri_a, tri_b);
     VG_LAUNCH_CHECK();
     if (p.nsplit > 1) {
       hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3((unsigned)ceil_div(m * n, 256), (unsigned)batch),
@@ -1019,14 +1039,12 @@ int gemm_launch_batched(int transa, int transb, int64_t m, int64_t n, int64_t k,
     }
     return 0;
   }
-  dim3 grid((unsigned)ceil_div(n, GBN), (unsigned)ceil_div(m, GBM), (unsigned)batch);
-  const double outs = (uplo_c == VGPOSP_LOWER) ? 0.5 * (double)m * (double)(m + 1) : (double)m * n;
-  ProfScope ps("gemm_f64", stream, 2.0 * batch * (double)k * outs,
-               8.0 * batch * ((double)m * k + (double)k * n + (beta != 0.0 ? 2.0 : 1.0) * outs));
-  if (!transa && !transb) hipLaunchKernelGGL((gemm_ref_kernel<false, false>), grid, dim3(256), 0, stream, p, va, vb);
-  else if (!transa && transb) hipLaunchKernelGGL((gemm_ref_kernel<false, true>), grid, dim3(256), 0, stream, p, va, vb);
-  else if (transa && !transb) hipLaunchKernelGGL((gemm_ref_kernel<true, false>), grid, dim3(256), 0, stream, p, va, vb);
-  else hipLaunchKernelGGL((gemm_ref_kernel<true, true>), grid, dim3(256), 0, stream, p, va, vb);
+  dim3 grid((unsigned)pl.tn, (unsigned)pl.tm, (unsigned)batch);
+  ProfScope ps("gemm_f64", stream, 2.0 * batch * (double)k * pl.outs, pl.bytes);
+  using Kernel = void (*)(GemmParams, int, int);
+  static const Kernel ref[4] = {gemm_ref_kernel<false, false>, gemm_ref_kernel<false, true>,
+                                gemm_ref_kernel<true, false>, gemm_ref_kernel<true, true>};
+  hipLaunchKernelGGL(ref[2 * !!transa + !!transb], grid, dim3(256), 0, stream, p, pl.va, pl.vb);
   VG_LAUNCH_CHECK();
   return 0;
 }
@@ -1054,7 +1072,7 @@ static std::atomic<int> g_split_min_k{16};
 
 // Split count for a launch with few output tiles and a long K: enough workgroups for 256 CUs
 // (about two per CU), each split at least 512 deep.
-static int auto_splits(int64_t m, int64_t n, int64_t k, int uplo_c, int transa = 0) {
+int gemm_auto_splits(int64_t m, int64_t n, int64_t k, int uplo_c, int transa) {
   if (n == 1 && uplo_c == VGPOSP_FULL) return gemv_splits(m, k, transa);
   const int64_t tm = ceil_div(m, GBM), tn = ceil_div(n, GBN);
   const int64_t nblk = uplo_c == VGPOSP_LOWER ? tm * (tm + 1) / 2 : tm * tn;
@@ -1077,7 +1095,7 @@ static int auto_splits(int64_t m, int64_t n, int64_t k, int uplo_c, int transa =
 // Partial elements problem g of a group needs (0 when it runs unsplit or off the fast kernel).
 static int64_t group_part_elems(int transa, int64_t m, int64_t n, int64_t k, int uplo_c) {
   if (m <= 0 || n <= 0 || k <= 0 || n == 1) return 0;
-  const int sp = auto_splits(m, n, k, uplo_c, transa);
+  const int sp = gemm_auto_splits(m, n, k, uplo_c, transa);
   return sp > 1 ? (int64_t)sp * m * n : 0;
 }
 
@@ -1098,36 +1116,26 @@ int gemm_launch_group(int count, const int* flags, const int64_t* dims, const do
     const int tra = flags[5 * g + 3], trb = flags[5 * g + 4];
     const int64_t m = dims[3 * g], n = dims[3 * g + 1], k = dims[3 * g + 2];
     if (m <= 0 || n <= 0) continue;
-    const bool fast = n > 1 && k > 0 && aligned16(A[g], lda[g]) && aligned16(B[g], ldb[g]) &&
-                      m % 2 == 0 && n % 2 == 0 && k % 2 == 0 && ng < GROUP_MAX;
     const int64_t pe = group_part_elems(ta, m, n, k, up);
-    if (!fast) {
+    GemmParams p{m, n, k, alpha[g], beta[g], A[g], lda[g], B[g], ldb[g], C[g], ldc[g], up, tra, trb,
+                 1, 0, 0, nullptr, 0, 0, 0, 0, tl_gemm_abort};
+    const int sp = pe > 0 ? (int)(pe / (m * n)) : 1;
+    const GemmPlan pl = gemm_plan(p, 1, sp, part + poff);
+    if (!pl.fast || ng == GROUP_MAX) {
       if (int rc = gemm_launch_split(ta, tb, m, n, k, alpha[g], A[g], lda[g], B[g], ldb[g], beta[g],
-                                     C[g], ldc[g], up, tra, trb, pe > 0 ? (int)(pe / (m * n)) : 1,
+                                     C[g], ldc[g], up, tra, trb, sp,
                                      pe > 0 ? part + poff : nullptr, s))
         return rc;
       poff += pe;
       continue;
     }
-    GemmParams p{m, n, k, alpha[g], beta[g], A[g], lda[g], B[g], ldb[g], C[g], ldc[g], up, tra, trb,
-                 1, 0, 0, nullptr, 0, 0, 0, 0, tl_gemm_abort};
-    const int tm = (int)ceil_div(m, GBM), tn = (int)ceil_div(n, GBN);
-    const int64_t nblk = up == VGPOSP_LOWER ? (int64_t)tm * (tm + 1) / 2 : (int64_t)tm * tn;
-    if (pe > 0) {
-      const int sp = (int)(pe / (m * n));
-      p.nblk = (int)nblk;
-      p.kchunk = ceil_div(ceil_div(k, sp), GBK) * GBK;
-      p.nsplit = (int)ceil_div(k, p.kchunk);
-      p.part = part + poff;
-      poff += pe;
-    }
-    const double outs = up == VGPOSP_LOWER ? 0.5 * (double)m * (double)(m + 1) : (double)m * n;
-    fl += 2.0 * (double)k * outs * ((tra && trb) ? (1.0 / 3.0) : (tra || trb) ? 0.5 : 1.0);
-    by += 8.0 * ((double)m * k + (double)k * n + (beta[g] != 0.0 ? 2.0 : 1.0) * outs);
+    poff += pe;
+    fl += pl.flops;
+    by += pl.bytes;
     gg.p[ng] = p;
-    gg.tiles_m[ng] = tm;
-    gg.tiles_n[ng] = tn;
-    gg.nwg[ng] = (int)(nblk * p.nsplit);
+    gg.tiles_m[ng] = pl.tm;
+    gg.tiles_n[ng] = pl.tn;
+    gg.nwg[ng] = (int)(pl.nblk * p.nsplit);
     gg.flags[ng] = (ta ? 1 : 0) | (tb ? 2 : 0) | (tra ? 4 : 0) | (trb ? 8 : 0);
     maxwg = std::max(maxwg, gg.nwg[ng]);
     rg.m[ng] = m;
@@ -1252,8 +1260,9 @@ static int gemm_launch_multi(int transa, int transb, int64_t m, int64_t n, int64
     x.beta[i - 1] = d[i].beta;
     outs += d[i].beta != 0.0 ? 2.0 : 1.0;
   }
-  const int tm = (int)ceil_div(m, GBM), tn = (int)ceil_div(n, GBN);
-  const int64_t nblk = (int64_t)tm * tn;
+  const GemmPlan pl = gemm_plan(p, 1, 1, nullptr);
+  const int tm = pl.tm, tn = pl.tn;
+  const int64_t nblk = pl.nblk;
   // the flops of the launch actually made (a Strassen product is a smaller classical product)
   ProfScope ps(gemm_class_name(transa, transb, 0, 0, nblk >= 512), stream,
                2.0 * (double)m * (double)n * (double)k,
@@ -1370,10 +1379,6 @@ void gemm_strassen_config(int64_t* min_dim, int* levels) {
 
 void gemm_set_abort(const int* flag) { tl_gemm_abort = flag; }
 
-int gemm_auto_splits(int64_t m, int64_t n, int64_t k, int uplo_c, int transa) {
-  return auto_splits(m, n, k, uplo_c, transa);
-}
-
 }  // namespace vgposp
 
 extern "C" int vgposp_gemm_set_split_depth(int min_k) {
@@ -1396,6 +1401,19 @@ extern "C" int vgposp_gemm_set_kloop(int kloop) {
 
 extern "C" int vgposp_gemm_kloop(void) { return vgposp::g_kloop.load(); }
 
+// The operand checks vgposp_gemm, vgposp_gemm_splitk and vgposp_gemm_strassen share: the same
+// arguments at the same positions (vgposp_gemm_batched has its strides in between).
+#define VGPOSP_GEMM_CHECK_OPERANDS()                                     \
+  VG_CHECK_ARG(m >= 0, 3);                                               \
+  VG_CHECK_ARG(n >= 0, 4);                                               \
+  VG_CHECK_ARG(k >= 0, 5);                                               \
+  VG_CHECK_ARG(A != nullptr || m == 0 || k == 0, 7);                     \
+  VG_CHECK_ARG(lda >= (transa ? (m > 0 ? m : 1) : (k > 0 ? k : 1)), 8);  \
+  VG_CHECK_ARG(B != nullptr || n == 0 || k == 0, 9);                     \
+  VG_CHECK_ARG(ldb >= (transb ? (k > 0 ? k : 1) : (n > 0 ? n : 1)), 10); \
+  VG_CHECK_ARG(C != nullptr || m == 0 || n == 0, 12);                    \
+  VG_CHECK_ARG(ldc >= (n > 0 ? n : 1), 13)
+
 extern "C" size_t vgposp_gemm_splitk_workspace_bytes(int64_t m, int64_t n, int64_t k, int uplo_c,
                                                      int splits) {
   using namespace vgposp;
@@ -1403,7 +1421,7 @@ extern "C" size_t vgposp_gemm_splitk_workspace_bytes(int64_t m, int64_t n, int64
   // the GEMV paths pick their split count by transa, which this query does not take: size for
   // the larger of the two
   if (splits <= 0)
-    splits = std::max(auto_splits(m, n, k, uplo_c, 0), auto_splits(m, n, k, uplo_c, 1));
+    splits = std::max(gemm_auto_splits(m, n, k, uplo_c, 0), gemm_auto_splits(m, n, k, uplo_c, 1));
   return splits > 1 ? 8 * (size_t)splits * m * n : 0;
 }
 
@@ -1414,18 +1432,10 @@ extern "C" int vgposp_gemm_splitk(int transa, int transb, int64_t m, int64_t n, 
                                   void* stream) {
   using namespace vgposp;
   clear_error();
-  VG_CHECK_ARG(m >= 0, 3);
-  VG_CHECK_ARG(n >= 0, 4);
-  VG_CHECK_ARG(k >= 0, 5);
-  VG_CHECK_ARG(A != nullptr || m == 0 || k == 0, 7);
-  VG_CHECK_ARG(lda >= (transa ? (m > 0 ? m : 1) : (k > 0 ? k : 1)), 8);
-  VG_CHECK_ARG(B != nullptr || n == 0 || k == 0, 9);
-  VG_CHECK_ARG(ldb >= (transb ? (k > 0 ? k : 1) : (n > 0 ? n : 1)), 10);
-  VG_CHECK_ARG(C != nullptr || m == 0 || n == 0, 12);
-  VG_CHECK_ARG(ldc >= (n > 0 ? n : 1), 13);
+  VGPOSP_GEMM_CHECK_OPERANDS();
   VG_CHECK_ARG(uplo_c == VGPOSP_FULL || (uplo_c == VGPOSP_LOWER && m == n), 14);
   if (m == 0 || n == 0) return 0;
-  if (splits <= 0) splits = k > 0 ? auto_splits(m, n, k, uplo_c, transa) : 1;
+  if (splits <= 0) splits = k > 0 ? gemm_auto_splits(m, n, k, uplo_c, transa) : 1;
   if (splits > 1) {
     const size_t need = 8 * (size_t)splits * m * n;
     if (ws == nullptr || ws_bytes < need) {
@@ -1443,15 +1453,7 @@ extern "C" int vgposp_gemm(int transa, int transb, int64_t m, int64_t n, int64_t
                            void* stream) {
   using namespace vgposp;
   clear_error();
-  VG_CHECK_ARG(m >= 0, 3);
-  VG_CHECK_ARG(n >= 0, 4);
-  VG_CHECK_ARG(k >= 0, 5);
-  VG_CHECK_ARG(A != nullptr || m == 0 || k == 0, 7);
-  VG_CHECK_ARG(lda >= (transa ? (m > 0 ? m : 1) : (k > 0 ? k : 1)), 8);
-  VG_CHECK_ARG(B != nullptr || n == 0 || k == 0, 9);
-  VG_CHECK_ARG(ldb >= (transb ? (k > 0 ? k : 1) : (n > 0 ? n : 1)), 10);
-  VG_CHECK_ARG(C != nullptr || m == 0 || n == 0, 12);
-  VG_CHECK_ARG(ldc >= (n > 0 ? n : 1), 13);
+  VGPOSP_GEMM_CHECK_OPERANDS();
   VG_CHECK_ARG(uplo_c == VGPOSP_FULL || (uplo_c == VGPOSP_LOWER && m == n), 14);
   return gemm_launch(transa, transb, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, uplo_c, tri_a,
                      tri_b, as_stream(stream));
@@ -1490,15 +1492,7 @@ extern "C" int vgposp_gemm_strassen(int transa, int transb, int64_t m, int64_t n
                                     void* ws, size_t ws_bytes, void* stream) {
   using namespace vgposp;
   clear_error();
-  VG_CHECK_ARG(m >= 0, 3);
-  VG_CHECK_ARG(n >= 0, 4);
-  VG_CHECK_ARG(k >= 0, 5);
-  VG_CHECK_ARG(A != nullptr || m == 0 || k == 0, 7);
-  VG_CHECK_ARG(lda >= (transa ? (m > 0 ? m : 1) : (k > 0 ? k : 1)), 8);
-  VG_CHECK_ARG(B != nullptr || n == 0 || k == 0, 9);
-  VG_CHECK_ARG(ldb >= (transb ? (k > 0 ? k : 1) : (n > 0 ? n : 1)), 10);
-  VG_CHECK_ARG(C != nullptr || m == 0 || n == 0, 12);
-  VG_CHECK_ARG(ldc >= (n > 0 ? n : 1), 13);
+  VGPOSP_GEMM_CHECK_OPERANDS();
   VG_CHECK_ARG(levels >= 0 && levels <= 2, 14);
   const size_t need = vgposp_gemm_strassen_workspace_bytes(m, n, k, levels);
   if (need > 0 && (ws == nullptr || ws_bytes < need)) {
@@ -1514,7 +1508,7 @@ extern "C" size_t vgposp_gemm_batched_workspace_bytes(int64_t m, int64_t n, int6
                                                       int batch) {
   using namespace vgposp;
   if (m <= 0 || n <= 0 || k <= 0 || batch <= 0 || n == 1) return 0;
-  const int sp = auto_splits(m, n, k, uplo_c, 0);
+  const int sp = gemm_auto_splits(m, n, k, uplo_c, 0);
   return sp > 1 ? 8 * (size_t)sp * m * n * batch : 0;
 }
 
@@ -1537,7 +1531,7 @@ extern "C" int vgposp_gemm_batched(int transa, int transb, int64_t m, int64_t n,
   VG_CHECK_ARG(uplo_c == VGPOSP_FULL || (uplo_c == VGPOSP_LOWER && m == n), 17);
   VG_CHECK_ARG(batch >= 1 && batch <= 65535, 20);
   if (m == 0 || n == 0) return 0;
-  int sp = (k > 0 && n > 1) ? auto_splits(m, n, k, uplo_c, transa) : 1;
+  int sp = (k > 0 && n > 1) ? gemm_auto_splits(m, n, k, uplo_c, transa) : 1;
   if (sp > 1 && (ws == nullptr || ws_bytes < 8 * (size_t)sp * m * n * batch)) sp = 1;
   return gemm_launch_batched(transa, transb, m, n, k, alpha, A, lda, sA, B, ldb, sB, beta, C, ldc,
                              sC, uplo_c, tri_a, tri_b, sp, sp > 1 ? static_cast<double*>(ws) : nullptr,

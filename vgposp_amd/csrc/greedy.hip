@@ -18,16 +18,9 @@
 #include <algorithm>
 #include <cfloat>
 
-#include "common.h"
+#include "dense.h"
 
 namespace vgposp {
-
-int potrf_one(double* A, int64_t n, int64_t lda, int invert, double* diag_out, int* info,
-              void* ws, hipStream_t stream, bool early = false, bool strassen = true);
-size_t potrf_ws_bytes(int64_t n);
-int partial_inverse(double* A, int64_t n, int64_t lda, int64_t c0, int64_t c1, double* tmp,
-                    void* ws, hipStream_t s);
-size_t partial_inverse_tmp_bytes(int64_t n, int64_t c0, int64_t c1);
 
 constexpr int RC = 512;     // rows per chunk of the transposed mat-vec
 constexpr int CT = 256;     // columns per mat-vec workgroup
@@ -644,10 +637,7 @@ extern "C" int vgposp_greedy_finish_slab(double* Sigma, int64_t n, int64_t lda, 
                7);
   VG_CHECK_ARG(ws != nullptr, 9);
   GreedyWS w = greedy_layout(ws, n, kmax);
-  if (ws_bytes < w.bytes) {
-    set_error("vgposp_greedy_finish_slab: workspace %zu < %zu bytes", ws_bytes, w.bytes);
-    return VGPOSP_E_WS;
-  }
+  VG_CHECK_WS(ws_bytes, w.bytes);
   if (c1 == c0) return 0;
   hipStream_t s = as_stream(stream);
   int rc = partial_inverse(Sigma, n, lda, c0, c1, tmp, greedy_fact_ws(ws, w, n), s);

@@ -18,27 +18,9 @@
 // The strictly upper triangle is never read or written.
 #include <algorithm>
 
-#include "common.h"
+#include "dense.h"
 
 namespace vgposp {
-
-int gemm_launch_split(int transa, int transb, int64_t m, int64_t n, int64_t k, double alpha,
-                      const double* A, int64_t lda, const double* B, int64_t ldb, double beta,
-                      double* C, int64_t ldc, int uplo_c, int tri_a, int tri_b, int nsplit,
-                      double* part, hipStream_t stream);
-int gemm_auto_splits(int64_t m, int64_t n, int64_t k, int uplo_c, int transa);
-void gemm_set_abort(const int* flag);
-int gemm_launch_batched(int transa, int transb, int64_t m, int64_t n, int64_t k, double alpha,
-                        const double* A, int64_t lda, int64_t sA, const double* B, int64_t ldb,
-                        int64_t sB, double beta, double* C, int64_t ldc, int64_t sC, int uplo_c,
-                        int tri_a, int tri_b, int nsplit, double* part, int64_t sP, int batch,
-                        hipStream_t stream);
-int gemm_strassen(int transa, int transb, int64_t m, int64_t n, int64_t k, double alpha,
-                  const double* A, int64_t lda, const double* B, int64_t ldb, double beta, double* C,
-                  int64_t ldc, int levels, int64_t min_dim, double* ws, int64_t ws_elems,
-                  hipStream_t stream);
-int64_t gemm_strassen_ws_elems(int64_t m, int64_t n, int64_t k, int levels, int64_t min_dim);
-void gemm_strassen_config(int64_t* min_dim, int* levels);
 
 constexpr int NB = 128;        // leaf size (== GEMM tile, so trsm leaves are in place)
 
@@ -378,16 +360,38 @@ struct Fact {
 constexpr int64_t PART_ELEMS = 8 << 20;
 constexpr int64_t PART_ELEMS_BATCHED = 2 << 20;
 
+// A plain m x n x k product takes at least one Strassen level at this threshold (the launching
+// recursion and StrassenNeed, which sizes its scratch, both ask here).
+static bool strassen_eligible(int64_t m, int64_t n, int64_t k, int64_t min_dim) {
+  return gemm_strassen_ws_elems(m, n, k, 1, min_dim) > 0;
+}
+
+// With Strassen scratch, a structured product whose plain part would be eligible is split once
+// into two half-size structured products and that plain product (half of its flops), and so on
+// down: the plain parts then go through gemm_strassen.  Without scratch, or below the threshold,
+// each is the single structured launch.
+static bool split_plain(const Fact& f, int64_t m, int64_t n, int64_t k) {
+  return f.str_ws != nullptr && f.batch == 1 && strassen_eligible(m, n, k, f.str_min);
+}
+
 // C = alpha op(A) op(B) + beta C with the split count of vgposp_gemm_splitk, reduced to what the
 // partials area holds.  In-place operands (C also read as A) are safe: the split kernels only
 // write the partials, the reduction writes C after all of them.
 static int pgemm(const Fact& f, int transa, int transb, int64_t m, int64_t n, int64_t k,
                  double alpha, const double* A, int64_t lda, const double* B, int64_t ldb,
                  double beta, double* C, int64_t ldc, int uplo_c, int tri_a, int tri_b) {
-  if (f.str_ws != nullptr && f.batch == 1 && uplo_c == VGPOSP_FULL && !tri_a && !tri_b &&
-      gemm_strassen_ws_elems(m, n, k, 1, f.str_min) > 0)
+  if (uplo_c == VGPOSP_FULL && !tri_a && !tri_b && split_plain(f, m, n, k)) {
+    // the scratch was sized by StrassenNeed's walk over these launches: a product it did not
+    // plan for is an error here, not a quietly shallower gemm_strassen
+    const int64_t need = gemm_strassen_ws_elems(m, n, k, f.str_levels, f.str_min);
+    if (need > f.str_elems) {
+      set_error("potrf: Strassen scratch %lld < %lld doubles for the %lld x %lld x %lld product",
+                (long long)f.str_elems, (long long)need, (long long)m, (long long)n, (long long)k);
+      return VGPOSP_E_WS;
+    }
     return gemm_strassen(transa, transb, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, f.str_levels,
                          f.str_min, f.str_ws, f.str_elems, f.s);
+  }
   int sp = f.part ? gemm_auto_splits(m, n, k, uplo_c, transa) : 1;
   while (sp > 1 && (int64_t)sp * m * n > f.part_elems) --sp;
   if (f.batch > 1)
@@ -396,14 +400,6 @@ static int pgemm(const Fact& f, int transa, int transb, int64_t m, int64_t n, in
                                sp > 1 ? f.part : nullptr, f.sW, f.batch, f.s);
   return gemm_launch_split(transa, transb, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, uplo_c,
                            tri_a, tri_b, sp, sp > 1 ? f.part : nullptr, f.s);
-}
-
-// With Strassen scratch, a structured product whose plain part would be eligible is split once
-// into two half-size structured products and that plain product (half of its flops), and so on
-// down: the plain parts then go through gemm_strassen.  Without scratch, or below the threshold,
-// each is the single structured launch.
-static bool split_plain(const Fact& f, int64_t m, int64_t n, int64_t k) {
-  return f.str_ws != nullptr && f.batch == 1 && gemm_strassen_ws_elems(m, n, k, 1, f.str_min) > 0;
 }
 
 // C (n x n, lower) = alpha A A^T + beta C,  A n x k
@@ -611,46 +607,55 @@ static int potrf_rec(const Fact& f, double* A, int64_t n, int64_t col0, bool blo
   return trtri_rec(f, X, NBI, n, col0, false);
 }
 
-// The workspace every entry point lays out (make_fact): leaf inverses | trtri scratch | block
-// inverses + TRSM scratch | split-K partials.
-static size_t potrf_ws_base(int64_t n) {
-  const int64_t leaves = (n + NB - 1) / NB;
-  const int64_t n1 = n > NB ? split_point(n) : 0;
-  const int64_t blk = n > NBI ? 2 * n * NBI : 0;  // xinv + tmp
-  const int64_t part = n > NB ? PART_ELEMS : 0;
-  return (size_t)(leaves * NB * NB + n1 * (n - n1) + blk + part + 64) * sizeof(double);
+// The workspace of every entry point, as element offsets from its base: leaf inverses | trtri
+// scratch | block inverses | TRSM scratch (both only for n > NBI) | split-K partials (n > NB) |
+// 64 spare doubles | Strassen scratch.  The sharded entry points and partial_inverse read the
+// first five in a workspace that another call filled, so their offsets depend on n alone.
+struct PotrfLayout {
+  int64_t n, work, xinv, tmp, part, part_elems, strassen, strassen_elems, total;
+  size_t bytes() const { return (size_t)total * sizeof(double); }
+};
+
+static PotrfLayout potrf_layout(int64_t n, int64_t part_elems, int64_t strassen_elems) {
+  const int64_t n1 = n > NB ? split_point(n) : 0, blk = n > NBI ? n * NBI : 0;
+  PotrfLayout l{n};
+  l.work = ceil_div(n, NB) * NB * NB;
+  l.xinv = l.work + n1 * (n - n1);
+  l.tmp = l.xinv + blk;
+  l.part = l.tmp + blk;
+  l.part_elems = n > NB ? part_elems : 0;
+  l.strassen = l.part + l.part_elems + 64;
+  l.strassen_elems = strassen_elems;
+  l.total = l.strassen + strassen_elems;
+  return l;
 }
 
-// Strassen scratch of potrf_one, appended AFTER that layout (the sharded entry points and the
-// slab finish read fixed places in it): the largest operand-temporary need over the plain
-// products that potrf_rec / trsm_rec / psyrk and trtri_rec / ptrmm_b / ptrmm_a launch for this n
-// (a walk over the same splits, a few hundred nodes at n = 65,536).  0 when no product is
-// eligible: nothing is appended then and every launch is the classical one.
+// Strassen scratch of potrf_one, the layout's last area: the largest operand-temporary need over
+// the plain products that potrf_rec / trsm_rec / psyrk and trtri_rec / ptrmm_b / ptrmm_a launch
+// for this n (a walk over the same splits, a few hundred nodes at n = 65,536).  0 when no product
+// is eligible: nothing is appended then and every launch is the classical one.
 struct StrassenNeed {
   int64_t min_dim;
   int levels;
   int64_t need = 0;
-  bool split(int64_t m, int64_t n, int64_t k) const {
-    return gemm_strassen_ws_elems(m, n, k, 1, min_dim) > 0;
-  }
   void plain(int64_t m, int64_t n, int64_t k) {
     need = std::max(need, gemm_strassen_ws_elems(m, n, k, levels, min_dim));
   }
   void syrk(int64_t n, int64_t k) {
     const int64_t h = n / 2;
-    if (n % 2 != 0 || !split(h, h, k)) return;
+    if (n % 2 != 0 || !strassen_eligible(h, h, k, min_dim)) return;
     plain(h, h, k);
     syrk(h, k);
   }
   void trmm_b(int64_t m, int64_t n) {
     const int64_t h = n / 2;
-    if (n % 2 != 0 || !split(m, h, h)) return;
+    if (n % 2 != 0 || !strassen_eligible(m, h, h, min_dim)) return;
     plain(m, h, h);
     trmm_b(m, h);
   }
   void trmm_a(int64_t m, int64_t n) {
     const int64_t h = m / 2;
-    if (m % 2 != 0 || !split(h, n, h)) return;
+    if (m % 2 != 0 || !strassen_eligible(h, n, h, min_dim)) return;
     plain(h, n, h);
     trmm_a(h, n);
   }
@@ -680,11 +685,28 @@ static int64_t potrf_strassen_elems(int64_t n, int64_t min_dim, int levels) {
   return s.need;
 }
 
+// One matrix: 64 MiB of partials.  Without Strassen scratch this is what the sharded entry points
+// and partial_inverse address (potrf_one's scratch, if any, lies behind it).
+static PotrfLayout potrf_layout_one(int64_t n, int64_t strassen_elems = 0) {
+  return potrf_layout(n, PART_ELEMS, strassen_elems);
+}
+
+// Each matrix of a batch factored by one recursion: 16 MiB of partials (use_part) or none (large
+// batches fill the GPU through the batch dimension; 16 MiB of partials per matrix would not
+// fit), never Strassen scratch.
+static PotrfLayout potrf_layout_batched(int64_t n, bool use_part) {
+  return potrf_layout(n, use_part ? PART_ELEMS_BATCHED : 0, 0);
+}
+
 size_t potrf_ws_bytes(int64_t n) {
   int64_t min_dim;
   int levels;
   gemm_strassen_config(&min_dim, &levels);
-  return potrf_ws_base(n) + (size_t)potrf_strassen_elems(n, min_dim, levels) * sizeof(double);
+  return potrf_layout_one(n, potrf_strassen_elems(n, min_dim, levels)).bytes();
+}
+
+size_t potrf_ws_bytes_opt(int64_t n, bool use_part) {
+  return potrf_layout_batched(n, use_part).bytes();
 }
 
 static int ensure_leaf_attr() {
@@ -700,53 +722,39 @@ static int ensure_leaf_attr() {
 static int trsm_left_rec(const Fact& f, const double* Lp, int64_t ldl, int64_t n, int64_t col0,
                          int trans, double* B, int64_t m, int64_t ldb);
 
-static Fact make_fact(int64_t n, int64_t lda, void* ws, double* diag_out, int* info,
+// The layout's offsets as pointers into ws (an area of no elements is null).
+static Fact make_fact(const PotrfLayout& l, int64_t lda, void* ws, double* diag_out, int* info,
                       hipStream_t stream) {
-  const int64_t leaves = (n + NB - 1) / NB;
-  const int64_t n1 = n > NB ? split_point(n) : 0;
   double* base = static_cast<double*>(ws);
-  double* work = base + leaves * NB * NB;
-  const bool blocks = n > NBI;  // a whole problem <= NBI never needs block inverses
-  double* xinv = blocks ? work + n1 * (n - n1) : nullptr;
-  double* tmp = blocks ? xinv + n * NBI : nullptr;
-  double* part = n > NB ? work + n1 * (n - n1) + (blocks ? 2 * n * NBI : 0) : nullptr;
-  Fact f{lda, base, work, xinv, tmp, diag_out, info, part, stream};
-  f.part_elems = PART_ELEMS;
+  const bool blocks = l.n > NBI;  // a whole problem <= NBI never needs block inverses
+  Fact f{lda, base, base + l.work, blocks ? base + l.xinv : nullptr,
+         blocks ? base + l.tmp : nullptr, diag_out, info,
+         l.part_elems > 0 ? base + l.part : nullptr, stream, l.part_elems};
+  f.str_ws = l.strassen_elems > 0 ? base + l.strassen : nullptr;
+  f.str_elems = l.strassen_elems;
   return f;
 }
 
 // `batch` matrices at stride sA factored by ONE recursion: every launch covers all of them (the
 // leaves as one workgroup per matrix, the GEMMs with a batch grid dimension), so B small
 // factorizations cost the launches and the latency chain of one.  ws holds B copies of the
-// single-matrix workspace.
-// Per-matrix workspace of a batched factorization: the single-matrix layout with a 16 MB partials
-// area (use_part) or none (large batches fill the GPU through the batch dimension; 16 MB of
-// partials per matrix would not fit).
-size_t potrf_ws_bytes_opt(int64_t n, bool use_part) {
-  const int64_t part = n > NB ? (use_part ? PART_ELEMS_BATCHED : 0) : 0;
-  return potrf_ws_base(n) - (size_t)((n > NB ? PART_ELEMS : 0) - part) * sizeof(double);
-}
-
+// per-matrix workspace (potrf_layout_batched).
 int potrf_batched(double* A, int64_t n, int64_t lda, int64_t sA, int batch, int invert,
                   double* diag_out, int* info, void* ws, hipStream_t stream, bool use_part) {
   if (int rc = ensure_leaf_attr()) return rc;
-  if (n <= NB) {
-    // one launch, one workgroup per matrix (no workspace needed)
-    ProfScope ps("potrf_diag", stream, batch * 2.0 * n * (double)n * n / 3.0,
-                 batch * 16.0 * n * (double)n);
-    hipLaunchKernelGGL(potrf_leaf_kernel, dim3(batch), dim3(LEAF_THREADS), leaf_shmem(), stream, A,
-                       lda, (int)n, (int64_t)0, invert, (double*)nullptr, diag_out, info, sA,
-                       (int64_t)0, batch > 1 ? n : (int64_t)-1);
-    VG_LAUNCH_CHECK();
-    return 0;
+  if (n <= NB) {  // one launch, one workgroup per matrix, inverted in LDS: no workspace
+    Fact f{lda, nullptr, nullptr, nullptr, nullptr, diag_out, info, nullptr, stream};
+    f.batch = batch;
+    f.sA = sA;
+    f.diag_n = n;
+    return leaf_factor(f, A, (int)n, 0, invert);
   }
   const bool blocks = n > NBI;
-  Fact f = make_fact(n, lda, ws, diag_out, info, stream);
-  if (!use_part) f.part = nullptr;
-  f.part_elems = PART_ELEMS_BATCHED;
+  const PotrfLayout l = potrf_layout_batched(n, use_part);
+  Fact f = make_fact(l, lda, ws, diag_out, info, stream);
   f.batch = batch;
   f.sA = sA;
-  f.sW = (int64_t)(potrf_ws_bytes_opt(n, use_part) / sizeof(double));
+  f.sW = l.total;
   f.ws0 = static_cast<const double*>(ws);
   f.diag_n = n;
   int rc = potrf_rec(f, A, n, 0, blocks);
@@ -758,19 +766,14 @@ int potrf_one(double* A, int64_t n, int64_t lda, int invert, double* diag_out, i
               void* ws, hipStream_t stream, bool early, bool strassen) {
   if (int rc = ensure_leaf_attr()) return rc;
   const bool blocks = n > NBI;
-  Fact f = make_fact(n, lda, ws, diag_out, info, stream);
+  int64_t min_dim = 0;
+  int levels = 0;  // the setting is read once: scratch size, threshold and levels belong together
+  if (strassen) gemm_strassen_config(&min_dim, &levels);
+  Fact f = make_fact(potrf_layout_one(n, potrf_strassen_elems(n, min_dim, levels)), lda, ws,
+                     diag_out, info, stream);
+  f.str_min = min_dim;
+  f.str_levels = levels;
   f.early = early;
-  if (strassen) {  // the setting is read once: scratch size, threshold and levels belong together
-    int64_t min_dim;
-    int levels;
-    gemm_strassen_config(&min_dim, &levels);
-    if (const int64_t se = potrf_strassen_elems(n, min_dim, levels)) {
-      f.str_ws = static_cast<double*>(ws) + potrf_ws_base(n) / sizeof(double);
-      f.str_elems = se;
-      f.str_min = min_dim;
-      f.str_levels = levels;
-    }
-  }
   AbortScope scope(early ? info : nullptr);
   int rc = potrf_rec(f, A, n, 0, blocks);
   if (rc || !invert) return rc;
@@ -791,7 +794,7 @@ int partial_inverse(double* A, int64_t n, int64_t lda, int64_t c0, int64_t c1, d
                     void* ws, hipStream_t s) {
   const int64_t w = c1 - c0, m2 = n - c1;
   if (w <= 0) return 0;
-  Fact f = make_fact(n, lda, ws, nullptr, nullptr, s);
+  Fact f = make_fact(potrf_layout_one(n), lda, ws, nullptr, nullptr, s);
   f.tmp = tmp + m2 * w;  // the TRSM leaves' out-of-place scratch: NB x w
   int rc;
   double* A11 = A + c0 * lda + c0;
@@ -819,7 +822,7 @@ int partial_inverse(double* A, int64_t n, int64_t lda, int64_t c0, int64_t c1, d
 int potrf_block(double* A, int64_t n, int64_t lda, int64_t col0, int64_t nb, int* info, void* ws,
                 hipStream_t s) {
   if (int rc = ensure_leaf_attr()) return rc;
-  Fact f = make_fact(n, lda, ws, nullptr, info, s);
+  Fact f = make_fact(potrf_layout_one(n), lda, ws, nullptr, info, s);
   return potrf_rec(f, A + col0 * (lda + 1), nb, col0, n > NBI);
 }
 
@@ -827,7 +830,7 @@ int potrf_block(double* A, int64_t n, int64_t lda, int64_t col0, int64_t nb, int
 //   A21 <- A21 L11^-T
 int potrf_panel(double* A, int64_t n, int64_t lda, int64_t col0, int64_t n1, int64_t r0,
                 int64_t r1, void* ws, hipStream_t s) {
-  Fact f = make_fact(n, lda, ws, nullptr, nullptr, s);
+  Fact f = make_fact(potrf_layout_one(n), lda, ws, nullptr, nullptr, s);
   double* A11 = A + col0 * (lda + 1);
   return trsm_rec(f, A11 + (n1 + r0) * lda, r1 - r0, lda, A11, n1, col0, n > NBI);
 }
@@ -836,7 +839,7 @@ int potrf_panel(double* A, int64_t n, int64_t lda, int64_t col0, int64_t n1, int
 //   A22 -= L21 L21^T   (the rectangle left of the band's diagonal square, then the square)
 int potrf_trailing(double* A, int64_t n, int64_t lda, int64_t col0, int64_t n1, int64_t b0,
                    int64_t b1, void* ws, hipStream_t s) {
-  Fact f = make_fact(n, lda, ws, nullptr, nullptr, s);
+  Fact f = make_fact(potrf_layout_one(n), lda, ws, nullptr, nullptr, s);
   double* L21 = A + (col0 + n1) * lda + col0;
   double* A22 = L21 + n1;
   const int64_t m = b1 - b0;
@@ -925,19 +928,30 @@ static int trsm_left_rec(const Fact& f, const double* Lp, int64_t ldl, int64_t n
   return trsm_left_rec(f, Lp, ldl, a, col0, 1, B, m, ldb);
 }
 
+// The TRSM workspace, as element offsets: leaf inverses | the leaves' out-of-place output (NB x m)
+// | split-K partials (the products are at most n x m: 16 MiB) | 64 spare doubles, the first of
+// which holds the leaf kernel's status word.
+struct TrsmLayout {
+  int64_t tmp, part, part_elems, status, total;
+};
+
+static TrsmLayout trsm_layout(int64_t n, int64_t m) {
+  const int64_t tmp = ceil_div(n, NB) * NB * NB, part = tmp + NB * m;
+  const int64_t status = part + PART_ELEMS_BATCHED;
+  return {tmp, part, PART_ELEMS_BATCHED, status, status + 64};
+}
+
 size_t trsm_ws_bytes(int64_t n, int64_t m) {
-  const int64_t leaves = (n + NB - 1) / NB;
-  return (size_t)(leaves * NB * NB + NB * m + PART_ELEMS_BATCHED + 64) * sizeof(double);
+  return (size_t)trsm_layout(n, m).total * sizeof(double);
 }
 
 int trsm_left(const double* L, int64_t n, int64_t ldl, int trans, double* B, int64_t m,
               int64_t ldb, void* ws, hipStream_t s) {
   if (int rc = ensure_leaf_attr()) return rc;
+  const TrsmLayout l = trsm_layout(n, m);
   double* leaves = static_cast<double*>(ws);
-  const int64_t nl = (n + NB - 1) / NB, nfull = n / NB;
-  double* tmp = leaves + nl * NB * NB;
-  double* part = tmp + NB * m;
-  int* dummy = reinterpret_cast<int*>(part + PART_ELEMS_BATCHED);  // the invert-only leaves never write it
+  const int64_t nl = ceil_div(n, NB), nfull = n / NB;
+  int* dummy = reinterpret_cast<int*>(leaves + l.status);  // the invert-only leaves never write it
   {
     ProfScope ps("trtri_leaf", s, 0.0, 8.0 * NB * NB * 2 * nl);
     if (nfull > 0)
@@ -951,8 +965,8 @@ int trsm_left(const double* L, int64_t n, int64_t ldl, int trans, double* B, int
                          (int64_t)0);
     VG_LAUNCH_CHECK();
   }
-  Fact f{ldl, leaves, nullptr, nullptr, tmp, nullptr, dummy, part, s};
-  f.part_elems = PART_ELEMS_BATCHED;  // the TRSM's products are at most n x m: 16 MB as before
+  Fact f{ldl, leaves, nullptr, nullptr, leaves + l.tmp, nullptr, dummy, leaves + l.part, s,
+         l.part_elems};
   return trsm_left_rec(f, L, ldl, n, 0, trans, B, m, ldb);
 }
 
@@ -976,10 +990,7 @@ extern "C" int vgposp_trsm_lower(const double* L, int64_t n, int64_t ldl, int tr
   VG_CHECK_ARG(ldb >= (nrhs > 0 ? nrhs : 1), 7);
   VG_CHECK_ARG(ws != nullptr || n == 0, 8);
   if (n == 0 || nrhs == 0) return 0;
-  if (ws_bytes < trsm_ws_bytes(n, nrhs)) {
-    set_error("vgposp_trsm_lower: workspace %zu < %zu bytes", ws_bytes, trsm_ws_bytes(n, nrhs));
-    return VGPOSP_E_WS;
-  }
+  VG_CHECK_WS(ws_bytes, trsm_ws_bytes(n, nrhs));
   return trsm_left(L, n, ldl, trans, B, nrhs, ldb, ws, as_stream(stream));
 }
 
@@ -1010,25 +1021,10 @@ extern "C" int vgposp_potrf_lower(double* A, int64_t n, int64_t lda, int64_t str
   hipStream_t s = as_stream(stream);
   VG_HIP(vg_memset(info, 0, sizeof(int) * batch, s));
   if (n == 0) return 0;
-  if (ws_bytes < potrf_ws_bytes(n)) {
-    set_error("vgposp_potrf_lower: workspace %zu < %zu bytes", ws_bytes, potrf_ws_bytes(n));
-    return VGPOSP_E_WS;
-  }
-  if (n <= NB && batch > 1) {
-    // one launch, one workgroup per matrix (e.g. the calc_H likelihood surface)
-    static bool attr_set = false;
-    if (!attr_set) {
-      VG_HIP(hipFuncSetAttribute((const void*)potrf_leaf_kernel,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)leaf_shmem()));
-      attr_set = true;
-    }
-    ProfScope ps("potrf_diag", s, batch * 2.0 * n * (double)n * n / 3.0, batch * 16.0 * n * (double)n);
-    hipLaunchKernelGGL(potrf_leaf_kernel, dim3(batch), dim3(LEAF_THREADS), leaf_shmem(), s, A, lda,
-                       (int)n, (int64_t)0, invert, (double*)nullptr, diag_out, info, stride);
-    VG_LAUNCH_CHECK();
-    return 0;
-  }
-  if (batch > 1 && ws_bytes >= vgposp_potrf_batched_workspace_bytes(n, (int)batch))
+  VG_CHECK_WS(ws_bytes, potrf_ws_bytes(n));
+  // one recursion over the batch where the workspace holds it; n <= NB is one launch, one
+  // workgroup per matrix (e.g. the calc_H likelihood surface), and needs none
+  if (batch > 1 && (n <= NB || ws_bytes >= vgposp_potrf_batched_workspace_bytes(n, (int)batch)))
     return potrf_batched(A, n, lda, stride, batch, invert, diag_out, info, ws, s, true);
   for (int b = 0; b < batch; ++b) {
     int rc = potrf_one(A + b * stride, n, lda, invert, diag_out ? diag_out + (int64_t)b * n : nullptr,
@@ -1053,31 +1049,30 @@ extern "C" int vgposp_potrf_block(double* A, int64_t n, int64_t lda, int64_t col
   VG_CHECK_ARG(nb >= 1 && col0 + nb <= n, 5);
   VG_CHECK_ARG(info != nullptr, 6);
   VG_CHECK_ARG(ws != nullptr, 7);
-  if (ws_bytes < potrf_ws_bytes(n)) {
-    set_error("vgposp_potrf_block: workspace %zu < %zu bytes", ws_bytes, potrf_ws_bytes(n));
-    return VGPOSP_E_WS;
-  }
+  VG_CHECK_WS(ws_bytes, potrf_ws_bytes(n));
   return potrf_block(A, n, lda, col0, nb, info, ws, as_stream(stream));
 }
+
+// The checks vgposp_potrf_panel and vgposp_potrf_trailing share: rows [lo, hi) below the split
+// n1 of node (col0, nsub); smaller nodes are vgposp_potrf_block's.
+#define VGPOSP_POTRF_NODE_CHECK(lo, hi)              \
+  VG_CHECK_ARG(A != nullptr, 1);                     \
+  VG_CHECK_ARG(n >= 1, 2);                           \
+  VG_CHECK_ARG(lda >= n, 3);                         \
+  VG_CHECK_ARG(col0 >= 0 && col0 % NB == 0, 4);      \
+  VG_CHECK_ARG(nsub > NBI && col0 + nsub <= n, 5);   \
+  const int64_t n1 = split_point(nsub);              \
+  VG_CHECK_ARG(lo >= 0 && lo <= hi, 6);              \
+  VG_CHECK_ARG(hi <= nsub - n1, 7);                  \
+  VG_CHECK_ARG(ws != nullptr, 8);                    \
+  VG_CHECK_WS(ws_bytes, potrf_ws_bytes(n))
 
 extern "C" int vgposp_potrf_panel(double* A, int64_t n, int64_t lda, int64_t col0, int64_t nsub,
                                   int64_t r0, int64_t r1, void* ws, size_t ws_bytes,
                                   void* stream) {
   using namespace vgposp;
   clear_error();
-  VG_CHECK_ARG(A != nullptr, 1);
-  VG_CHECK_ARG(n >= 1, 2);
-  VG_CHECK_ARG(lda >= n, 3);
-  VG_CHECK_ARG(col0 >= 0 && col0 % NB == 0, 4);
-  VG_CHECK_ARG(nsub > NBI && col0 + nsub <= n, 5);  // smaller nodes: vgposp_potrf_block
-  const int64_t n1 = split_point(nsub);
-  VG_CHECK_ARG(r0 >= 0 && r0 <= r1, 6);
-  VG_CHECK_ARG(r1 <= nsub - n1, 7);
-  VG_CHECK_ARG(ws != nullptr, 8);
-  if (ws_bytes < potrf_ws_bytes(n)) {
-    set_error("vgposp_potrf_panel: workspace %zu < %zu bytes", ws_bytes, potrf_ws_bytes(n));
-    return VGPOSP_E_WS;
-  }
+  VGPOSP_POTRF_NODE_CHECK(r0, r1);
   if (r1 == r0) return 0;
   return potrf_panel(A, n, lda, col0, n1, r0, r1, ws, as_stream(stream));
 }
@@ -1087,19 +1082,7 @@ extern "C" int vgposp_potrf_trailing(double* A, int64_t n, int64_t lda, int64_t 
                                      size_t ws_bytes, void* stream) {
   using namespace vgposp;
   clear_error();
-  VG_CHECK_ARG(A != nullptr, 1);
-  VG_CHECK_ARG(n >= 1, 2);
-  VG_CHECK_ARG(lda >= n, 3);
-  VG_CHECK_ARG(col0 >= 0 && col0 % NB == 0, 4);
-  VG_CHECK_ARG(nsub > NBI && col0 + nsub <= n, 5);
-  const int64_t n1 = split_point(nsub);
-  VG_CHECK_ARG(b0 >= 0 && b0 <= b1, 6);
-  VG_CHECK_ARG(b1 <= nsub - n1, 7);
-  VG_CHECK_ARG(ws != nullptr, 8);
-  if (ws_bytes < potrf_ws_bytes(n)) {
-    set_error("vgposp_potrf_trailing: workspace %zu < %zu bytes", ws_bytes, potrf_ws_bytes(n));
-    return VGPOSP_E_WS;
-  }
+  VGPOSP_POTRF_NODE_CHECK(b0, b1);
   return potrf_trailing(A, n, lda, col0, n1, b0, b1, ws, as_stream(stream));
 }
 

@@ -16,18 +16,9 @@
 // fp32 factor too poor to refine), k > 0 when fp32 pivot k fails.
 #include <algorithm>
 
-#include "common.h"
+#include "dense.h"
 
 namespace vgposp {
-
-int trsm_left(const double* L, int64_t n, int64_t ldl, int trans, double* B, int64_t m, int64_t ldb,
-              void* ws, hipStream_t s);
-size_t trsm_ws_bytes(int64_t n, int64_t m);
-int gemm_launch_split(int transa, int transb, int64_t m, int64_t n, int64_t k, double alpha,
-                      const double* A, int64_t lda, const double* B, int64_t ldb, double beta,
-                      double* C, int64_t ldc, int uplo_c, int tri_a, int tri_b, int nsplit,
-                      double* part, hipStream_t stream);
-int gemm_auto_splits(int64_t m, int64_t n, int64_t k, int uplo_c, int transa);
 
 constexpr int64_t RPART = 1 << 23;  // split-K partials of the refinement GEMMs (64 MiB)
 
@@ -287,10 +278,7 @@ extern "C" int vgposp_potrf_mixed(const double* A, int64_t n, int64_t lda, doubl
   VG_CHECK_ARG(info != nullptr, 9);
   VG_CHECK_ARG(ws != nullptr, 10);
   MixedWS w = mixed_layout(ws, n);
-  if (ws_bytes < w.bytes) {
-    set_error("vgposp_potrf_mixed: workspace %zu < %zu bytes", ws_bytes, w.bytes);
-    return VGPOSP_E_WS;
-  }
+  VG_CHECK_WS(ws_bytes, w.bytes);
   hipStream_t s = as_stream(stream);
   VG_HIP(vg_memset(info, 0, sizeof(int), s));
   VG_HIP(vg_memset(w.amax, 0, sizeof(unsigned long long), s));
