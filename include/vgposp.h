@@ -120,6 +120,13 @@ int vgposp_gemm_split_depth(void);
  * results.  Read at launch; not read from the environment. */
 int vgposp_gemm_set_kloop(int kloop);
 int vgposp_gemm_kloop(void);
+/* Process-wide choice of the fast GEMM kernels' epilogue (every entry point that launches them,
+ * grouped launches included): 0 = the element-wise reference (one memory round trip per
+ * accumulator element and destination), 1 = the batched one (16 loads, one wait, 16 stores per
+ * group and destination; interior tiles without tests).  Both give bit-identical results.  Read
+ * at launch; not read from the environment. */
+int vgposp_gemm_set_epilogue(int epilogue);
+int vgposp_gemm_epilogue(void);
 int vgposp_gemm_splitk(int transa, int transb, int64_t m, int64_t n, int64_t k, double alpha,
                        const double* A, int64_t lda, const double* B, int64_t ldb, double beta,
                        double* C, int64_t ldc, int uplo_c, int tri_a, int tri_b, int splits,

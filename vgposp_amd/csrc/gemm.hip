@@ -53,6 +53,9 @@ struct GemmParams {
   // device abort flag (a failed pivot of the enclosing factorization): non-zero -> the launch
   // does nothing (vgposp_greedy_init's early stop without a host synchronisation)
   const int* abort;
+  // epilogue of the fast kernels (vgposp_gemm_set_epilogue): 0 = element-wise reference,
+  // 1 = batched; filled by gemm_plan
+  int epilogue;
 };
 
 // Further destinations of one product (gemm_glds_multi_kernel, the Strassen products): besides
@@ -446,6 +449,76 @@ __device__ __forceinline__ void kloop_pair(dbl4 (&acc)[4][4], u32x8& vo, u32x8& 
 #undef KL_OPERANDS
 }
 
+// One group of the batched epilogue: fragment row i of a wave, that is this lane's 16 elements
+// a[j][r] of the four accumulators acc[i][0..3] (rows lr + 4 r, columns lc + 16 j of the tile),
+// into one destination whose tile origin is org (wave-uniform) with leading dimension ld.
+//   the 16 loads of C (only with beta != 0: C may hold anything otherwise), one wait,
+//   t = alpha a and fma(beta, c, t) exactly as the element-wise epilogue computes them,
+//   the 16 stores
+// INNER (interior tile): no tests; an element is at a uniform base plus one per-lane offset.
+// Otherwise (edge tiles: rows x cols of C lie behind org; diag: diagonal tile of a lower C, only
+// columns <= row are written): the loads go to an address clamped into the part of C that the
+// tile writes, the stores are under the lane's own mask.
+// Offsets are 32-bit: the caller checks 128 ld * 8 < 2^32.
+template <bool INNER>
+__device__ __forceinline__ void epi_group(const dbl4 (&a)[4], double* org, int64_t ld, double alpha,
+                                          double beta, int lr, int lc, int64_t rows, int64_t cols,
+                                          bool diag) {
+  char* at[4][4];
+  unsigned off[4][4];
+  bool ok[4][4];
+  const unsigned ldb = (unsigned)ld * 8u;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (INNER) {
+        at[r][j] = reinterpret_cast<char*>(org + 4 * r * ld + 16 * j);
+        off[r][j] = (unsigned)lr * ldb + (unsigned)lc * 8u;
+        ok[r][j] = true;
+      } else {
+        const int row = lr + 4 * r, col = lc + 16 * j;
+        ok[r][j] = row < rows && col < cols && (!diag || col <= row);
+        const int rc = (int)min((int64_t)row, rows - 1);
+        int cc = (int)min((int64_t)col, cols - 1);
+        if (diag) cc = min(cc, rc);
+        at[r][j] = reinterpret_cast<char*>(org);
+        off[r][j] = (unsigned)rc * ldb + (unsigned)cc * 8u;
+      }
+    }
+  }
+  if (beta != 0.0) {
+    double c[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) c[r][j] = *reinterpret_cast<const double*>(at[r][j] + off[r][j]);
+    if (!INNER) {
+      // all 16 values are wanted here: the compiler otherwise sinks each use into its masked
+      // store's block and waits there again, which drains the store before it
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(c[r][j]));
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) c[r][j] = __builtin_fma(beta, c[r][j], alpha * a[j][r]);
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (INNER || ok[r][j]) *reinterpret_cast<double*>(at[r][j] + off[r][j]) = c[r][j];
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (INNER || ok[r][j]) *reinterpret_cast<double*>(at[r][j] + off[r][j]) = alpha * a[j][r];
+  }
+}
+
 // One workgroup of the fast kernel: workgroup `bid` of the launch's `nwg` for this problem, batch
 // element bz, LDS ring at smem (the kernel's own __shared__ array).
 // MULTI: the epilogue also writes the extra destinations *x (plain products only: no triangular
@@ -679,37 +752,85 @@ __device__ __forceinline__ void gemm_glds_body(const GemmParams& p, int tiles_m,
   const int efr = KL ? et & 15 : fr, efk = KL ? (et & 63) >> 4 : fk;
   const int ewm = KL ? et >> 7 : wm, ewn = KL ? (et >> 6) & 1 : wn;
   const bool lower = p.uplo_c == VGPOSP_LOWER;
+  // 32-bit per-lane offsets in the batched epilogue: 128 rows of a leading dimension below 2^21
+  bool batched = p.epilogue != 0 && (p.nsplit > 1 ? p.n : p.ldc) < (1 << 21);
+  // whole inside C and, for a lower C, strictly below the diagonal
+  const bool inner = m0 + GBM <= p.m && n0 + GBN <= p.n && !(lower && ti == tj);
+  if (MULTI) {
+    // (the Strassen products have no edge tiles: m and n are multiples of 128)
+    if (!inner) batched = false;
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
+    for (int d = 0; d < GEMM_XDST; ++d)
+      if (d < xd->n && xd->ld[d] >= (1 << 21)) batched = false;
+  }
+  if (!batched) {
+    // the element-wise reference: every test and the memory round trip once per element
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int64_t col = n0 + ewn * 64 + j * 16 + efr;
+    for (int i = 0; i < 4; ++i) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int64_t row = m0 + ewm * 64 + i * 16 + efk + 4 * r;
-        if (row < p.m && col < p.n && (!lower || col <= row)) {
-          if (p.nsplit > 1) {
-            p.part[bz * p.sP + (int64_t)zsplit * p.m * p.n + row * p.n + col] = p.alpha * acc[i][j][r];
-            continue;
-          }
-          double* c = p.C + bz * p.sC + row * p.ldc + col;
-          double v = p.alpha * acc[i][j][r];
-          if (p.beta != 0.0) v += p.beta * *c;
-          *c = v;
-          if (MULTI) {
+      for (int j = 0; j < 4; ++j) {
+        const int64_t col = n0 + ewn * 64 + j * 16 + efr;
 #pragma unroll
-            for (int d = 0; d < GEMM_XDST; ++d) {
-              if (d < xd->n) {
-                double* c2 = xd->C[d] + row * xd->ld[d] + col;
-                double v2 = xd->alpha[d] * acc[i][j][r];
-                if (xd->beta[d] != 0.0) v2 += xd->beta[d] * *c2;
-                *c2 = v2;
+        for (int r = 0; r < 4; ++r) {
+          const int64_t row = m0 + ewm * 64 + i * 16 + efk + 4 * r;
+          if (row < p.m && col < p.n && (!lower || col <= row)) {
+            if (p.nsplit > 1) {
+              p.part[bz * p.sP + (int64_t)zsplit * p.m * p.n + row * p.n + col] = p.alpha * acc[i][j][r];
+              continue;
+            }
+            double* c = p.C + bz * p.sC + row * p.ldc + col;
+            double v = p.alpha * acc[i][j][r];
+            if (p.beta != 0.0) v += p.beta * *c;
+            *c = v;
+            if (MULTI) {
+#pragma unroll
+              for (int d = 0; d < GEMM_XDST; ++d) {
+                if (d < xd->n) {
+                  double* c2 = xd->C[d] + row * xd->ld[d] + col;
+                  double v2 = xd->alpha[d] * acc[i][j][r];
+                  if (xd->beta[d] != 0.0) v2 += xd->beta[d] * *c2;
+                  *c2 = v2;
+                }
               }
             }
           }
         }
       }
     }
+    return;
+  }
+
+  // The batched epilogue (epi_group above).  Everything wave-uniform is decided here, once per
+  // tile: partial or C, the destinations and their beta, and whether the tile is interior.
+  const int lr = ewm * 64 + efk, lc = ewn * 64 + efr;
+  const int64_t rows = p.m - m0, cols = p.n - n0;
+  const bool diag = lower && ti == tj;
+  if (p.nsplit > 1) {  // the split's partial: alpha acc, row stride n
+    double* const org = p.part + bz * p.sP + (int64_t)zsplit * p.m * p.n + m0 * p.n + n0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (inner) epi_group<true>(acc[i], org, p.n, p.alpha, 0.0, lr + 16 * i, lc, rows, cols, diag);
+      else epi_group<false>(acc[i], org, p.n, p.alpha, 0.0, lr + 16 * i, lc, rows, cols, diag);
+    }
+    return;
+  }
+  double* const org = p.C + bz * p.sC + m0 * p.ldc + n0;
+  if (inner) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      epi_group<true>(acc[i], org, p.ldc, p.alpha, p.beta, lr + 16 * i, lc, rows, cols, diag);
+      if (MULTI) {
+#pragma unroll
+        for (int d = 0; d < GEMM_XDST; ++d)
+          if (d < xd->n)
+            epi_group<true>(acc[i], xd->C[d] + m0 * xd->ld[d] + n0, xd->ld[d], xd->alpha[d],
+                            xd->beta[d], lr + 16 * i, lc, rows, cols, diag);
+      }
+    }
+  } else if (!MULTI) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      epi_group<false>(acc[i], org, p.ldc, p.alpha, p.beta, lr + 16 * i, lc, rows, cols, diag);
   }
 }
 
@@ -745,7 +866,10 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, GEMM_OCC) void gemm_group_kernel(G
   const int g = blockIdx.y;
   const int bid = blockIdx.x, nwg = gg.nwg[g];
   if (bid >= nwg) return;
-  const GemmParams& p = gg.p[g];
+  // a copy, read once: the sixteen bodies then use scalars of their own and gg itself has few
+  // enough uses to stay in the kernel-argument segment (the compiler otherwise copies all of it
+  // to scratch to index it by g)
+  const GemmParams p = gg.p[g];
   const int tm = gg.tiles_m[g], tn = gg.tiles_n[g];
 #define VG_GROUP_CASE(F)                                                                      \
   case F:                                                                                   \
@@ -765,6 +889,15 @@ __global__ __launch_bounds__(64 * GEMM_WAVES, GEMM_OCC) void gemm_group_kernel(G
 // hand-scheduled interior K-tiles (kloop_pair).  Process-wide, read at launch.  Bit-identical
 // results either way.  Default from the 65k step's A/B (DESIGN.md §4 "Hand-scheduled K loop").
 static std::atomic<int> g_kloop{VGPOSP_KLOOP_DEFAULT};
+
+// Epilogue of the fast kernels (vgposp_gemm_set_epilogue): 0 = the element-wise reference, 1 = the
+// batched one (gemm_glds_body).  Process-wide, read at launch into GemmParams, so one branch per
+// tile and no further kernels.  Bit-identical results either way.  Default from the 65k step's
+// A/B (DESIGN.md §4 "Batched epilogue").
+#ifndef VGPOSP_EPILOGUE_DEFAULT
+#define VGPOSP_EPILOGUE_DEFAULT 1
+#endif
+static std::atomic<int> g_epilogue{VGPOSP_EPILOGUE_DEFAULT};
 
 // The kernel of a launch: every (transa, transb, tri_a, tri_b) combination has its C++-loop
 // kernel (the K-range and mask logic is generic in the four flags); the TA = false ones also
@@ -956,9 +1089,11 @@ struct GemmPlan {
   double flops, bytes;  // a triangular operand halves the useful products
 };
 
-// Also fills p's split-K fields when the fast kernel takes p split (nsplit > 1, partials at part).
+// Also fills p's split-K fields when the fast kernel takes p split (nsplit > 1, partials at part),
+// and its epilogue setting.
 static GemmPlan gemm_plan(GemmParams& p, int batch, int nsplit, double* part) {
   GemmPlan pl{};
+  p.epilogue = g_epilogue.load(std::memory_order_relaxed);
   pl.va = aligned16(p.A, p.lda) && (batch == 1 || p.sA % 2 == 0);
   pl.vb = aligned16(p.B, p.ldb) && (batch == 1 || p.sB % 2 == 0);
   pl.fast = pl.va && pl.vb && (p.m % 2 == 0) && (p.n % 2 == 0) && (p.k % 2 == 0) && p.k > 0;
@@ -1400,6 +1535,16 @@ extern "C" int vgposp_gemm_set_kloop(int kloop) {
 }
 
 extern "C" int vgposp_gemm_kloop(void) { return vgposp::g_kloop.load(); }
+
+extern "C" int vgposp_gemm_set_epilogue(int epilogue) {
+  using namespace vgposp;
+  clear_error();
+  VG_CHECK_ARG(epilogue == 0 || epilogue == 1, 1);
+  g_epilogue.store(epilogue, std::memory_order_relaxed);
+  return 0;
+}
+
+extern "C" int vgposp_gemm_epilogue(void) { return vgposp::g_epilogue.load(); }
 
 // The operand checks vgposp_gemm, vgposp_gemm_splitk and vgposp_gemm_strassen share: the same
 // arguments at the same positions (vgposp_gemm_batched has its strides in between).
