@@ -270,8 +270,15 @@ int vgposp_index_taper(double* C, int64_t n, int64_t ldc, int64_t I0, int64_t I1
  *   invert = 1: lower triangle of A <- L^-1 (recursive triangular inverse after the factor).
  * The strictly upper triangle of A is never read or written (it keeps Sigma for the greedy
  * nominators).  diag_out ([batch][n], or NULL) receives diag(L) (log-det).  info: [batch] int32.
- * ws must hold vgposp_potrf_workspace_bytes(n).
+ * ws must hold vgposp_potrf_workspace_bytes(n), which includes a fixed 64 MiB of split-K
+ * partials for every n > 128 (sized for the large factorizations).  A caller that factors a small
+ * matrix and minds the memory (the chunked predictive variance) may pass
+ * vgposp_potrf_compact_workspace_bytes(n) instead: the partials area is then min(64 MiB, 64 n^2
+ * bytes), which holds every split an order-n factorization takes, so the results are bit-identical;
+ * the two sizes are equal for n <= 128 and n >= 1024.  Any ws_bytes below the full size is laid
+ * out compactly.
  * --------------------------------------------------------------------------------------------- */
+size_t vgposp_potrf_compact_workspace_bytes(int64_t n);
 /* Workspace for factoring a batch of n > 128 matrices in ONE recursion (every launch covers the
  * whole batch): pass at least this many bytes to vgposp_potrf_lower with batch > 1 (a smaller
  * workspace of vgposp_potrf_workspace_bytes(n) factors them one after another). */
@@ -359,6 +366,19 @@ int vgposp_lml_grad(int kind, const double* X, int64_t n, int d, const double* a
                     const double* ls, const double* Cinv, int64_t ldc, int64_t stride_c,
                     const double* alpha, int batch, double* grad, void* ws, size_t ws_bytes,
                     void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Row sums of squares of a row-major strip V (rows x cols, ldv >= cols):
+ *     out[i] = alpha * sum_j V[i][j]^2 + (beta != 0 ? beta * out[i] : 0),   0 <= i < rows
+ * The marginal predictive variance without the P x P covariance: with V = K_*x L^-T one row per
+ * prediction point, alpha = -1 and beta = 1 onto out = k(x*, x*) give the reference's
+ * s2 = np.diag(K_ss) - np.sum(Lk**2, axis=0) (plot_confidence_interval.py:51; the stddev() of
+ * main_GP_fit.py:251 and main_tests.py:404).  out is not read when beta == 0.  rows == 0 returns
+ * 0 without device work; cols == 0 writes beta * out.  No workspace, no host synchronisation,
+ * no atomics: column j always goes to the same lane, so two runs are bit-identical.
+ * --------------------------------------------------------------------------------------------- */
+int vgposp_row_sumsq(const double* V, int64_t rows, int64_t cols, int64_t ldv, double alpha,
+                     double beta, double* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Greedy mutual-information placement (Krause, Singh & Guestrin Alg. 2 as implemented by

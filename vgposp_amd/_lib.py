@@ -109,6 +109,7 @@ SIGNATURES = {
                                   _c_void_p]),
     "vgposp_potrf_batched_workspace_bytes": (_size, [_i64, _i32]),
     "vgposp_potrf_workspace_bytes": (_size, [_i64]),
+    "vgposp_potrf_compact_workspace_bytes": (_size, [_i64]),
     "vgposp_potrf_lower": (_i32, [_c_void_p, _i64, _i64, _i64, _i32, _i32, _c_void_p, _c_void_p,
                                   _c_void_p, _size, _c_void_p]),
     "vgposp_trsm_workspace_bytes": (_size, [_i64, _i64]),
@@ -120,6 +121,7 @@ SIGNATURES = {
     "vgposp_lml_grad_workspace_bytes": (_size, [_i64, _i32]),
     "vgposp_lml_grad": (_i32, [_i32, _c_void_p, _i64, _i32, _c_void_p, _c_void_p, _c_void_p, _i64,
                                _i64, _c_void_p, _i32, _c_void_p, _c_void_p, _size, _c_void_p]),
+    "vgposp_row_sumsq": (_i32, [_c_void_p, _i64, _i64, _i64, _f64, _f64, _c_void_p, _c_void_p]),
     "vgposp_greedy_workspace_bytes": (_size, [_i64, _i32]),
     "vgposp_greedy_init": (_i32, [_c_void_p, _i64, _i64, _i32, _c_void_p, _c_void_p, _size,
                                   _c_void_p]),

@@ -31,10 +31,12 @@ void gemm_strassen_config(int64_t* min_dim, int* levels);
 
 // ---- potrf.hip ------------------------------------------------------------------------------
 int potrf_one(double* A, int64_t n, int64_t lda, int invert, double* diag_out, int* info,
-              void* ws, hipStream_t stream, bool early = false, bool strassen = true);
+              void* ws, hipStream_t stream, bool early = false, bool strassen = true,
+              bool compact = false);  // compact: ws is potrf_ws_bytes_compact(n)
 int potrf_batched(double* A, int64_t n, int64_t lda, int64_t sA, int batch, int invert,
                   double* diag_out, int* info, void* ws, hipStream_t stream, bool use_part);
 size_t potrf_ws_bytes(int64_t n);
+size_t potrf_ws_bytes_compact(int64_t n);
 size_t potrf_ws_bytes_opt(int64_t n, bool use_part);
 int partial_inverse(double* A, int64_t n, int64_t lda, int64_t c0, int64_t c1, double* tmp,
                     void* ws, hipStream_t s);

@@ -8,6 +8,7 @@
 //     dLML/dtheta = 0.5 sum_ij (alpha alpha^T - C^-1)_ij dC_ij/dtheta
 // The gradient pass regenerates dK/dtheta from X on the fly (no dK matrices in HBM) and reads the
 // lower triangle of C^-1 once: it is HBM-bound at 4 n(n+1) bytes per batch entry.
+#include <algorithm>
 #include <cmath>
 
 #include "common.h"
@@ -163,9 +164,172 @@ __global__ __launch_bounds__(1024) void lml_grad_reduce_kernel(int64_t nblk, con
   }
 }
 
+// ---- row sums of squares (the marginal predictive variance) ----------------------------------
+// s2 = diag(K_ss) - sum(Lk^2, axis=0) of plot_confidence_interval.py:51: the second term for a
+// row-major strip V (one prediction point per row).  HBM / Infinity-Cache read-bound.
+//
+// A row belongs to a group of G lanes (G = 64: one wave per row; G = 32 / 16: two / four rows per
+// wave for rows of at most 32 / 16 loads), and column c to lane (c / W) % G of its group (W = 2
+// with 16-byte loads, 1 on the scalar path) whatever the grid, so a result does not depend on the
+// launch geometry: four independent accumulators per lane in a fixed order, then the xor
+// butterfly of wave_sum restricted to the group (steps G/2 ... 1; a group is never narrower than
+// a 16-lane DPP row, below which the row_ror:4 step of common.h would no longer be lane ^ 4).
+typedef double rs_d2v __attribute__((ext_vector_type(2)));
+
+// Non-temporal loads: measured against plain loads (tools/bench_variance.py --alt-lib)
+// they stream a 4 GiB strip 12 % faster and make no difference on a chunk strip that the GEMM
+// has just left in the Infinity Cache.
+#ifndef VG_ROWSUMSQ_NT
+#define VG_ROWSUMSQ_NT 1
+#endif
+
+template <class T>
+__device__ __forceinline__ T rs_load(const T* p) {
+#if VG_ROWSUMSQ_NT
+  return __builtin_nontemporal_load(p);
+#else
+  return *p;
+#endif
+}
+
+template <int G>
+__device__ __forceinline__ double group_sum(double v) {
+  const auto add = [](double a, double b) { return a + b; };
+  if constexpr (G >= 64) v = wave_step<32>(v, add);
+  if constexpr (G >= 32) v = wave_step<16>(v, add);
+  v = wave_step<8>(v, add);
+  v = wave_step<4>(v, add);
+  v = wave_step<2>(v, add);
+  return wave_step<1>(v, add);
+}
+
+// This lane's share of sum_j p[j]^2, j < cols (gl = lane within the group).  VEC: p is 16-byte
+// aligned.  Whole blocks of four loads per lane first (wave-uniform trip count, every load issued
+// before the first use), then at most four predicated loads for the tail.
+template <int G, bool VEC>
+__device__ __forceinline__ double row_part(const double* __restrict__ p, int64_t cols, int gl) {
+  double s[4] = {0.0, 0.0, 0.0, 0.0};
+  if constexpr (VEC) {
+    constexpr int64_t STEP = 2 * G;
+    const int64_t pairs = cols & ~(int64_t)1;
+    int64_t c = 0;
+    for (; c + 4 * STEP <= pairs; c += 4 * STEP) {
+      const rs_d2v* q = reinterpret_cast<const rs_d2v*>(p + c + 2 * gl);
+      rs_d2v a[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) a[u] = rs_load(q + u * G);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) s[u] = fma(a[u].y, a[u].y, fma(a[u].x, a[u].x, s[u]));
+    }
+    rs_d2v a[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int64_t cc = c + 2 * gl + u * STEP;
+      a[u] = rs_d2v{0.0, 0.0};
+      if (cc < pairs) a[u] = rs_load(reinterpret_cast<const rs_d2v*>(p + cc));
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) s[u] = fma(a[u].y, a[u].y, fma(a[u].x, a[u].x, s[u]));
+    if (pairs < cols && gl == 0) {  // the odd last column
+      const double x = p[pairs];
+      s[1] = fma(x, x, s[1]);
+    }
+  } else {
+    int64_t c = 0;
+    for (; c + 4 * G <= cols; c += 4 * G) {
+      double a[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) a[u] = rs_load(p + c + gl + u * G);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) s[u] = fma(a[u], a[u], s[u]);
+    }
+    double a[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int64_t cc = c + gl + u * G;
+      a[u] = 0.0;
+      if (cc < cols) a[u] = rs_load(p + cc);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) s[u] = fma(a[u], a[u], s[u]);
+  }
+  return (s[0] + s[1]) + (s[2] + s[3]);
+}
+
+// out[i] = alpha sum_j V[i][j]^2 (+ beta out[i]).  Grid-stride over sets of RU * (64 / G) rows per
+// wave: the RU row groups of a set are loaded together, so a wave with short rows still has
+// several loads in flight.  A row index past the end is clamped for the loads and not stored, so
+// every lane stays active through the butterflies.
+template <int G, bool VEC, int RU>
+__global__ __launch_bounds__(256) void row_sumsq_kernel(const double* __restrict__ V, int64_t rows,
+                                                        int64_t cols, int64_t ldv, double alpha,
+                                                        double beta, double* __restrict__ out) {
+  constexpr int RPW = 64 / G;  // rows per wave and group
+  const int lane = threadIdx.x & 63;
+  const int gl = lane % G, sub = lane / G;
+  const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t nwave = (int64_t)gridDim.x * 4;
+  const int64_t nset = (rows + RU * RPW - 1) / (RU * RPW);
+  for (int64_t set = wave; set < nset; set += nwave) {
+    double s[RU];
+#pragma unroll
+    for (int u = 0; u < RU; ++u) {
+      const int64_t i = min((set * RU + u) * RPW + sub, rows - 1);
+      s[u] = row_part<G, VEC>(V + i * ldv, cols, gl);
+    }
+#pragma unroll
+    for (int u = 0; u < RU; ++u) {
+      const double t = group_sum<G>(s[u]);
+      const int64_t i = (set * RU + u) * RPW + sub;
+      if (gl == 0 && i < rows) out[i] = beta != 0.0 ? fma(alpha, t, beta * out[i]) : alpha * t;
+    }
+  }
+}
+
+template <int G, bool VEC, int RU>
+static void launch_row_sumsq(hipStream_t s, const double* V, int64_t rows, int64_t cols,
+                             int64_t ldv, double alpha, double beta, double* out) {
+  constexpr int ROWS_PER_WG = 4 * RU * (64 / G);
+  // capped: 8 workgroups of 4 waves per CU keep every SIMD's wave slots full on 256 CUs
+  const int64_t nwg = std::min<int64_t>(ceil_div(rows, ROWS_PER_WG), 2048);
+  hipLaunchKernelGGL((row_sumsq_kernel<G, VEC, RU>), dim3((unsigned)nwg), dim3(256), 0, s, V,
+                     rows, cols, ldv, alpha, beta, out);
+}
+
 }  // namespace vgposp
 
 using namespace vgposp;
+
+extern "C" int vgposp_row_sumsq(const double* V, int64_t rows, int64_t cols, int64_t ldv,
+                                double alpha, double beta, double* out, void* stream) {
+  clear_error();
+  VG_CHECK_ARG(rows >= 0, 2);
+  VG_CHECK_ARG(cols >= 0, 3);
+  VG_CHECK_ARG(ldv >= cols, 4);
+  if (rows == 0) return 0;
+  VG_CHECK_ARG(V != nullptr || cols == 0, 1);
+  VG_CHECK_ARG(out != nullptr, 7);
+  hipStream_t s = as_stream(stream);
+  // 16-byte loads need every row start aligned: an aligned base and an even row stride
+  const bool vec = (reinterpret_cast<uintptr_t>(V) % 16 == 0) && (ldv % 2 == 0);
+  ProfScope ps("row_sumsq", s, 2.0 * (double)rows * (double)cols,
+               8.0 * ((double)rows * (double)cols + (double)rows));
+  // the group is as wide as a row has loads (a wave on a 64-column row of 16-byte loads would
+  // leave half its lanes without one)
+  const int64_t loads = vec ? (cols + 1) / 2 : cols;
+  if (loads <= 16) {
+    if (vec) launch_row_sumsq<16, true, 4>(s, V, rows, cols, ldv, alpha, beta, out);
+    else launch_row_sumsq<16, false, 4>(s, V, rows, cols, ldv, alpha, beta, out);
+  } else if (loads <= 32) {
+    if (vec) launch_row_sumsq<32, true, 4>(s, V, rows, cols, ldv, alpha, beta, out);
+    else launch_row_sumsq<32, false, 4>(s, V, rows, cols, ldv, alpha, beta, out);
+  } else {
+    if (vec) launch_row_sumsq<64, true, 2>(s, V, rows, cols, ldv, alpha, beta, out);
+    else launch_row_sumsq<64, false, 2>(s, V, rows, cols, ldv, alpha, beta, out);
+  }
+  VG_LAUNCH_CHECK();
+  return 0;
+}
 
 extern "C" size_t vgposp_lml_workspace_bytes(int64_t n, int batch) {
   return (size_t)n * batch * sizeof(double);

@@ -687,9 +687,17 @@ static int64_t potrf_strassen_elems(int64_t n, int64_t min_dim, int levels) {
 
 // One matrix: 64 MiB of partials.  Without Strassen scratch this is what the sharded entry points
 // and partial_inverse address (potrf_one's scratch, if any, lies behind it).
-static PotrfLayout potrf_layout_one(int64_t n, int64_t strassen_elems = 0) {
-  return potrf_layout(n, PART_ELEMS, strassen_elems);
+static PotrfLayout potrf_layout_one(int64_t n, int64_t strassen_elems = 0,
+                                    int64_t part_elems = PART_ELEMS) {
+  return potrf_layout(n, part_elems, strassen_elems);
 }
+
+// The partials an order-n factorization can use.  Its products have both output dimensions <= n
+// and K <= n; below n = 1024 that is K < 4096, where gemm_auto_splits gives at most 8 splits (a
+// GEMV shape with a transposed A at most K / 32 < 32 splits of m < 1024 elements), so 8 n^2
+// doubles hold every product's partials and pgemm never has to lower a split count: a compact
+// workspace factors bit-identically to the full one.  From n = 1024 on the two are the same size.
+static int64_t part_elems_compact(int64_t n) { return std::min<int64_t>(PART_ELEMS, 8 * n * n); }
 
 // Each matrix of a batch factored by one recursion: 16 MiB of partials (use_part) or none (large
 // batches fill the GPU through the batch dimension; 16 MiB of partials per matrix would not
@@ -703,6 +711,14 @@ size_t potrf_ws_bytes(int64_t n) {
   int levels;
   gemm_strassen_config(&min_dim, &levels);
   return potrf_layout_one(n, potrf_strassen_elems(n, min_dim, levels)).bytes();
+}
+
+size_t potrf_ws_bytes_compact(int64_t n) {
+  int64_t min_dim;
+  int levels;
+  gemm_strassen_config(&min_dim, &levels);
+  return potrf_layout_one(n, potrf_strassen_elems(n, min_dim, levels), part_elems_compact(n))
+      .bytes();
 }
 
 size_t potrf_ws_bytes_opt(int64_t n, bool use_part) {
@@ -763,14 +779,15 @@ int potrf_batched(double* A, int64_t n, int64_t lda, int64_t sA, int batch, int 
 }
 
 int potrf_one(double* A, int64_t n, int64_t lda, int invert, double* diag_out, int* info,
-              void* ws, hipStream_t stream, bool early, bool strassen) {
+              void* ws, hipStream_t stream, bool early, bool strassen, bool compact) {
   if (int rc = ensure_leaf_attr()) return rc;
   const bool blocks = n > NBI;
   int64_t min_dim = 0;
   int levels = 0;  // the setting is read once: scratch size, threshold and levels belong together
   if (strassen) gemm_strassen_config(&min_dim, &levels);
-  Fact f = make_fact(potrf_layout_one(n, potrf_strassen_elems(n, min_dim, levels)), lda, ws,
-                     diag_out, info, stream);
+  Fact f = make_fact(potrf_layout_one(n, potrf_strassen_elems(n, min_dim, levels),
+                                      compact ? part_elems_compact(n) : PART_ELEMS),
+                     lda, ws, diag_out, info, stream);
   f.str_min = min_dim;
   f.str_levels = levels;
   f.early = early;
@@ -998,6 +1015,10 @@ extern "C" size_t vgposp_potrf_workspace_bytes(int64_t n) {
   return n > 0 ? vgposp::potrf_ws_bytes(n) : 0;
 }
 
+extern "C" size_t vgposp_potrf_compact_workspace_bytes(int64_t n) {
+  return n > 0 ? vgposp::potrf_ws_bytes_compact(n) : 0;
+}
+
 extern "C" size_t vgposp_potrf_batched_workspace_bytes(int64_t n, int batch) {
   // one recursion over the batch at the per-matrix stride of potrf_batched (16 MiB of split-K
   // partials each, never Strassen scratch); never less than one single-matrix workspace
@@ -1021,14 +1042,17 @@ extern "C" int vgposp_potrf_lower(double* A, int64_t n, int64_t lda, int64_t str
   hipStream_t s = as_stream(stream);
   VG_HIP(vg_memset(info, 0, sizeof(int) * batch, s));
   if (n == 0) return 0;
-  VG_CHECK_WS(ws_bytes, potrf_ws_bytes(n));
+  // a workspace below the full size is laid out compactly (the same results, see
+  // part_elems_compact)
+  const bool compact = ws_bytes < potrf_ws_bytes(n);
+  VG_CHECK_WS(ws_bytes, potrf_ws_bytes_compact(n));
   // one recursion over the batch where the workspace holds it; n <= NB is one launch, one
   // workgroup per matrix (e.g. the calc_H likelihood surface), and needs none
   if (batch > 1 && (n <= NB || ws_bytes >= vgposp_potrf_batched_workspace_bytes(n, (int)batch)))
     return potrf_batched(A, n, lda, stride, batch, invert, diag_out, info, ws, s, true);
   for (int b = 0; b < batch; ++b) {
     int rc = potrf_one(A + b * stride, n, lda, invert, diag_out ? diag_out + (int64_t)b * n : nullptr,
-                       info + b, ws, s, false, true);
+                       info + b, ws, s, false, true, compact);
     if (rc) return rc;
   }
   return 0;

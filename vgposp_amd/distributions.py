@@ -27,6 +27,32 @@ from .variables import Placeholder, Softplus, Variable, fed, resolve
 
 LOG_2PI = math.log(2.0 * math.pi)
 
+# Budget of the per-chunk strips (K_*x and V = K_*x L^-T, plus U for the VGP; 8 * chunk * n bytes
+# each) of the chunked marginal variance.  Swept over 32 / 64 / 128 / 256 MiB at P = 128^3
+# (tools/bench_variance.py, profiles/variance_map.json): the largest was the fastest on both the
+# GPRM (n = 4,096) and the VGP (M = 512), because the triangular-operand GEMM of a chunk balances
+# its tiles better over more rows, while the strips' cache residency made no measurable
+# difference.  256 MiB, the size of the Infinity Cache, is the cap: it must not grow past it.
+PREDICT_CHUNK_BYTES = 256 << 20
+
+
+def _predict_chunk(P, n, strips, chunk_points=None):
+    """Rows per chunk: ``chunk_points`` as given, else the largest multiple of 256 (at least 256)
+    whose ``strips`` [chunk, n] float64 strips fit PREDICT_CHUNK_BYTES; never more than P."""
+    if chunk_points is not None:
+        c = int(chunk_points)
+        if c < 1:
+            raise ValueError(f"chunk_points must be >= 1, got {chunk_points}")
+    else:
+        c = max(256, PREDICT_CHUNK_BYTES // (8 * max(int(n), 1) * strips) // 256 * 256)
+    return max(1, min(c, int(P)))
+
+
+def _device_pts(x):
+    """Index points as a [P, d] float64 device tensor."""
+    X = linalg.as_device(_pts(x))
+    return X[:, None] if X.dim() == 1 else X
+
 
 def _as_obs(value, n):
     y = linalg.as_device(value).reshape(-1)
@@ -98,11 +124,11 @@ class GaussianProcess:
         return linalg.as_device(self.mean_fn(X)).reshape(-1)
 
     # -- factorization ------------------------------------------------------------------------
-    def _factor_inverse(self, X):
+    def _factor_inverse(self, X, compact_ws=False):
         """C = K + (noise + jitter) I, lower(C) <- L^-1 in place; returns (Minv[B,n,n], diag(L))."""
         shift = self._noise() + self.jitter
         C = self.kernel.matrix(X, X, diag_shift=shift, lower=True, keep_batch=True)
-        C, ldiag, _ = linalg.cholesky_(C, invert=True, check=True)
+        C, ldiag, _ = linalg.cholesky_(C, invert=True, check=True, compact_ws=compact_ws)
         return C, ldiag
 
     def _factor(self, X, extra_shift=0.0):
@@ -145,11 +171,19 @@ class GaussianProcess:
         C = self.kernel.matrix(X, X, diag_shift=self._noise(), keep_batch=True)
         return C if self.batch_shape != () else C[0]
 
-    def variance(self, index_points=None):
-        return torch.diagonal(self.covariance(index_points), dim1=-2, dim2=-1)
+    def _prior_variance(self, P, noise):
+        """k(x, x) + noise = amp^2 + noise as [B, P] (every kernel here is stationary)."""
+        amp, _ = self.kernel.params()
+        return (amp * amp + noise).reshape(-1, 1).expand(self._B(), P).contiguous()
 
-    def stddev(self, index_points=None):
-        return torch.sqrt(self.variance(index_points))
+    def variance(self, index_points=None, chunk_points=None):
+        """Marginal variance amp^2 + noise, [B, P] or [P]; nothing P x P is formed."""
+        X = self.index_points if index_points is None else index_points
+        v = self._prior_variance(int(_pts(X).shape[0]), self._noise())
+        return v if self.batch_shape != () else v[0]
+
+    def stddev(self, index_points=None, chunk_points=None):
+        return torch.sqrt(self.variance(index_points, chunk_points))
 
     def sample(self, sample_shape=(), seed=None, index_points=None):
         X = self.index_points if index_points is None else index_points
@@ -229,6 +263,52 @@ class GaussianProcessRegressionModel(GaussianProcess):
         _, c = self._posterior()
         return c if self.batch_shape != () else c[0]
 
+    def _marginals(self, index_points, chunk_points, want_mean):
+        """(mean or None, variance) as [B, P] in one pass over chunks of prediction points:
+        var = amp^2 + pred_noise - rowsumsq(K_*x L^-T), the reference's
+        s2 = diag(K_ss) - sum(Lk^2, axis=0) (plot_confidence_interval.py:51), in O(chunk * n)
+        memory.  The factorization is done once; the two strips are reused by every chunk."""
+        X = self.observation_index_points
+        Xo = _device_pts(X)
+        Xs = _device_pts(self.index_points if index_points is None else index_points)
+        n, P, B = int(Xo.shape[0]), int(Xs.shape[0]), self._B()
+        # (the compact workspace: a small factorization must not cost more memory than the chunks)
+        Minv, ldiag = self._factor_inverse(X, compact_ws=True)
+        amp, ls = self.kernel.params()
+        var = self._prior_variance(P, resolve(self.predictive_noise_variance, B))
+        mean = alpha = None
+        if want_mean:
+            y = _as_obs(self.observations, n) - self._mean(X)
+            _, alpha = linalg.lml_from_inverse(Minv, ldiag, y, want_alpha=True)
+            mean = torch.empty((B, P), dtype=torch.float64, device=Xs.device)
+        chunk = _predict_chunk(P, n, 2, chunk_points)
+        Kbuf = torch.empty((chunk, n), dtype=torch.float64, device=Xs.device)
+        Vbuf = torch.empty((chunk, n), dtype=torch.float64, device=Xs.device)
+        for b in range(B):
+            for s in range(0, P, chunk):
+                e = min(s + chunk, P)
+                Ksx, V = Kbuf[:e - s], Vbuf[:e - s]
+                linalg.kernel_matrix(self.kernel.kind, Xs[s:e], Xo, amp[b:b + 1], ls[b:b + 1],
+                                     out=Ksx.unsqueeze(0))
+                if want_mean:
+                    linalg.gemm(Ksx, alpha[b].reshape(n, 1), mean[b, s:e].reshape(e - s, 1))
+                linalg.gemm(Ksx, Minv[b], V, transb=True, tri_b=True)  # V = K_*x L^-T
+                linalg.row_sumsq(V, out=var[b, s:e], alpha=-1.0, beta=1.0)
+        if want_mean:
+            mean = mean + self._mean(self.index_points if index_points is None else index_points)
+        return mean, var
+
+    def variance(self, index_points=None, chunk_points=None):
+        """Marginal predictive variance [B, P] or [P] without the P x P covariance.  Small
+        negative values from cancellation are not clamped (as in TFP)."""
+        _, v = self._marginals(index_points, chunk_points, want_mean=False)
+        return v if self.batch_shape != () else v[0]
+
+    def mean_and_variance(self, index_points=None, chunk_points=None):
+        """(mean, variance) from one pass over the chunks (each K_*x strip feeds both)."""
+        m, v = self._marginals(index_points, chunk_points, want_mean=True)
+        return (m, v) if self.batch_shape != () else (m[0], v[0])
+
     def sample(self, sample_shape=(), seed=None, index_points=None):
         mean, cov = self._posterior()
         B, M = cov.shape[0], cov.shape[-1]
@@ -292,11 +372,11 @@ class VariationalGaussianProcess(GaussianProcess):
         scale = scale.reshape(-1, M, M).expand(B, M, M).contiguous()
         return loc, scale
 
-    def _kzz_factor(self):
+    def _kzz_factor(self, compact_ws=False):
         """Lz^-1 with Lz = chol(Kzz + jitter I) (lower triangles), and the [B, M, M] inverse."""
         Z = self._Z()
         Kzz = self.kernel.matrix(Z, Z, diag_shift=self.jitter, lower=True, keep_batch=True)
-        Lzinv, ldiag, _ = linalg.cholesky_(Kzz, invert=True, check=True)
+        Lzinv, ldiag, _ = linalg.cholesky_(Kzz, invert=True, check=True, compact_ws=compact_ws)
         return Lzinv, ldiag
 
     @staticmethod
@@ -448,6 +528,57 @@ class VariationalGaussianProcess(GaussianProcess):
     def covariance(self, index_points=None):
         _, c = self._predictive()
         return c if self.batch_shape != () else c[0]
+
+    def _marginals(self, index_points, chunk_points, want_mean):
+        """(mean or None, variance) as [B, P], chunked: with V = K_*z Lz^-T and U = V (Lz^-1 A),
+        var = amp^2 + pred_noise - rowsumsq(V) + rowsumsq(U), the diagonal of _predictive's
+        K_** - V V^T + U^T U because A^T Kzz^-1 K_z* = (V Lz^-1 A)^T."""
+        Xs = _device_pts(self.index_points if index_points is None else index_points)
+        Z = self._Z()
+        Zd = _device_pts(Z)
+        B, P = self._B(), int(Xs.shape[0])
+        loc, scale = self._loc_scale()
+        M = scale.shape[-1]
+        Lzinv, _ = self._kzz_factor(compact_ws=True)
+        amp, ls = self.kernel.params()
+        var = self._prior_variance(P, resolve(self.predictive_noise_variance, B))
+        mean = None
+        if want_mean:
+            mz = self._mean(Z)
+            mean = torch.empty((B, P), dtype=torch.float64, device=Xs.device)
+        chunk = _predict_chunk(P, M, 3, chunk_points)
+        Kbuf, Vbuf, Ubuf = (torch.empty((chunk, M), dtype=torch.float64, device=Xs.device)
+                            for _ in range(3))
+        for b in range(B):
+            G = linalg.gemm(Lzinv[b], scale[b], tri_a=True)               # Lz^-1 A
+            if want_mean:
+                w = linalg.gemm(Lzinv[b], (loc[b] - mz).reshape(M, 1), tri_a=True)
+                kinv_loc = linalg.gemm(Lzinv[b], w, transa=True, tri_a=True)
+            for s in range(0, P, chunk):
+                e = min(s + chunk, P)
+                Ksz, V, U = Kbuf[:e - s], Vbuf[:e - s], Ubuf[:e - s]
+                linalg.kernel_matrix(self.kernel.kind, Xs[s:e], Zd, amp[b:b + 1], ls[b:b + 1],
+                                     out=Ksz.unsqueeze(0))
+                if want_mean:
+                    linalg.gemm(Ksz, kinv_loc, mean[b, s:e].reshape(e - s, 1))
+                linalg.gemm(Ksz, Lzinv[b], V, transb=True, tri_b=True)   # K_*z Lz^-T
+                linalg.gemm(V, G, U)
+                linalg.row_sumsq(V, out=var[b, s:e], alpha=-1.0, beta=1.0)
+                linalg.row_sumsq(U, out=var[b, s:e], alpha=1.0, beta=1.0)
+        if want_mean:
+            mean = mean + self._mean(self.index_points if index_points is None else index_points)
+        return mean, var
+
+    def variance(self, index_points=None, chunk_points=None):
+        """Marginal predictive variance [B, P] or [P] without the P x P covariance (not
+        clamped)."""
+        _, v = self._marginals(index_points, chunk_points, want_mean=False)
+        return v if self.batch_shape != () else v[0]
+
+    def mean_and_variance(self, index_points=None, chunk_points=None):
+        """(mean, variance) from one pass over the chunks (each K_*z strip feeds both)."""
+        m, v = self._marginals(index_points, chunk_points, want_mean=True)
+        return (m, v) if self.batch_shape != () else (m[0], v[0])
 
     def sample(self, sample_shape=(), seed=None, index_points=None):
         mean, cov = self._predictive()

@@ -229,11 +229,13 @@ def check_info(info):
         raise CholeskyError(int(info[b]), b)
 
 
-def cholesky_(A, invert=False, check=True, ldiag=None):
+def cholesky_(A, invert=False, check=True, ldiag=None, compact_ws=False):
     """In-place blocked Cholesky of the lower triangle of A ([n, n] or [B, n, n]).
 
     invert=False: lower(A) <- L;  invert=True: lower(A) <- L^-1.  The strictly upper triangle is
-    untouched.  Returns (A, ldiag[B, n] = diag(L), info[B])."""
+    untouched.  Returns (A, ldiag[B, n] = diag(L), info[B]).  ``compact_ws``: a single matrix is
+    factored in vgposp_potrf_compact_workspace_bytes(n) (64 n^2 bytes of split-K partials
+    instead of a fixed 64 MiB below n = 1024; the same bits)."""
     A3, _ = _batched(A)
     Bn, n = A3.shape[0], A3.shape[-1]
     # rows contiguous; a padded row stride (lda > n) is allowed
@@ -244,7 +246,8 @@ def cholesky_(A, invert=False, check=True, ldiag=None):
     info = torch.empty(Bn, dtype=torch.int32, device=A3.device)
     # a batch of n > 128 matrices runs as ONE recursion (every launch covers the batch)
     ws = workspace(query("vgposp_potrf_batched_workspace_bytes", n, Bn) if Bn > 1 and n > 128
-                   else query("vgposp_potrf_workspace_bytes", n))
+                   else query("vgposp_potrf_compact_workspace_bytes" if compact_ws
+                              else "vgposp_potrf_workspace_bytes", n))
     call("vgposp_potrf_lower", _p(A3), n, A3.stride(1), A3.stride(0), Bn, int(invert), _p(ldiag),
          _p(info), _p(ws), ws.numel(), _stream())
     if check:
@@ -321,6 +324,32 @@ def lml_from_inverse(Minv, ldiag, y, want_alpha=False):
     call("vgposp_lml", _p(M3), n, M3.stride(1), M3.stride(0), Bn, _p(ldiag), _p(y), _p(alpha),
          _p(out), _p(ws), ws.numel(), _stream())
     return (out, alpha) if want_alpha else out
+
+
+def row_sumsq(V, out=None, alpha=1.0, beta=0.0):
+    """out[i] = alpha sum_j V[i, j]^2 + beta out[i] for a [rows, cols] device matrix with
+    contiguous rows (a padded row stride is allowed); ``out`` [rows] is not read when beta == 0
+    (vgposp_row_sumsq: no workspace, deterministic)."""
+    if not isinstance(V, torch.Tensor) or V.device.type != "cuda" or V.dtype != F64:
+        V = as_device(V)
+    if V.dim() != 2:
+        raise ValueError(f"row_sumsq: V must be 2-D, got shape {tuple(V.shape)}")
+    rows, cols = V.shape
+    if cols > 1 and V.stride(1) != 1:
+        V = V.contiguous()
+    ldv = cols if rows <= 1 else V.stride(0)
+    if ldv < cols:
+        V = V.contiguous()
+        ldv = cols
+    if out is None:
+        if beta != 0.0:
+            raise ValueError("row_sumsq: beta != 0 needs an out to accumulate onto")
+        out = torch.empty(rows, dtype=F64, device=V.device)
+    if (out.dim() != 1 or out.numel() != rows or out.dtype != F64 or out.device != V.device
+            or (rows > 1 and out.stride(0) != 1)):
+        raise ValueError("row_sumsq: out must be a contiguous float64 [rows] tensor on V's device")
+    call("vgposp_row_sumsq", _p(V), rows, cols, ldv, float(alpha), float(beta), _p(out), _stream())
+    return out
 
 
 def inverse_from_factor_inverse(Minv):
