@@ -430,6 +430,38 @@ int vgposp_greedy_cache(void* ws, int64_t n, int kmax, double** cache);
  * padding candidate with this. */
 int vgposp_greedy_exclude(void* ws, int64_t n, int kmax, int64_t idx, void* stream);
 
+/* A candidate set and pre-installed sensors: Krause's split of V into S (where a sensor may go) and
+ * U (whose uncertainty counts, but where none can be put), and a greedy loop that starts from
+ * sensors A0 already in place.  The reference assumes both away ("assume U is empty, assume
+ * V = S", A = [], placement_algorithm2.py:128-160); here A starts as A0 (in the given order),
+ * A_bar as V \ A0, and the arg-max loops (argmax_cache_linear :53-67, argmax_ :105-125) run over
+ * candidates \ A.  nominator (:371-388) and denominator (:408-413) are unchanged, so A_bar keeps
+ * every non-candidate location.
+ *   vgposp_greedy_mask   after init: selmask[i] |= !allowed[i] for a device byte mask allowed[n]
+ *                        (the set form of vgposp_greedy_exclude).
+ *   vgposp_greedy_force  a selection round whose pick is given: y = forced[j] (device array, so
+ *                        nothing synchronises the host) instead of the arg-max; writes
+ *                        selected[round], the selection mask and the pivot data exactly as
+ *                        vgposp_greedy_select does after choosing (A.append(y), :211) and leaves
+ *                        the cache, the fresh flags and evals alone.  It counts towards kmax.
+ *   vgposp_greedy_condition  right after init: rounds 0 .. m-1 as forced rounds on
+ *                        placed[0 .. m), with the workspace sized for kmax >= m + k rounds; the k
+ *                        free rounds then continue with vgposp_greedy_step(round = m, ...), which
+ *                        conditions on placed[m-1] itself.  batch = 1 runs one vgposp_greedy_update
+ *                        per sensor (one pass over L^-1 each); batch = 4 or 8 forms the columns
+ *                        q_a = M^T (M e_a) of that many sensors in ONE pass over L^-1 (they do not
+ *                        depend on each other; only the O(n t) Gram-Schmidt of the update is
+ *                        sequential).  scratch: vgposp_greedy_condition_workspace_bytes(n, batch)
+ *                        bytes (0 for an unsupported batch), separate from the greedy workspace.
+ * Index range and duplicates in placed are the caller's to check before upload. */
+int vgposp_greedy_mask(void* ws, int64_t n, int kmax, const unsigned char* allowed, void* stream);
+int vgposp_greedy_force(int64_t n, int kmax, int round, const int64_t* forced, int64_t j,
+                        int64_t* selected, void* ws, size_t ws_bytes, void* stream);
+size_t vgposp_greedy_condition_workspace_bytes(int64_t n, int batch);
+int vgposp_greedy_condition(const double* Sigma, int64_t n, int64_t lda, int kmax, int m, int k,
+                            int batch, const int64_t* placed, int64_t* selected, void* ws,
+                            size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Placement algorithm 3, the local-kernel greedy (snippets_a3.sparse_placement_algorithm_3,
  * snippets_a3.py:43-330; with vgposp_greedy_init_ex(..., 1e-6, 1e-7, 1e8, ...) as its tf_nominator
  * constants).  Per round, after vgposp_greedy_update(round): round 0 scores every candidate into

@@ -129,6 +129,12 @@ SIGNATURES = {
                                      _c_void_p, _size, _c_void_p]),
     "vgposp_greedy_cache": (_i32, [_c_void_p, _i64, _i32, ctypes.POINTER(_c_void_p)]),
     "vgposp_greedy_exclude": (_i32, [_c_void_p, _i64, _i32, _i64, _c_void_p]),
+    "vgposp_greedy_mask": (_i32, [_c_void_p, _i64, _i32, _c_void_p, _c_void_p]),
+    "vgposp_greedy_force": (_i32, [_i64, _i32, _i32, _c_void_p, _i64, _c_void_p, _c_void_p, _size,
+                                   _c_void_p]),
+    "vgposp_greedy_condition_workspace_bytes": (_size, [_i64, _i32]),
+    "vgposp_greedy_condition": (_i32, [_c_void_p, _i64, _i64, _i32, _i32, _i32, _i32, _c_void_p,
+                                       _c_void_p, _c_void_p, _size, _c_void_p, _size, _c_void_p]),
     "vgposp_greedy_select_window": (_i32, [_i64, _i32, _i32, _i64, _i64, _i64, _i32, _i64, _i64,
                                            _c_void_p, _c_void_p, _c_void_p, _c_void_p, _size,
                                            _c_void_p]),

@@ -794,3 +794,260 @@ extern "C" int vgposp_greedy_exclude(void* ws, int64_t n, int kmax, int64_t idx,
   VG_LAUNCH_CHECK();
   return 0;
 }
+
+// ---- candidate set S != V and pre-installed sensors A0 (Krause's S / U split, which
+// placement_algorithm2.py:128-160 assumes away: "assume U is empty, assume V = S", A = []) ----
+namespace vgposp {
+
+// selmask[i] |= !allowed[i]: a masked location is never an arg-max, but greedy_update_kernel keeps
+// updating its nom / prec, so it stays in A_bar (denominator, :408-413) like every unselected one.
+__global__ void greedy_mask_kernel(int64_t n, const unsigned char* allowed,
+                                   unsigned char* selmask) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n && !allowed[i]) selmask[i] = 1;
+}
+
+// Indices come validated from the host (range, duplicates); the clamp only keeps a corrupt value
+// from addressing outside the matrix.
+__device__ __forceinline__ int64_t forced_index(const int64_t* forced, int64_t j, int64_t n) {
+  return min(max(forced[j], (int64_t)0), n - 1);
+}
+
+// The tail of greedy_select_kernel for a pick given by the caller: y = forced[j] instead of the
+// arg-max (A.append(y), :211).  Cache, fresh flags and evaluation counts are not touched.
+__global__ __launch_bounds__(256) void greedy_force_kernel(int64_t n, int round,
+                                                           const int64_t* forced, int64_t j,
+                                                           int64_t* selected, GreedyWS w) {
+  const int64_t y = forced_index(forced, j, n);
+  if (threadIdx.x == 0) {
+    selected[round] = y;
+    w.selmask[y] = 1;
+    w.piv[0] = w.nom[y];
+    w.piv[1] = w.prec[y];
+  }
+  for (int t = threadIdx.x; t < round; t += blockDim.x) {
+    w.piv[2 + t] = w.W[(int64_t)t * n + y];
+    w.piv[2 + round + t] = w.V[(int64_t)t * n + y];
+  }
+}
+
+// X[r][j] = (M e_{a_j})_r for r >= a_j, else 0, a_j = forced[j0 + j], j < nt; columns nt..T-1 are
+// zero.  Row-interleaved so the mat-vec reads the T values of a row with one uniform load.
+template <int T>
+__global__ void greedy_extract_batch_kernel(const double* M, int64_t n, int64_t lda,
+                                            const int64_t* forced, int64_t j0, int nt, double* X) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n * T) return;
+  const int64_t r = e / T;
+  const int j = (int)(e % T);
+  double x = 0.0;
+  if (j < nt) {
+    const int64_t a = forced_index(forced, j0 + j, n);
+    if (r >= a) x = M[r * lda + a];
+  }
+  X[e] = x;
+}
+
+// greedy_trmv_kernel<false> for T right-hand sides in one pass over M = L^-1:
+//   part[j][rc][c] = sum_{r in chunk rc, r >= max(c, a_j)} M[r][c] * X[r][j]
+// Same tiling and the same 16-byte non-temporal column-pair loads; rows start at
+// max(c, min_j a_j) (X[.][j] is zero above a_j).  The row index is uniform over the workgroup, so
+// the T values of X for a row are wave-uniform operands; the diagonal tile (RC == TRMV_COLS, all
+// columns) masks the entries above the diagonal, which hold Sigma.
+static_assert(RC == TRMV_COLS, "the batched mat-vec takes tile (b, b) as the diagonal tile");
+
+template <int T, bool VEC>
+__global__ __launch_bounds__(CT) void greedy_trmv_batch_kernel(
+    const double* __restrict__ M, int64_t n, int64_t lda, const int64_t* __restrict__ forced,
+    int64_t j0, int nt, const double* __restrict__ X, double* __restrict__ part) {
+  typedef double d2v __attribute__((ext_vector_type(2)));
+  const int64_t cb = (int64_t)blockIdx.x * TRMV_COLS;
+  const int64_t r0 = (int64_t)blockIdx.y * RC;
+  const int64_t r1 = min(r0 + RC, n);
+  if (cb >= r1) return;  // tile strictly above the diagonal: never read by the reducer
+  int64_t amin = n;
+  for (int j = 0; j < nt; ++j) amin = min(amin, forced_index(forced, j0 + j, n));
+  if (amin >= r1) return;  // rows above every a_j: the reducer starts at chunk a_j / RC
+  const bool diag = blockIdx.x == blockIdx.y;
+  const int64_t c = cb + 2 * threadIdx.x;
+  if (c >= n) return;
+  const bool two = c + 1 < n;
+  double acc0[T], acc1[T];  // column c, column c + 1
+#pragma unroll
+  for (int j = 0; j < T; ++j) acc0[j] = acc1[j] = 0.0;
+  auto load = [&](const double* p) -> d2v {
+    if (VEC && two) return __builtin_nontemporal_load(reinterpret_cast<const d2v*>(p));
+    d2v m;
+    m.x = __builtin_nontemporal_load(p);
+    m.y = two ? __builtin_nontemporal_load(p + 1) : 0.0;
+    return m;
+  };
+  auto row = [&](d2v m, int64_t r) {
+    if (diag) {  // lower triangle only: (r, c) needs r >= c, (r, c + 1) needs r > c
+      m.x = r >= c ? m.x : 0.0;
+      m.y = r > c ? m.y : 0.0;
+    }
+    const double* x = X + r * T;
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+      acc0[j] = fma(m.x, x[j], acc0[j]);
+      acc1[j] = fma(m.y, x[j], acc1[j]);
+    }
+  };
+  int64_t r = max(max(r0, cb), amin);
+  const double* p = M + r * lda + c;
+  for (; r + 3 < r1; r += 4, p += 4 * lda) {
+    const d2v m0 = load(p), m1 = load(p + lda), m2 = load(p + 2 * lda), m3 = load(p + 3 * lda);
+    row(m0, r);
+    row(m1, r + 1);
+    row(m2, r + 2);
+    row(m3, r + 3);
+  }
+  for (; r < r1; ++r, p += lda) row(load(p), r);
+  const int64_t nrc = (n + RC - 1) / RC;
+#pragma unroll
+  for (int j = 0; j < T; ++j) {
+    if (j < nt) {
+      double* o = part + ((int64_t)j * nrc + blockIdx.y) * n + c;
+      o[0] = acc0[j];
+      if (two) o[1] = acc1[j];
+    }
+  }
+}
+
+struct CondScratch {
+  double *X, *part;
+  size_t bytes;
+};
+
+static CondScratch cond_layout(void* base, int64_t n, int batch) {
+  CondScratch c{};
+  char* p = static_cast<char*>(base);
+  const size_t xb = align_up((size_t)n * batch * 8);
+  c.X = (double*)p;
+  c.part = (double*)(p ? p + xb : nullptr);
+  c.bytes = xb + align_up((size_t)batch * ceil_div(n, RC) * n * 8);
+  return c;
+}
+
+static bool cond_batch_ok(int batch) { return batch == 1 || batch == 4 || batch == 8; }
+
+template <int T>
+static void launch_cond_batch(const double* Sigma, int64_t n, int64_t lda, const int64_t* forced,
+                              int64_t j0, int nt, const CondScratch& c, hipStream_t s) {
+  hipLaunchKernelGGL(greedy_extract_batch_kernel<T>, dim3((unsigned)ceil_div(n * T, 256)),
+                     dim3(256), 0, s, Sigma, n, lda, forced, j0, nt, c.X);
+  dim3 g((unsigned)ceil_div(n, TRMV_COLS), (unsigned)ceil_div(n, RC));
+  const bool vec = (reinterpret_cast<uintptr_t>(Sigma) % 16 == 0) && (lda % 2 == 0);
+  ProfScope ps("greedy_trmv_batch", s, 2.0 * T * 0.5 * (double)n * (n + 1),
+               8.0 * (0.5 * (double)n * (n + 1) + (double)T * n));
+  if (vec)
+    hipLaunchKernelGGL((greedy_trmv_batch_kernel<T, true>), g, dim3(CT), 0, s, Sigma, n, lda,
+                       forced, j0, nt, c.X, c.part);
+  else
+    hipLaunchKernelGGL((greedy_trmv_batch_kernel<T, false>), g, dim3(CT), 0, s, Sigma, n, lda,
+                       forced, j0, nt, c.X, c.part);
+}
+
+}  // namespace vgposp
+
+extern "C" int vgposp_greedy_mask(void* ws, int64_t n, int kmax, const unsigned char* allowed,
+                                  void* stream) {
+  using namespace vgposp;
+  clear_error();
+  VG_CHECK_ARG(ws != nullptr, 1);
+  VG_CHECK_ARG(n >= 1 && n <= (int64_t)MAXCH * CH, 2);
+  VG_CHECK_ARG(kmax >= 1 && kmax <= n, 3);
+  VG_CHECK_ARG(allowed != nullptr, 4);
+  GreedyWS w = greedy_layout(ws, n, kmax);
+  hipLaunchKernelGGL(greedy_mask_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0,
+                     as_stream(stream), n, allowed, w.selmask);
+  VG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int vgposp_greedy_force(int64_t n, int kmax, int round, const int64_t* forced,
+                                   int64_t j, int64_t* selected, void* ws, size_t ws_bytes,
+                                   void* stream) {
+  using namespace vgposp;
+  clear_error();
+  GreedyWS w;
+  double dummy = 0.0;
+  int rc = greedy_check(__func__, &dummy, n, n, kmax, round, ws, ws_bytes, &w);
+  if (rc) return rc;
+  VG_CHECK_ARG(forced != nullptr, 4);
+  VG_CHECK_ARG(j >= 0, 5);
+  VG_CHECK_ARG(selected != nullptr, 6);
+  hipLaunchKernelGGL(greedy_force_kernel, dim3(1), dim3(256), 0, as_stream(stream), n, round,
+                     forced, j, selected, w);
+  VG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" size_t vgposp_greedy_condition_workspace_bytes(int64_t n, int batch) {
+  using namespace vgposp;
+  if (n <= 0 || !cond_batch_ok(batch)) return 0;
+  return batch == 1 ? 256 : cond_layout(nullptr, n, batch).bytes;
+}
+
+extern "C" int vgposp_greedy_condition(const double* Sigma, int64_t n, int64_t lda, int kmax,
+                                       int m, int k, int batch, const int64_t* placed,
+                                       int64_t* selected, void* ws, size_t ws_bytes,
+                                       void* scratch, size_t scratch_bytes, void* stream) {
+  using namespace vgposp;
+  clear_error();
+  GreedyWS w;
+  int rc = greedy_check(__func__, Sigma, n, lda, kmax, 0, ws, ws_bytes, &w);
+  if (rc) return rc;
+  VG_CHECK_ARG(m >= 1 && m <= kmax, 5);
+  VG_CHECK_ARG(k >= 0 && (int64_t)m + k <= kmax, 6);
+  VG_CHECK_ARG(batch >= 1 && cond_batch_ok(batch), 7);
+  VG_CHECK_ARG(placed != nullptr, 8);
+  VG_CHECK_ARG(selected != nullptr, 9);
+  VG_CHECK_ARG(scratch != nullptr, 12);
+  const size_t need = vgposp_greedy_condition_workspace_bytes(n, batch);
+  if (scratch_bytes < need) {
+    set_error("%s: scratch %zu < %zu bytes", __func__, scratch_bytes, need);
+    return VGPOSP_E_WS;
+  }
+  hipStream_t s = as_stream(stream);
+  auto force = [&](int round) {
+    return vgposp_greedy_force(n, kmax, round, placed, round, selected, ws, ws_bytes, stream);
+  };
+  // round 0: nom = diag(Sigma), prec = Q_ii from init's column norms; A <- [a_0]
+  if ((rc = vgposp_greedy_update(Sigma, n, lda, kmax, 0, 0, n, selected, ws, ws_bytes, stream)))
+    return rc;
+  if ((rc = force(0))) return rc;
+  // rounds 1 .. m-1 condition on a_0 .. a_{m-2}; a_{m-1}'s column is left to the next
+  // vgposp_greedy_step (round m), whose own mat-vec reads selected[m - 1]
+  if (batch == 1) {
+    for (int r = 1; r < m; ++r) {
+      if ((rc = vgposp_greedy_update(Sigma, n, lda, kmax, r, 0, n, selected, ws, ws_bytes,
+                                     stream)))
+        return rc;
+      if ((rc = force(r))) return rc;
+    }
+    return 0;
+  }
+  const CondScratch c = cond_layout(scratch, n, batch);
+  const int64_t slice = ceil_div(n, RC) * n;
+  for (int j0 = 0; j0 < m - 1; j0 += batch) {
+    const int nt = std::min(batch, m - 1 - j0);
+    if (batch == 4)
+      launch_cond_batch<4>(Sigma, n, lda, placed, j0, nt, c, s);
+    else
+      launch_cond_batch<8>(Sigma, n, lda, placed, j0, nt, c, s);
+    VG_LAUNCH_CHECK();
+    for (int j = 0; j < nt; ++j) {
+      const int r = j0 + j + 1;  // the update that conditions on a_{r-1} = placed[j0 + j]
+      GreedyWS wj = w;
+      wj.part = c.part + (int64_t)j * slice;
+      ProfScope psu("greedy_update", s, 0.0, 8.0 * (double)n * (6 + 2.0 * r));
+      hipLaunchKernelGGL(greedy_update_kernel, dim3((unsigned)ceil_div(n, CH)), dim3(CH), 0, s,
+                         Sigma, n, lda, selected, r, wj, (int64_t)0, n);
+      VG_LAUNCH_CHECK();
+      if ((rc = force(r))) return rc;
+    }
+  }
+  return 0;
+}

@@ -26,7 +26,12 @@ import torch
 
 from . import linalg
 from ._lib import CholeskyError, call, query
+from .constraints import normalize_constraints
 from .linalg import _p, _stream
+
+# Sensors whose columns q_a = M^T (M e_a) one pass over L^-1 forms while conditioning on ``placed``
+# (vgposp_greedy_condition: 1, 4 or 8).
+CONDITION_BATCH = 8
 
 
 class GreedyPlacement:
@@ -35,16 +40,31 @@ class GreedyPlacement:
     ``Sigma`` (float64, contiguous, lda = N) is FACTORED IN PLACE by ``init()``: its lower triangle
     becomes L^-1, the strictly upper triangle (Sigma itself) and the saved diagonal are what the
     nominators read.  Pass ``copy=True`` to work on a private copy.
+
+    ``candidates`` (index list or boolean mask of length N) restricts where a sensor may go: the
+    other locations are never picked but stay in A_bar, so every denominator still conditions on
+    them.  ``placed`` (index list, in order, not necessarily inside ``candidates``) are sensors
+    already installed: ``init()`` conditions the state on them (``condition_batch`` of their
+    columns per pass over L^-1) and the rounds continue from there.  ``kmax``, ``rounds`` and
+    ``result()`` count the new picks only; ``placed`` holds A0.
     """
 
     def __init__(self, Sigma, kmax, copy=False, jitter=0.0, threshold=1e-8,
-                 cache_init=float("inf"), pad_odd=False):
+                 cache_init=float("inf"), pad_odd=False, candidates=None, placed=None,
+                 condition_batch=None):
         S = linalg.as_device(Sigma)
         if S.dim() != 2 or S.shape[0] != S.shape[1]:
             raise ValueError("cov_vv must be a square matrix")
         self.N = int(S.shape[0])                     # candidates
         if not (1 <= kmax <= self.N):
             raise ValueError(f"k must be in [1, {self.N}], got {kmax}")
+        self.constrained = candidates is not None or placed is not None
+        self.allowed, self.placed = (normalize_constraints(self.N, kmax, candidates, placed)
+                                     if self.constrained else (None, np.zeros(0, np.int64)))
+        self.m = len(self.placed)                    # |A0|: forced rounds before the first pick
+        self.condition_batch = CONDITION_BATCH if condition_batch is None else int(condition_batch)
+        if self.condition_batch not in (1, 4, 8):
+            raise ValueError(f"condition_batch must be 1, 4 or 8, got {condition_batch}")
         # pad_odd (with copy): an odd order is factored as [Sigma 0; 0 s] at N + 1, so every
         # recursion level runs on the fast (even-leading-dimension) GEMM; the padding candidate is
         # excluded on device after init (vgposp_greedy_exclude) and couples to nothing
@@ -58,7 +78,8 @@ class GreedyPlacement:
         else:
             self.S = S.clone() if copy else S
         self.n = int(self.S.shape[0])                # the library's order
-        self.kmax = int(kmax)
+        self.k = int(kmax)                           # new picks
+        self.kmax = self.k + self.m                  # the library's rounds: A0, then the picks
         dev = self.S.device
         self.ws = linalg.workspace(query("vgposp_greedy_workspace_bytes", self.n, self.kmax))
         self.info = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -69,14 +90,44 @@ class GreedyPlacement:
         # (jitter, |nom|/|denom| threshold, initial cache): (0, 1e-8, inf) is placement_algorithm2;
         # (1e-6, 1e-7, 1e8) is the TF variant snippets_a2.sparse_placement_algorithm_2
         self.params = (float(jitter), float(threshold), float(cache_init))
+        self._lazy = True                            # the mode of the last step()
+        # the constraints are uploaded here, so that init() only enqueues work (graph capture)
+        self._blocked = self._allowed_dev = self._placed_dev = self._cond_ws = None
+        if self.constrained:
+            allowed = np.zeros(self.n, dtype=bool)   # the odd-order padding is never allowed
+            allowed[: self.N] = True if self.allowed is None else self.allowed
+            if self.allowed is not None:
+                self._allowed_dev = torch.as_tensor(allowed.astype(np.uint8), device=dev)
+            allowed[self.placed] = False
+            self.free = int(allowed.sum())           # |candidates \ A0|
+            # never an arg-max: not a candidate, or in A0
+            self._blocked = torch.as_tensor(~allowed[: self.N], device=dev)
+        if self.m:
+            self._placed_dev = torch.as_tensor(self.placed, dtype=torch.int64, device=dev)
+            self._cond_ws = linalg.workspace(query("vgposp_greedy_condition_workspace_bytes",
+                                                   self.n, self.condition_batch))
 
     def init(self):
         call("vgposp_greedy_init_ex", _p(self.S), self.n, self.S.stride(0), self.kmax,
              *self.params, _p(self.info), _p(self.ws), self.ws.numel(), _stream())
         if self.padded:
             call("vgposp_greedy_exclude", _p(self.ws), self.n, self.kmax, self.N, _stream())
+        if self.constrained:
+            self.constrain()
         self.rounds = 0
         return self
+
+    def constrain(self):
+        """The constrained part of init(), on the state the factorization leaves: mask the
+        non-candidates, then the forced rounds on ``placed``."""
+        if self._allowed_dev is not None:
+            call("vgposp_greedy_mask", _p(self.ws), self.n, self.kmax, _p(self._allowed_dev),
+                 _stream())
+        if self.m:
+            call("vgposp_greedy_condition", _p(self.S), self.n, self.S.stride(0), self.kmax,
+                 self.m, self.k, self.condition_batch, _p(self._placed_dev), _p(self.selected),
+                 _p(self.ws), self.ws.numel(), _p(self._cond_ws), self._cond_ws.numel(),
+                 _stream())
 
     def cache(self):
         """Device view of the lazy cache (delta_cached) [n] inside the workspace."""
@@ -89,15 +140,16 @@ class GreedyPlacement:
         linalg.check_info(self.info)
 
     def step(self, lazy=True):
-        if self.rounds >= self.kmax:
+        if self.rounds >= self.k:
             raise RuntimeError("all k sensors already placed")
-        call("vgposp_greedy_step", _p(self.S), self.n, self.S.stride(0), self.kmax, self.rounds,
-             int(lazy), _p(self.selected), _p(self.sel_delta), _p(self.evals), _p(self.ws),
-             self.ws.numel(), _stream())
+        call("vgposp_greedy_step", _p(self.S), self.n, self.S.stride(0), self.kmax,
+             self.m + self.rounds, int(lazy), _p(self.selected), _p(self.sel_delta),
+             _p(self.evals), _p(self.ws), self.ws.numel(), _stream())
+        self._lazy = bool(lazy)
         self.rounds += 1
 
     def run(self, k=None, lazy=True):
-        k = self.kmax if k is None else k
+        k = self.k if k is None else k
         self.init()
         for _ in range(k):
             self.step(lazy)
@@ -117,21 +169,28 @@ class GreedyPlacement:
         cache = self.cache()
         key = torch.nan_to_num(cache.clone(), nan=-float("inf"))
         if r:
-            key[self.selected[:r]] = -float("inf")
+            key[self.selected[self.m:self.m + r]] = -float("inf")
+        if self._blocked is not None:  # the reference's loop runs over candidates \ A only
+            key[self._blocked] = -float("inf")
         self.step(lazy=True)
-        order = torch.sort(key, descending=True, stable=True).indices[: int(self.evals[r])]
+        order = torch.sort(key, descending=True, stable=True).indices[: int(self.evals[self.m + r])]
         for c, d in zip(order.cpu().numpy(), cache[order].cpu().numpy()):
             trace.append((int(c), float(d)))
-        trace.append(("select", int(self.selected[r])))
+        trace.append(("select", int(self.selected[self.m + r])))
 
     def result(self):
-        """Selections (host list of np.int64), their deltas, and per-round evaluation counts."""
+        """Selections (host list of np.int64), their deltas, and per-round evaluation counts.
+        With ``placed``, these are the new picks only (A0 is ``self.placed``)."""
         self.check()
-        sel = self.selected[: self.rounds].cpu().numpy()
+        new = slice(self.m, self.m + self.rounds)
+        sel = self.selected[new].cpu().numpy()
         if (sel < 0).any():
             raise RuntimeError("greedy placement found no candidate (all deltas NaN?)")
-        return ([np.int64(s) for s in sel], self.sel_delta[: self.rounds].cpu().numpy(),
-                self.evals[: self.rounds].cpu().numpy())
+        evals = self.evals[new].cpu().numpy()
+        if self.constrained and not self._lazy:
+            # full greedy scores every candidate outside A (argmax_, :105-125): |candidates \ A|
+            evals = self.free - np.arange(self.rounds, dtype=np.int64)
+        return [np.int64(s) for s in sel], self.sel_delta[new].cpu().numpy(), evals
 
 
 # A singular (PSD, not PD) cov_vv, e.g. an empirical covariance with fewer samples than locations
@@ -166,14 +225,17 @@ def _rounds(g, k, lazy, trace):
     return g.result()[0]
 
 
-def _place(cov_vv, k, lazy, verbose, trace=None):
+def _place(cov_vv, k, lazy, verbose, trace=None, candidates=None, placed=None):
+    con = dict(candidates=candidates, placed=placed)
     if k < 1:
+        if candidates is not None or placed is not None:
+            normalize_constraints(int(np.shape(cov_vv)[0]), max(k, 0), candidates, placed)
         return []
     if verbose and trace is None:
         trace = []
     tr = None if trace is None else []
     try:
-        g = GreedyPlacement(cov_vv, k, copy=True, pad_odd=True)
+        g = GreedyPlacement(cov_vv, k, copy=True, pad_odd=True, **con)
         sdiag = torch.diagonal(g.S).clone()
         g.init()
         _check_pivots(g, sdiag)
@@ -184,7 +246,8 @@ def _place(cov_vv, k, lazy, verbose, trace=None):
         for rel in SINGULAR_EPS:
             try:
                 tr = None if trace is None else []
-                g = GreedyPlacement(S, k, copy=True, jitter=rel * scale, pad_odd=True).init()
+                g = GreedyPlacement(S, k, copy=True, jitter=rel * scale, pad_odd=True,
+                                    **con).init()
                 A = _rounds(g, k, lazy, tr)
                 break
             except CholeskyError:
@@ -202,18 +265,23 @@ def _place(cov_vv, k, lazy, verbose, trace=None):
     return A
 
 
-def placement_algorithm_2(cov_vv, k, verbose=False, trace=None):
+def placement_algorithm_2(cov_vv, k, verbose=False, trace=None, candidates=None, placed=None):
     """Lazy greedy MI placement (placement_algorithm2.py:151-219).  Returns k indices.
+
+    ``candidates`` (index list or boolean mask of length N): the locations where a sensor may go;
+    the others are never picked but still count in every denominator.  ``placed`` (index list):
+    sensors already installed; the k new picks are returned, ``placed`` is not part of them.
 
     ``verbose=True`` prints the reference's per-evaluation lines (``delta_y= … y_st= …`` for every
     delta evaluated, ``y*= …`` per selection, :205 / :188); ``trace`` (a list) receives the same
     records as ``(y, delta)`` / ``('select', y)`` tuples without printing."""
-    return _place(cov_vv, k, True, verbose, trace)
+    return _place(cov_vv, k, True, verbose, trace, candidates, placed)
 
 
-def placement_algorithm_1(cov_vv, k, verbose=False):
-    """Full greedy MI placement (placement_algorithm2.py:128-145).  Returns k indices."""
-    return _place(cov_vv, k, False, verbose)
+def placement_algorithm_1(cov_vv, k, verbose=False, candidates=None, placed=None):
+    """Full greedy MI placement (placement_algorithm2.py:128-145).  Returns k indices;
+    ``candidates`` / ``placed`` as in ``placement_algorithm_2``."""
+    return _place(cov_vv, k, False, verbose, None, candidates, placed)
 
 
 def cov_vv_4x4():
@@ -231,8 +299,9 @@ def dg_create_random_cov(n, rng=None):
     return np.dot(m, m.T)
 
 
-def placement_from_points(X, k, kind="eq", amp=1.0, ls=1.0, noise=1e-2, jitter=1e-6, lazy=True):
+def placement_from_points(X, k, kind="eq", amp=1.0, ls=1.0, noise=1e-2, jitter=1e-6, lazy=True,
+                          candidates=None, placed=None):
     """Assemble Sigma = K(X, X) + (noise + jitter) I on device and place k sensors."""
     K = linalg.kernel_matrix(kind, X, None, amp, ls, diag_shift=noise + jitter)[0]
-    g = GreedyPlacement(K, k).run(k, lazy=lazy)
+    g = GreedyPlacement(K, k, candidates=candidates, placed=placed).run(k, lazy=lazy)
     return g.result()[0]

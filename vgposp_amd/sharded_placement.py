@@ -32,6 +32,7 @@ import torch
 import torch.distributed as dist
 
 from ._lib import call
+from .constraints import reject_constraints
 from .linalg import _p, _stream
 
 
@@ -68,8 +69,9 @@ def inverse_slabs(n, world, align=128):
 class HipGreedyBackend:
     """The per-rank device state: a GreedyPlacement plus tensor views of its delta / pivot."""
 
-    def __init__(self, Sigma, kmax, copy=False, jitter=0.0):
+    def __init__(self, Sigma, kmax, copy=False, jitter=0.0, candidates=None, placed=None):
         from .placement_algorithm2 import GreedyPlacement
+        reject_constraints("the sharded placement", candidates, placed)
         self._src = Sigma if copy else None
         self.g = GreedyPlacement(Sigma, kmax, copy=copy, jitter=jitter)
         # diag(Sigma) for the pivot-ratio check, taken right before each factorization
@@ -194,7 +196,10 @@ class HipGreedyBackend:
 
 class ShardedGreedyPlacement:
     def __init__(self, backend, group=None, balance=True, partition_inverse=False, align=128,
-                 dist_factor=True, dist_min=None):
+                 dist_factor=True, dist_min=None, candidates=None, placed=None):
+        reject_constraints("the sharded placement", candidates, placed)
+        if getattr(getattr(backend, "g", None), "constrained", False):
+            raise ValueError("the sharded placement does not support candidates / placed")
         self.b = backend
         self.dist_factor = bool(dist_factor)
         self.dist_min = dist_min
@@ -294,9 +299,10 @@ class ShardedGreedyPlacement:
 
 
 def placement_algorithm_2_sharded(cov_vv, k, group=None, lazy=True, partition_inverse=True,
-                                  dist_factor=True, dist_min=None):
+                                  dist_factor=True, dist_min=None, candidates=None, placed=None):
     """placement_algorithm_2 with candidates sharded over the ranks of ``group`` (every rank
     passes the same cov_vv and gets the same list)."""
+    reject_constraints("the sharded placement", candidates, placed)
     sh = ShardedGreedyPlacement(HipGreedyBackend(cov_vv, k, copy=True), group,
                                 partition_inverse=partition_inverse, dist_factor=dist_factor,
                                 dist_min=dist_min)

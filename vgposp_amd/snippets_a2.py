@@ -22,6 +22,7 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
+from .constraints import reject_constraints
 from .placement_algorithm2 import GreedyPlacement
 
 TF_JITTER = 1e-6   # snippets_a2.py:161-163
@@ -37,10 +38,11 @@ class SparseSet(NamedTuple):
 
 
 def sparse_placement_algorithm_2(cov_vv, k, COVER_spatial, jitter=TF_JITTER, threshold=TF_SMALL,
-                                 cache_init=TF_INF):
+                                 cache_init=TF_INF, candidates=None, placed=None):
     """Returns ``(A, len_A, delta_cached_iters [N, k] f64, A_selection_and_delta [k, 2] f64)``
     like snippets_a2.py:822.  ``cov_vv``: [N, N] float64 (numpy or device tensor), N must equal
     COVER_spatial[0] * COVER_spatial[1] * COVER_spatial[2] (the tf.Assert at :692)."""
+    reject_constraints("sparse_placement_algorithm_2", candidates, placed)
     N = int(cov_vv.shape[0])
     cover = int(np.prod([int(c) for c in COVER_spatial[:3]]))
     if N != cover:

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from ._lib import call
+from .constraints import reject_constraints
 from .linalg import _p, _stream
 from .placement_algorithm2 import GreedyPlacement
 from .snippets_a2 import TF_INF, TF_JITTER, TF_SMALL, SparseSet
@@ -34,7 +35,8 @@ class WindowGreedy(GreedyPlacement):
     """Device-resident algorithm 3 (round-by-round, like GreedyPlacement)."""
 
     def __init__(self, Sigma, kmax, COVER_spatial, cutoff, copy=False, jitter=TF_JITTER,
-                 threshold=TF_SMALL, cache_init=TF_INF):
+                 threshold=TF_SMALL, cache_init=TF_INF, candidates=None, placed=None):
+        reject_constraints("WindowGreedy (placement algorithm 3)", candidates, placed)
         super().__init__(Sigma, kmax, copy=copy, jitter=jitter, threshold=threshold,
                          cache_init=cache_init)
         self.I = _cover(COVER_spatial, self.n)
@@ -53,18 +55,20 @@ class WindowGreedy(GreedyPlacement):
         self.rounds += 1
 
 
-def sparse_placement_algorithm_3(cov_vv, k, COVER_spatial, cutoff):
+def sparse_placement_algorithm_3(cov_vv, k, COVER_spatial, cutoff, candidates=None, placed=None):
     """-> (A as a SparseSet, final delta_cached [N, 1], delta_cached_iters [N, k]) like
     snippets_a3.py:330; ``A.order`` is not part of the reference (its A is a set) — the ordered
     picks are returned by ``placement_algorithm_3``."""
+    reject_constraints("sparse_placement_algorithm_3", candidates, placed)
     A, cache, dci = _run(cov_vv, k, COVER_spatial, cutoff)
     vals = np.sort(np.asarray(A, dtype=np.int64))
     Aset = SparseSet(np.stack([vals, np.zeros_like(vals)], axis=1), vals, (len(cache), 1))
     return Aset, cache.reshape(-1, 1), dci
 
 
-def placement_algorithm_3(cov_vv, k, COVER_spatial, cutoff):
+def placement_algorithm_3(cov_vv, k, COVER_spatial, cutoff, candidates=None, placed=None):
     """The ordered picks of algorithm 3 (list of np.int64)."""
+    reject_constraints("placement_algorithm_3", candidates, placed)
     return _run(cov_vv, k, COVER_spatial, cutoff)[0]
 
 

@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from ._lib import KERNEL_KINDS, CholeskyError, call, query
+from .constraints import reject_constraints
 from .linalg import _p, _stream
 from .taper import TF_JITTER, TF_SMALL, taper_support
 from .nested_dissection import frontal_tree
@@ -741,7 +742,8 @@ class ExactTaperPlacement:
 
     def __init__(self, X, shape, k, cutoff, beta=4.0, kind="eq", amp=1.0, ls=1.0, diag_shift=0.0,
                  jitter=TF_JITTER, threshold=TF_SMALL, leaf=512, device=None, group=None,
-                 method="auto"):
+                 method="auto", candidates=None, placed=None):
+        reject_constraints("the exact tapered placement", candidates, placed)
         if method not in ("auto", "bounds", "selinv"):
             raise ValueError(f"method must be auto / bounds / selinv, got {method!r}")
         self.prob = TaperProblem(X, shape, beta, kind, amp, ls, diag_shift, jitter, threshold,
@@ -789,11 +791,12 @@ class ExactTaperPlacement:
 
 def tapered_placement_algorithm_3(X, k, COVER_spatial, cutoff, beta=4.0, kernel="eq", amp=1.0,
                                   ls=1.0, diag_shift=0.0, snapshots=False, leaf=512, group=None,
-                                  method="auto"):
+                                  method="auto", candidates=None, placed=None):
     """snippets_a3.sparse_placement_algorithm_3(cov_vv, k, COVER_spatial, cutoff) for the tapered
     covariance of the grid points X (C order, COVER_spatial = (I0, I1, I2)), exact, without the
     dense cov_vv.  -> (picks as a list of np.int64 in selection order, the pick deltas,
     delta_cached_iters [N, k] or None)."""
+    reject_constraints("the exact tapered placement", candidates, placed)
     shape = tuple(int(c) for c in COVER_spatial[:3])
     N = shape[0] * shape[1] * shape[2]
     if len(X) != N:                                         # snippets_a3.py:51 tf.Assert
