@@ -242,6 +242,38 @@ int vgposp_kernel_vjp(int kind, const double* X1, int64_t n1, const double* X2, 
                       size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Per-feature length scales: tfkern.FeatureScaled(base, scale_diag),
+ *     k(x1, x2) = base(x1 / scale_diag, x2 / scale_diag),   scale: device [d], 1 <= d <= 8.
+ * vgposp_scale_points: out[i][k] = X[i][k] / scale[k] (a true division, as TFP; out may alias X;
+ *   n == 0 returns 0 without device work; no host synchronisation).  Every assembly entry of this
+ *   header applied to scaled points is the FeatureScaled kernel.
+ * vgposp_kernel_vjp_scaled: vgposp_kernel_vjp on ALREADY-SCALED points Z1 = X1 / scale,
+ *   Z2 = X2 / scale, with the scale gradient from the same single pass over Kbar:
+ *     grad[0], grad[1] as vgposp_kernel_vjp,
+ *     grad[2 + k] = sum_ij (Kbar + u w^T)_ij dK_ij/dscale_k,
+ *                   dK_ij/dscale_k = -c_ij (z1_ik - z2_jk)^2 / scale_k,  dK/dz1 = c (z1 - z2),
+ *     X1bar [n1 x d] or NULL: with respect to the UNSCALED X1 (the z-space adjoint / scale_k).
+ *   grad: [2 + d].  Deterministic (fixed-order reduction, no atomics).
+ * vgposp_lml_grad_scaled: vgposp_lml_grad for one FeatureScaled kernel (batch 1) on scaled points
+ *   Z [n x d]: grad [3 + d] = (d/damp, d/dls, d/dnoise, d/dscale_0 ... d/dscale_{d-1}),
+ *     grad[3 + k] = 0.5 sum_ij (alpha alpha^T - C^-1)_ij dC_ij/dscale_k.
+ *   Reads the lower triangle of Cinv.  Deterministic.
+ * --------------------------------------------------------------------------------------------- */
+int vgposp_scale_points(const double* X, int64_t n, int d, const double* scale, double* out,
+                        void* stream);
+size_t vgposp_kernel_vjp_scaled_workspace_bytes(int64_t n1, int64_t n2, int d);
+int vgposp_kernel_vjp_scaled(int kind, const double* Z1, int64_t n1, const double* Z2, int64_t n2,
+                             int d, const double* amp, const double* ls, const double* scale,
+                             const double* Kbar, int64_t ldk, const double* u, const double* w,
+                             double* grad, double* X1bar, void* ws, size_t ws_bytes,
+                             void* stream);
+size_t vgposp_lml_grad_scaled_workspace_bytes(int64_t n);
+int vgposp_lml_grad_scaled(int kind, const double* Z, int64_t n, int d, const double* amp,
+                           const double* ls, const double* scale, const double* Cinv, int64_t ldc,
+                           const double* alpha, double* grad, void* ws, size_t ws_bytes,
+                           void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Covariance builders (cov_vv on device).
  * vgposp_kernel_matvec: out[i] = sum_j K(X1_i, X2_j) v[j] + beta * out[i] for one kernel (amp, ls:
  *   device [1]), without materialising K: the VGP / GPRM predictive mean at many points, e.g. the

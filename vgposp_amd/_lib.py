@@ -102,6 +102,16 @@ SIGNATURES = {
     "vgposp_kernel_vjp": (_i32, [_i32, _c_void_p, _i64, _c_void_p, _i64, _i32, _c_void_p,
                                  _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p,
                                  _c_void_p, _c_void_p, _size, _c_void_p]),
+    "vgposp_scale_points": (_i32, [_c_void_p, _i64, _i32, _c_void_p, _c_void_p, _c_void_p]),
+    "vgposp_kernel_vjp_scaled_workspace_bytes": (_size, [_i64, _i64, _i32]),
+    "vgposp_kernel_vjp_scaled": (_i32, [_i32, _c_void_p, _i64, _c_void_p, _i64, _i32, _c_void_p,
+                                        _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p,
+                                        _c_void_p, _c_void_p, _c_void_p, _c_void_p, _size,
+                                        _c_void_p]),
+    "vgposp_lml_grad_scaled_workspace_bytes": (_size, [_i64]),
+    "vgposp_lml_grad_scaled": (_i32, [_i32, _c_void_p, _i64, _i32, _c_void_p, _c_void_p,
+                                      _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p,
+                                      _size, _c_void_p]),
     "vgposp_kernel_matvec": (_i32, [_i32, _c_void_p, _i64, _c_void_p, _i64, _i32, _c_void_p,
                                     _c_void_p, _c_void_p, _f64, _c_void_p, _c_void_p]),
     "vgposp_center_rows": (_i32, [_c_void_p, _i64, _i64, _i64, _f64, _c_void_p]),

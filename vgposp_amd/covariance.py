@@ -25,6 +25,7 @@ import torch
 from . import linalg
 from ._lib import FULL, LOWER, call
 from .linalg import F64, _p, _stream, kind_id
+from .psd_kernels import scaled_points
 
 
 def kernel_matvec(kind, X1, X2, amp, ls, v, out=None, beta=0.0):
@@ -89,7 +90,7 @@ def vgp_tracer_samples(vgp, locations, tp_samples, chunk_points=1 << 24):
     tp = tp[:, None] if tp.dim() == 1 else tp
     N, S = loc.shape[0], tp.shape[0]
     w, mz_free = vgp.mean_weights()
-    Z = linalg.as_device(vgp._Z())
+    Z = linalg.as_device(scaled_points(vgp.kernel, vgp._Z()))
     amp, ls = vgp.kernel.params()
     T = torch.empty((N, S), dtype=F64, device=loc.device)
     rows = max(1, chunk_points // S)
@@ -97,7 +98,7 @@ def vgp_tracer_samples(vgp, locations, tp_samples, chunk_points=1 << 24):
         r1 = min(N, r0 + rows)
         pts = torch.cat([loc[r0:r1, None, :].expand(r1 - r0, S, loc.shape[1]),
                          tp[None, :, :].expand(r1 - r0, S, tp.shape[1])], dim=2)
-        pts = pts.reshape(-1, loc.shape[1] + tp.shape[1]).contiguous()
+        pts = scaled_points(vgp.kernel, pts.reshape(-1, loc.shape[1] + tp.shape[1]).contiguous())
         kernel_matvec(vgp.kernel.kind, pts, Z, amp[0:1], ls[0:1], w, out=T[r0:r1].reshape(-1))
     if not mz_free:
         raise NotImplementedError("vgp_tracer_samples supports the zero mean function only")

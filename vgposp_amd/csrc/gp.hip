@@ -12,6 +12,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "psd.h"
 
 namespace vgposp {
 
@@ -162,6 +163,110 @@ __global__ __launch_bounds__(1024) void lml_grad_reduce_kernel(int64_t nblk, con
     const double v = block_sum_1024(s[q]);
     if (threadIdx.x == 0) grad[b * 3 + q] = 0.5 * v;
   }
+}
+
+// ---- the LML gradient of a FeatureScaled kernel ------------------------------------------------
+// On points z = x / s (already divided): the three sums of lml_grad_kernel plus, per feature k,
+//   sum G dK/ds_k = -(1 / s_k) sum G c(r) (z_ik - z_jk)^2      (c of psd.h's kvjp_entry),
+// in the same pass over the lower triangle of C^-1.  A workgroup owns a 16-row stripe, whose points
+// and alpha sit in LDS; a lane owns a column of each 256-column block and keeps that point and its
+// alpha in registers for the 16 rows, so a point is read from global memory once per block and
+// stripe, not once per entry.  Row by row the lanes read consecutive columns of C^-1 (coalesced).
+constexpr int GS_MAXD = 8;
+
+template <int KIND, int D>
+__global__ __launch_bounds__(256) void lml_grad_scaled_kernel(const double* Z, int64_t n,
+                                                              const double* amp, const double* ls,
+                                                              const double* Cinv, int64_t ldc,
+                                                              const double* alpha, double* part) {
+  constexpr int NG = 3 + D;
+  __shared__ double zr[GR_ROWS][D];
+  __shared__ double ar[GR_ROWS];
+  __shared__ double sh[NG][4];
+  const int64_t r0 = (int64_t)blockIdx.x * GR_ROWS;
+  const int rows = (int)min((int64_t)GR_ROWS, n - r0);
+  for (int e = threadIdx.x; e < rows * D; e += 256) zr[e / D][e % D] = Z[r0 * D + e];
+  if ((int)threadIdx.x < rows) ar[threadIdx.x] = alpha[r0 + threadIdx.x];
+  __syncthreads();
+  const double a = amp[0], l = ls[0];
+  const double tla = 2.0 * log(a), inv_l = 1.0 / l, inv_l2 = inv_l * inv_l, two_over_a = 2.0 / a;
+  double sa = 0.0, sl = 0.0, sn = 0.0, gs[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) gs[k] = 0.0;
+  for (int64_t j = threadIdx.x; j < r0 + rows; j += 256) {
+    double zj[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) zj[k] = Z[j * D + k];
+    const double aj = alpha[j];
+    // rows above column j (i < j) lie in the upper triangle: start at the first row i >= j
+    for (int rr = (int)max((int64_t)0, j - r0); rr < rows; ++rr) {
+      const int64_t i = r0 + rr;
+      double diff[D], d2 = 0.0;
+#pragma unroll
+      for (int k = 0; k < D; ++k) {
+        diff[k] = zr[rr][k] - zj[k];
+        d2 += diff[k] * diff[k];
+      }
+      double K, dkl, cx;
+      kvjp_entry<KIND>(d2, tla, inv_l, inv_l2, K, dkl, cx);
+      const double g = ar[rr] * aj - Cinv[i * ldc + j];
+      const double wg = (j == i ? 1.0 : 2.0) * g;
+      sa += wg * K * two_over_a;
+      sl += wg * dkl;
+      if (j == i) sn += g;
+      const double cf = wg * cx;
+#pragma unroll
+      for (int k = 0; k < D; ++k) gs[k] += cf * diff[k] * diff[k];
+    }
+  }
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  sa = wave_sum(sa);
+  sl = wave_sum(sl);
+  sn = wave_sum(sn);
+  if (lane == 0) {
+    sh[0][w] = sa;
+    sh[1][w] = sl;
+    sh[2][w] = sn;
+  }
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    const double v = wave_sum(gs[k]);
+    if (lane == 0) sh[3 + k][w] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < NG) {
+    const double v = sh[threadIdx.x][0] + sh[threadIdx.x][1] + sh[threadIdx.x][2] + sh[threadIdx.x][3];
+    part[(int64_t)blockIdx.x * NG + threadIdx.x] = v;
+  }
+}
+
+// grad[q] = 0.5 sum over the stripes (fixed order), the scale entries times -1 / s_k.
+__global__ __launch_bounds__(1024) void lml_grad_scaled_reduce_kernel(int64_t nblk, int d,
+                                                                      const double* part,
+                                                                      const double* scale,
+                                                                      double* grad) {
+  const int ng = 3 + d;
+  for (int q = 0; q < ng; ++q) {
+    double s = 0.0;
+    for (int64_t e = threadIdx.x; e < nblk; e += blockDim.x) s += part[e * ng + q];
+    const double v = block_sum_1024(s);
+    if (threadIdx.x == 0) grad[q] = q < 3 ? 0.5 * v : -0.5 * v / scale[q - 3];
+  }
+}
+
+template <int KIND>
+static void launch_lml_grad_scaled(dim3 g, hipStream_t s, int d, const double* Z, int64_t n,
+                                   const double* amp, const double* ls, const double* Cinv,
+                                   int64_t ldc, const double* alpha, double* part) {
+#define GS_CASE(DD)                                                                              \
+  case DD:                                                                                       \
+    hipLaunchKernelGGL((lml_grad_scaled_kernel<KIND, DD>), g, dim3(256), 0, s, Z, n, amp, ls,    \
+                       Cinv, ldc, alpha, part);                                                  \
+    break;
+  switch (d) {
+    GS_CASE(1) GS_CASE(2) GS_CASE(3) GS_CASE(4) GS_CASE(5) GS_CASE(6) GS_CASE(7) GS_CASE(8)
+  }
+#undef GS_CASE
 }
 
 // ---- row sums of squares (the marginal predictive variance) ----------------------------------
@@ -400,6 +505,46 @@ extern "C" int vgposp_lml_grad(int kind, const double* X, int64_t n, int d, cons
                      amp, ls, Cinv, ldc, stride_c, alpha, part);
   VG_LAUNCH_CHECK();
   hipLaunchKernelGGL(lml_grad_reduce_kernel, dim3(batch), dim3(1024), 0, s, nblk, part, grad);
+  VG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" size_t vgposp_lml_grad_scaled_workspace_bytes(int64_t n) {
+  if (n <= 0) return 0;
+  return (size_t)ceil_div(n, GR_ROWS) * (3 + GS_MAXD) * sizeof(double);
+}
+
+extern "C" int vgposp_lml_grad_scaled(int kind, const double* Z, int64_t n, int d,
+                                      const double* amp, const double* ls, const double* scale,
+                                      const double* Cinv, int64_t ldc, const double* alpha,
+                                      double* grad, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  VG_CHECK_ARG(kind >= VGPOSP_KERNEL_EQ && kind <= VGPOSP_KERNEL_MATERN52, 1);
+  VG_CHECK_ARG(Z != nullptr, 2);
+  VG_CHECK_ARG(n >= 1, 3);
+  VG_CHECK_ARG(d >= 1 && d <= GS_MAXD, 4);
+  VG_CHECK_ARG(amp != nullptr, 5);
+  VG_CHECK_ARG(ls != nullptr, 6);
+  VG_CHECK_ARG(scale != nullptr, 7);
+  VG_CHECK_ARG(Cinv != nullptr, 8);
+  VG_CHECK_ARG(ldc >= n, 9);
+  VG_CHECK_ARG(alpha != nullptr, 10);
+  VG_CHECK_ARG(grad != nullptr, 11);
+  VG_CHECK_ARG(ws != nullptr, 12);
+  VG_CHECK_WS(ws_bytes, vgposp_lml_grad_scaled_workspace_bytes(n));
+  hipStream_t s = as_stream(stream);
+  const int64_t nblk = ceil_div(n, GR_ROWS);
+  double* part = static_cast<double*>(ws);
+  const dim3 g((unsigned)nblk);
+  switch (kind) {
+    case VGPOSP_KERNEL_EQ: launch_lml_grad_scaled<VGPOSP_KERNEL_EQ>(g, s, d, Z, n, amp, ls, Cinv, ldc, alpha, part); break;
+    case VGPOSP_KERNEL_MATERN12: launch_lml_grad_scaled<VGPOSP_KERNEL_MATERN12>(g, s, d, Z, n, amp, ls, Cinv, ldc, alpha, part); break;
+    case VGPOSP_KERNEL_MATERN32: launch_lml_grad_scaled<VGPOSP_KERNEL_MATERN32>(g, s, d, Z, n, amp, ls, Cinv, ldc, alpha, part); break;
+    default: launch_lml_grad_scaled<VGPOSP_KERNEL_MATERN52>(g, s, d, Z, n, amp, ls, Cinv, ldc, alpha, part); break;
+  }
+  VG_LAUNCH_CHECK();
+  hipLaunchKernelGGL(lml_grad_scaled_reduce_kernel, dim3(1), dim3(1024), 0, s, nblk, d, part, scale,
+                     grad);
   VG_LAUNCH_CHECK();
   return 0;
 }

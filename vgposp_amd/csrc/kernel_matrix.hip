@@ -232,3 +232,32 @@ extern "C" int vgposp_kernel_matrix_matvec(int kind, const double* X1, int64_t n
   VG_LAUNCH_CHECK();
   return 0;
 }
+
+// ---- FeatureScaled inputs: out[i][k] = X[i][k] / scale[k] ------------------------------------
+// A true division (TFP divides; a multiply by the reciprocal differs in the last bit).  Elementwise
+// and in order, so out may alias X.
+namespace vgposp {
+__global__ __launch_bounds__(256) void scale_points_kernel(const double* X, int64_t total, int d,
+                                                           const double* scale, double* out) {
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += stride)
+    out[e] = X[e] / scale[e % d];
+}
+}  // namespace vgposp
+
+extern "C" int vgposp_scale_points(const double* X, int64_t n, int d, const double* scale,
+                                   double* out, void* stream) {
+  clear_error();
+  VG_CHECK_ARG(n >= 0, 2);
+  VG_CHECK_ARG(d >= 1 && d <= KM_MAXD, 3);
+  if (n == 0) return 0;
+  VG_CHECK_ARG(X != nullptr, 1);
+  VG_CHECK_ARG(scale != nullptr, 4);
+  VG_CHECK_ARG(out != nullptr, 5);
+  const int64_t total = n * d;
+  const int64_t nwg = ceil_div(total, 256) < 2048 ? ceil_div(total, 256) : 2048;
+  hipLaunchKernelGGL(scale_points_kernel, dim3((unsigned)nwg), dim3(256), 0, as_stream(stream), X,
+                     total, d, scale, out);
+  VG_LAUNCH_CHECK();
+  return 0;
+}

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import linalg
-from .psd_kernels import _pts
+from .psd_kernels import FeatureScaled, _pts, scaled_points
 from .variables import Placeholder, Softplus, Variable, fed, resolve
 
 LOG_2PI = math.log(2.0 * math.pi)
@@ -149,7 +149,8 @@ class GaussianProcess:
         return LogProb(out, self, value)
 
     def log_prob_and_grads(self, value, index_points=None):
-        """(LML[B], dLML/damp[B], dLML/dls[B], dLML/dnoise[B]) on device."""
+        """(LML[B], dLML/damp[B], dLML/dls[B], dLML/dnoise[B]) on device; with a FeatureScaled
+        kernel a fifth value, dLML/dscale_diag [d]."""
         X = self.index_points if index_points is None else index_points
         Xp = _pts(X)
         n = int(Xp.shape[0])
@@ -158,6 +159,10 @@ class GaussianProcess:
         lml, alpha = linalg.lml_from_inverse(Minv, ldiag, y, want_alpha=True)
         Q = linalg.inverse_from_factor_inverse(Minv)
         amp, ls = self.kernel.params()
+        if isinstance(self.kernel, FeatureScaled):
+            g = linalg.lml_grad_scaled(self.kernel.kind, self.kernel.scaled(Xp), amp, ls,
+                                       self.kernel.scale(), Q[0], alpha[0])
+            return lml, g[0:1], g[1:2], g[2:3], g[3:]
         g = linalg.lml_grad(self.kernel.kind, Xp, amp, ls, Q, alpha)
         return lml, g[:, 0], g[:, 1], g[:, 2]
 
@@ -269,8 +274,10 @@ class GaussianProcessRegressionModel(GaussianProcess):
         s2 = diag(K_ss) - sum(Lk^2, axis=0) (plot_confidence_interval.py:51), in O(chunk * n)
         memory.  The factorization is done once; the two strips are reused by every chunk."""
         X = self.observation_index_points
-        Xo = _device_pts(X)
-        Xs = _device_pts(self.index_points if index_points is None else index_points)
+        # (a FeatureScaled kernel: the strips below are assembled from the divided points)
+        Xo = _device_pts(scaled_points(self.kernel, X))
+        Xs = _device_pts(scaled_points(
+            self.kernel, self.index_points if index_points is None else index_points))
         n, P, B = int(Xo.shape[0]), int(Xs.shape[0]), self._B()
         # (the compact workspace: a small factorization must not cost more memory than the chunks)
         Minv, ldiag = self._factor_inverse(X, compact_ws=True)
@@ -533,9 +540,10 @@ class VariationalGaussianProcess(GaussianProcess):
         """(mean or None, variance) as [B, P], chunked: with V = K_*z Lz^-T and U = V (Lz^-1 A),
         var = amp^2 + pred_noise - rowsumsq(V) + rowsumsq(U), the diagonal of _predictive's
         K_** - V V^T + U^T U because A^T Kzz^-1 K_z* = (V Lz^-1 A)^T."""
-        Xs = _device_pts(self.index_points if index_points is None else index_points)
+        Xs = _device_pts(scaled_points(
+            self.kernel, self.index_points if index_points is None else index_points))
         Z = self._Z()
-        Zd = _device_pts(Z)
+        Zd = _device_pts(scaled_points(self.kernel, Z))
         B, P = self._B(), int(Xs.shape[0])
         loc, scale = self._loc_scale()
         M = scale.shape[-1]

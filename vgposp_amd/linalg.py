@@ -97,6 +97,20 @@ def kernel_matrix(kind, X1, X2=None, amp=1.0, ls=1.0, diag_shift=None, lower=Fal
     return out
 
 
+def scale_points(X, scale, out=None):
+    """out[i, k] = X[i, k] / scale[k] (vgposp_scale_points): the inputs of a FeatureScaled kernel.
+    ``X`` [n, d], ``scale`` a [d] device tensor; ``out`` may be X itself.  No host sync."""
+    X = as_device(X)
+    X = X[:, None] if X.dim() == 1 else X
+    n, d = X.shape
+    if scale.numel() != d:
+        raise ValueError(f"scale_diag has {scale.numel()} entries, the points have {d} features")
+    if out is None:
+        out = torch.empty_like(X)
+    call("vgposp_scale_points", _p(X), n, d, _p(scale), _p(out), _stream())
+    return out
+
+
 def kernel_matrix_matvec(kind, X1, X2, amp, ls, v, out_K, out_v):
     """out_K [n1, n2] <- K(X1, X2) (one amplitude / length scale) and out_v [n1] <- K v in one
     pass (vgposp_kernel_matrix_matvec: K is never re-read for the product)."""
@@ -375,4 +389,18 @@ def lml_grad(kind, X, amp, ls, Cinv, alpha):
     ws = workspace(query("vgposp_lml_grad_workspace_bytes", n, Bn))
     call("vgposp_lml_grad", kind_id(kind), _p(X), n, X.shape[1], _p(a), _p(l), _p(C3),
          C3.stride(1), C3.stride(0), _p(alpha), Bn, _p(grad), _p(ws), ws.numel(), _stream())
+    return grad
+
+
+def lml_grad_scaled(kind, Z, amp, ls, scale, Cinv, alpha):
+    """[3 + d] = dLML/d(amp, ls, noise, scale_diag) of one FeatureScaled kernel, given the scaled
+    points Z = X / scale, C^-1 [n, n] (lower triangle) and alpha = C^-1 y [n]."""
+    Z = as_device(Z)
+    Z = Z[:, None] if Z.dim() == 1 else Z
+    n, d = Z.shape
+    a, l = _vec(amp, 1), _vec(ls, 1)
+    grad = torch.empty(3 + d, dtype=F64, device=Z.device)
+    ws = workspace(query("vgposp_lml_grad_scaled_workspace_bytes", n))
+    call("vgposp_lml_grad_scaled", kind_id(kind), _p(Z), n, d, _p(a), _p(l), _p(scale), _p(Cinv),
+         Cinv.stride(-2), _p(alpha), _p(grad), _p(ws), ws.numel(), _stream())
     return grad

@@ -18,6 +18,7 @@ import torch
 
 from . import _lib, linalg
 from ._lib import call
+from .psd_kernels import FeatureScaled
 from .variables import Softplus, Variable, resolve
 
 
@@ -70,6 +71,8 @@ class GPTrainOp:
         k = self.gp.kernel
         self.views = {"amp": k.amplitude, "ls": k.length_scale,
                       "noise": self.gp.observation_noise_variance}
+        if isinstance(k, FeatureScaled):  # d more slots: the per-feature scales
+            self.views["scale"] = k.scale_diag
         self.trainable = [(name, v) for name, v in self.views.items()
                           if isinstance(v, Softplus) and v.var.trainable
                           and (var_list is None or v.var in var_list or v in var_list)]
@@ -90,9 +93,10 @@ class GPTrainOp:
 
     def run(self, observations=None):
         obs = self.observations if observations is None else observations
-        lml, ga, gl, gn = self.gp.log_prob_and_grads(obs)
+        lml, ga, gl, gn, *gscale = self.gp.log_prob_and_grads(obs)
         B = lml.numel()
-        for name, g in (("amp", ga), ("ls", gl), ("noise", gn)):
+        grads = [("amp", ga), ("ls", gl), ("noise", gn)] + [("scale", g) for g in gscale]
+        for name, g in grads:
             if name not in self.slices:
                 continue
             off, sz, sp = self.slices[name]
@@ -139,7 +143,11 @@ class VGPTrainOp:
     Scheduling switches (each measured, defaults = the faster setting): ``streams`` the VGP
     step's side-stream bitmask (``VGPObjective``), ``fused_params`` the softplus values in one
     launch and their chain rule inside the Adam launch, ``grouped`` one launch per dependency
-    level of M x M products."""
+    level of M x M products.
+
+    A ``FeatureScaled`` kernel trains its softplus ``scale_diag`` too: d more slots in the flat
+    buffer between the scalar parameters and Z, their chain rule as an elementwise launch (the
+    fused Adam launch takes at most 4 chain slots).  Single-GPU only."""
 
     def __init__(self, loss, opt, var_list=None, group=None, graph=True, precision="fp64",
                  streams=None, fused_params=True, grouped=True):
@@ -171,7 +179,14 @@ class VGPTrainOp:
                           if isinstance(p, Softplus) and chosen(p.var)]
         self.train_Z = isinstance(Z, Variable) and chosen(Z)
         self.Z = Z
-        n = len(self.trainable) + (Z.value.numel() if self.train_Z else 0)
+        self.scale = kernel.scale_diag if isinstance(kernel, FeatureScaled) else None
+        if self.scale is not None and group is not None:
+            raise NotImplementedError("data-parallel VGP training with a FeatureScaled kernel is "
+                                      "not supported")
+        self.train_scale = isinstance(self.scale, Softplus) and chosen(self.scale.var)
+        self.s_off = len(self.trainable)
+        self.z_off = self.s_off + (self.scale.var.value.numel() if self.train_scale else 0)
+        n = self.z_off + (Z.value.numel() if self.train_Z else 0)
         dev = linalg.device()
         self.theta = torch.zeros(max(n, 1), dtype=torch.float64, device=dev)
         self.grad = torch.zeros_like(self.theta)
@@ -182,7 +197,8 @@ class VGPTrainOp:
         for i, (k, p) in enumerate(self.trainable):
             p.var._rebind(self.theta[i:i + 1])
             self.slot[k] = i
-        self.z_off = len(self.trainable)
+        if self.train_scale:
+            self.scale.var._rebind(self.theta[self.s_off:self.z_off])
         if self.train_Z:
             Z._rebind(self.theta[self.z_off:])
         self.objective = VGPObjective(kernel.kind, spec["observation_index_points"],
@@ -220,8 +236,15 @@ class VGPTrainOp:
         else:
             vals = [self._value(self.params[k]) for k in names]
         zbar = self.grad[self.z_off:].view_as(Zv) if self.train_Z else None
-        loss, ga, gl, gn, gZ = self.objective.loss_and_grads(
-            Zv, *vals, Xb, yb, self.loss.kl_weight, infos=infos, zbar_out=zbar)
+        if self.scale is None:
+            loss, ga, gl, gn, gZ = self.objective.loss_and_grads(
+                Zv, *vals, Xb, yb, self.loss.kl_weight, infos=infos, zbar_out=zbar)
+        else:
+            sc = self.scale.value() if isinstance(self.scale, Softplus) else resolve(self.scale)
+            loss, ga, gl, gn, gZ, gsc = self.objective.loss_and_grads(
+                Zv, *vals, Xb, yb, self.loss.kl_weight, infos=infos, zbar_out=zbar, scale=sc)
+            if self.train_scale:
+                self.grad[self.s_off:self.z_off] = gsc * self.scale.dvalue_dvar().reshape(-1)
         chain = [(self.slot[k], g) for k, g in zip(names, (ga, gl, gn)) if k in self.slot]
         if not fused:  # the chain rule as elementwise launches (A/B reference)
             for i, g in chain:

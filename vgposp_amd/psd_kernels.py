@@ -99,3 +99,90 @@ class MaternThreeHalves(PositiveSemidefiniteKernel):
 
 class MaternFiveHalves(PositiveSemidefiniteKernel):
     kind = "matern52"
+
+
+MAX_FEATURES = 8  # the d <= 8 of every libvgposp assembly kernel
+
+
+class FeatureScaled(PositiveSemidefiniteKernel):
+    """``tfkern.FeatureScaled(kernel, scale_diag)``: per-feature (ARD) length scales,
+
+        k(x1, x2) = kernel(x1 / scale_diag, x2 / scale_diag).
+
+    The base kernel keeps its own amplitude and length_scale.  ``scale_diag`` [d] is an array, a
+    device tensor or a trainable ``variables.Softplus``.  The points are divided once
+    (``scaled``, libvgposp ``vgposp_scale_points``) and every assembly kernel of the base then
+    evaluates the scaled kernel.  One (non-batched) base kernel and one scale vector only."""
+
+    def __init__(self, kernel, scale_diag, validate_args=False, name=None):
+        if isinstance(kernel, FeatureScaled):
+            raise NotImplementedError("a FeatureScaled inside a FeatureScaled is not supported: "
+                                      "multiply the two scale_diag vectors instead")
+        if kernel.batch_shape != () or kernel.batch_size != 1:
+            raise NotImplementedError("FeatureScaled needs one (non-batched) base kernel")
+        shape = tuple(scale_diag.shape) if hasattr(scale_diag, "shape") else np.shape(scale_diag)
+        if len(shape) != 1:
+            raise ValueError(f"scale_diag must have shape [d] (batched scales are not supported), "
+                             f"got {shape}")
+        if not 1 <= shape[0] <= MAX_FEATURES:
+            raise ValueError(f"scale_diag has {shape[0]} entries; 1 to {MAX_FEATURES} features are "
+                             "supported")
+        self.kernel = kernel
+        self.scale_diag = scale_diag
+        self.num_features = int(shape[0])
+        self.feature_ndims = kernel.feature_ndims
+        self.validate_args = validate_args
+        self.name = name or type(self).__name__
+        if validate_args and not hasattr(scale_diag, "value"):
+            host = scale_diag.detach().cpu().numpy() if isinstance(scale_diag, torch.Tensor) \
+                else np.asarray(scale_diag, dtype=np.float64)
+            if not (host > 0).all():
+                raise ValueError("scale_diag must be positive")
+
+    # -- the base kernel's parameters -----------------------------------------------------------
+    @property
+    def kind(self):
+        return self.kernel.kind
+
+    @property
+    def amplitude(self):
+        return self.kernel.amplitude
+
+    @property
+    def length_scale(self):
+        return self.kernel.length_scale
+
+    def params(self):
+        return self.kernel.params()
+
+    def scale(self):
+        """Current scale_diag as a [d] float64 device tensor."""
+        s = resolve(self.scale_diag)
+        if self.validate_args and not bool((s > 0).all()):
+            raise ValueError("scale_diag must be positive")
+        return s
+
+    # -- evaluation -----------------------------------------------------------------------------
+    def scaled(self, x):
+        """x / scale_diag as a [n, d] device tensor."""
+        x = _pts(x if hasattr(x, "shape") else np.asarray(x, dtype=np.float64))
+        d = 1 if len(x.shape) == 1 else int(x.shape[-1])
+        if d != self.num_features:
+            raise ValueError(f"scale_diag has {self.num_features} entries, the index points have "
+                             f"{d} features")
+        return linalg.scale_points(x, self.scale())
+
+    def matrix(self, x1, x2, diag_shift=None, lower=False, keep_batch=None):
+        z1 = self.scaled(x1)
+        z2 = z1 if x2 is x1 else self.scaled(x2)
+        return self.kernel.matrix(z1, z2, diag_shift=diag_shift, lower=lower,
+                                  keep_batch=keep_batch)
+
+    def __repr__(self):
+        return f"{self.name}({self.kernel!r}, scale_diag={self.scale_diag!r})"
+
+
+def scaled_points(kernel, x):
+    """The points a kernel's assembly sees: ``x / scale_diag`` for a FeatureScaled kernel, ``x``
+    itself otherwise.  For call sites that assemble through ``linalg`` with ``kernel.kind``."""
+    return kernel.scaled(x) if isinstance(kernel, FeatureScaled) else x

@@ -36,17 +36,29 @@ from . import linalg
 from ._lib import call, query
 from .linalg import F64, _p, _stream, kind_id
 
-def kernel_vjp(kind, X1, X2, amp, ls, Kbar, u=None, w=None, want_x1bar=True):
+def kernel_vjp(kind, X1, X2, amp, ls, Kbar, u=None, w=None, want_x1bar=True, scale=None):
     """(grad[2] = (d/damp, d/dls), X1bar [n1, d] or None) of sum(Kbar * K(X1, X2))
-    (+ the rank-1 term u w^T added to Kbar)."""
+    (+ the rank-1 term u w^T added to Kbar).
+
+    ``scale`` (a [d] device tensor): the FeatureScaled kernel.  X1 and X2 are then the points
+    ALREADY divided by it (``linalg.scale_points``), grad is [2 + d] with d/dscale_diag after the
+    two, and X1bar is with respect to the undivided X1 (vgposp_kernel_vjp_scaled, one pass)."""
     X1, X2 = linalg.as_device(X1), linalg.as_device(X2)
     X1 = X1[:, None] if X1.dim() == 1 else X1
     X2 = X2[:, None] if X2.dim() == 1 else X2
     n1, d = X1.shape
     n2 = X2.shape[0]
     a, l = linalg._vec(amp), linalg._vec(ls)
-    grad = torch.empty(2, dtype=F64, device=X1.device)
+    grad = torch.empty(2 if scale is None else 2 + d, dtype=F64, device=X1.device)
     X1bar = torch.empty((n1, d), dtype=F64, device=X1.device) if want_x1bar else None
+    if scale is not None:
+        if scale.numel() != d:
+            raise ValueError(f"scale has {scale.numel()} entries, the points have {d} features")
+        ws = linalg.workspace(query("vgposp_kernel_vjp_scaled_workspace_bytes", n1, n2, d))
+        call("vgposp_kernel_vjp_scaled", kind_id(kind), _p(X1), n1, _p(X2), n2, d, _p(a), _p(l),
+             _p(scale), _p(Kbar), Kbar.stride(0), _p(u), _p(w), _p(grad), _p(X1bar), _p(ws),
+             ws.numel(), _stream())
+        return grad, X1bar
     ws = linalg.workspace(query("vgposp_kernel_vjp_workspace_bytes", n1, n2, d))
     call("vgposp_kernel_vjp", kind_id(kind), _p(X1), n1, _p(X2), n2, d, _p(a), _p(l), _p(Kbar),
          Kbar.stride(0), _p(u), _p(w), _p(grad), _p(X1bar), _p(ws), ws.numel(), _stream())
@@ -125,6 +137,11 @@ class VGPObjective:
     likelihood variance) and ``posterior_jitter`` that of optimal_variational_posterior.  The KL
     prior is N(0, Kzz + (noise + 1e-6) I): TFP's inducing-point GaussianProcess with its default
     jitter.
+
+    ``scale`` (``loss_and_grads`` / ``optimal_posterior``; a [d] device tensor, a value like amp):
+    the kernel is FeatureScaled(kind, scale).  X, Xb and Z are divided by it inside the step (it
+    changes every step), all three kernel VJPs run the scaled entry, and ``loss_and_grads`` returns
+    a sixth value d/dscale [d]; d/dZ stays in undivided coordinates.
     """
 
     def __init__(self, kind, X, y, jitter=1e-6, posterior_jitter=1e-6, trace_adjoint=False,
@@ -152,6 +169,7 @@ class VGPObjective:
         self.trace_adjoint = bool(trace_adjoint)
         self.group = group
         self._Kzx = None
+        self._Xs = None  # X / scale of the current step (FeatureScaled kernels)
         self._side = None
         self._tail = None  # side stream of the step (Kzb, the vector chain, VJPs, reductions)
         self._capture_hook = None  # set by VGPTrainOp while capturing a data-parallel step
@@ -187,20 +205,33 @@ class VGPObjective:
             dist.all_reduce(t, group=self.group)
         return t
 
-    def _kzx(self, Z, a, l, c):
+    def _kzx(self, Z, a, l, c, X):
         """Kzx = K(Z, X) [M, N] and c <- Kzx y in one pass over Kzx."""
-        M, N = Z.shape[0], self.X.shape[0]
+        M, N = Z.shape[0], X.shape[0]
         if self._Kzx is None or self._Kzx.shape != (M, N):
-            self._Kzx = torch.empty((M, N), dtype=F64, device=self.X.device)
-        linalg.kernel_matrix_matvec(self.kind, Z, self.X, a, l, self.y, self._Kzx, c)
+            self._Kzx = torch.empty((M, N), dtype=F64, device=X.device)
+        linalg.kernel_matrix_matvec(self.kind, Z, X, a, l, self.y, self._Kzx, c)
         return self._Kzx
 
-    def optimal_posterior(self, Z, amp, ls, noise):
+    def _scaled(self, scale, *pts):
+        """The observations and ``pts`` divided by ``scale`` (the observations into a buffer kept
+        across steps); everything as it is without a scale."""
+        if scale is None:
+            return (self.X,) + pts
+        if self.group is not None:
+            raise NotImplementedError("data-parallel VGP training with a FeatureScaled kernel")
+        if self._Xs is None:
+            self._Xs = torch.empty_like(self.X)
+        return (linalg.scale_points(self.X, scale, out=self._Xs),) + tuple(
+            linalg.scale_points(p, scale) for p in pts)
+
+    def optimal_posterior(self, Z, amp, ls, noise, scale=None):
         """(loc [M], scale [M, M]) of optimal_variational_posterior over all shards."""
         Z = linalg.as_device(Z)
         Z = Z[:, None] if Z.dim() == 1 else Z
         a, l, s = (linalg.as_device(v).reshape(()) for v in (amp, ls, noise))
-        st = self._forward_posterior(Z, a, l, s)
+        X, Z = self._scaled(None if scale is None else linalg.as_device(scale).reshape(-1), Z)
+        st = self._forward_posterior(Z, a, l, s, X=X)
         return st["m"], st["A"]
 
     def _kzz_factors(self, Kzz, s, infos, fork):
@@ -237,7 +268,7 @@ class VGPObjective:
             t.record_stream(main)
         return out, self._side
 
-    def _forward_posterior(self, Z, a, l, s, infos=None, side=False):
+    def _forward_posterior(self, Z, a, l, s, infos=None, side=False, X=None):
         """The optimal posterior's pieces.  side=True (the training step) also forms the three
         Kzz-only inverse factors: fp64 as ONE batched Cholesky + inverse of [Sinv, Kzz + jI,
         Kzz + (s + 1e-6) I, Kzz] after the SYRK (every launch of the recursion covers the four,
@@ -253,7 +284,7 @@ class VGPObjective:
         red = torch.empty(M * M + M, dtype=F64, device=Z.device)
         P0 = red[:M * M].view(M, M)
         c = red[M * M:].view(M, 1)
-        Kzx = self._kzx(Z, a, l, c)  # c = Kzx y fused into the assembly
+        Kzx = self._kzx(Z, a, l, c, self.X if X is None else X)  # c = Kzx y fused in
         linalg.gemm(Kzx, Kzx, P0, transb=True, lower_c=True, splitk=True)
         fac = self._kzz_factors(Kzz, s, infos, fork) if fork is not None else None
         self._allreduce(red)
@@ -287,9 +318,9 @@ class VGPObjective:
         return st
 
     def loss_and_grads(self, Z, amp, ls, noise, Xb, yb, kl_weight, want_grads=True, infos=None,
-                       zbar_out=None):
+                       zbar_out=None, scale=None):
         """-> (loss, d/damp, d/dls, d/dnoise, d/dZ [M, d]) as 0-d / [M, d] device tensors
-        (d/dZ written into ``zbar_out`` when given).
+        (d/dZ written into ``zbar_out`` when given); with ``scale`` also d/dscale [d].
 
         No host synchronisation unless ``infos`` is None: with a list, the device Cholesky
         statuses are appended for the caller to check (the graph-captured training step)."""
@@ -299,6 +330,10 @@ class VGPObjective:
         Xb = Xb[:, None] if Xb.dim() == 1 else Xb
         yb = linalg.as_device(yb).reshape(-1)
         a, l, s = (linalg.as_device(v).reshape(()) for v in (amp, ls, noise))
+        sc = None if scale is None else linalg.as_device(scale).reshape(-1)
+        # from here on Z, Xb and X are what the base kernel sees (divided by a FeatureScaled
+        # kernel's scale); the scaled VJP entry takes X1bar back to undivided coordinates
+        X, Z, Xb = self._scaled(sc, Z, Xb)
         j, w = self.j, float(kl_weight)
         M, nb = Z.shape[0], yb.numel()
         check = infos is None
@@ -320,7 +355,7 @@ class VGPObjective:
         with torch.cuda.stream(tail):
             Kzb = linalg.kernel_matrix(self.kind, Z, Xb, a, l)[0]
         Kzb.record_stream(main)
-        st = self._forward_posterior(Z, a, l, s, infos, side=True)
+        st = self._forward_posterior(Z, a, l, s, infos, side=True, X=X)
         Kzz, Kzx, P0, c, Li, t, m, A = (st[k] for k in
                                         ("Kzz", "Kzx", "P0", "c", "Li", "t", "m", "A"))
         _wait(main, tail)
@@ -381,7 +416,7 @@ class VGPObjective:
             if check:
                 for info in infos:
                     linalg.check_info(info)
-            return out[0], None, None, None, None
+            return (out[0], None, None, None, None) + (() if sc is None else (None,))
         P, QAQA = rest
         # ---- reverse pass (d E) ----
         # dE/dR = -R / s gives A_b = -(1/s) A HHt (HHt A for trace_adjoint) and H_b = -(1/s) Q H;
@@ -412,8 +447,8 @@ class VGPObjective:
         # was made on the main stream before the fork and stays referenced until the join.
         _wait(tail, main)
         with torch.cuda.stream(tail):
-            g1, Zb1 = kernel_vjp(self.kind, Z, Z, a, l, KzzS)
-            g3, Zb3 = kernel_vjp(self.kind, Z, Xb, a, l, Kzb_b, v, mu_b)
+            g1, Zb1 = kernel_vjp(self.kind, Z, Z, a, l, KzzS, scale=sc)
+            g3, Zb3 = kernel_vjp(self.kind, Z, Xb, a, l, Kzb_b, v, mu_b, scale=sc)
             rev = [(Kp_inv, M + 1, None, 0, M, 0), (qv, 1, qv, 1, M, 0),
                    (QAQA, M + 1, None, 0, M, 0), (m_b, 1, m, 1, M, 0), (G, 1, P0, 1, M * M, 0)]
             _dots(fwd + rev, sums)
@@ -421,7 +456,7 @@ class VGPObjective:
         # whose epilogue reduced each tile straight into the VJP partials (Kzx_bar never written)
         # was measured slower: 2.92 ms against 2.30 + 0.43 ms for the two passes
         Kzx_b = linalg.gemm(G, Kzx)
-        g2, Zb2 = kernel_vjp(self.kind, Z, self.X, a, l, Kzx_b, c_b, self.y)
+        g2, Zb2 = kernel_vjp(self.kind, Z, X, a, l, Kzx_b, c_b, self.y, scale=sc)
         if self.group is not None:
             red = torch.cat([g2, Zb2.reshape(-1)])
             self._allreduce(red)
@@ -434,7 +469,11 @@ class VGPObjective:
         if check:
             for info in infos:
                 linalg.check_info(info)
-        return out[0], out[1], out[2], out[3], Z_b
+        if sc is None:
+            return out[0], out[1], out[2], out[3], Z_b
+        # (g1 is of the symmetrised Kzz adjoint, hence the half, as for amp and ls)
+        gscale = _lincomb([(g1[2:], -0.5, 0), (g2[2:], -1.0, 0), (g3[2:], -1.0, 0)])
+        return out[0], out[1], out[2], out[3], Z_b, gscale
 
 
 __all__ = ["VGPObjective", "kernel_vjp"]

@@ -63,12 +63,14 @@ def c4_grid(n=128, seed=0):
 
 
 def vgp_c3_graph(X, y, Z, B, lr=0.01, precision="fp64", group=None, n_total=None, kernel="eq",
-                 **train_options):
+                 scale_diag=None, **train_options):
     """The reference's training graph (variational_Gaussian_process_example.py:51-102) in this
     package's API -> (train_op, loss, x_batch placeholder, y_batch placeholder).  ``group``: the
     observations (X, y) are this rank's shard of ``n_total`` (data-parallel optimal posterior,
     two all-reduces per step); every rank feeds the same minibatch.  ``train_options``: the
-    VGPTrainOp scheduling switches (graph, streams, fused_params, grouped)."""
+    VGPTrainOp scheduling switches (graph, streams, fused_params, grouped).  ``scale_diag`` [d]:
+    the kernel becomes FeatureScaled with these initial per-feature scales, trained as softplus
+    variables with the rest."""
     from . import distributions as tfd
     from . import psd_kernels as tfkern
     from .optimizers import AdamOptimizer
@@ -80,6 +82,10 @@ def vgp_c3_graph(X, y, Z, B, lr=0.01, precision="fp64", group=None, n_total=None
     cls = {"eq": tfkern.ExponentiatedQuadratic, "matern52": tfkern.MaternFiveHalves,
            "matern32": tfkern.MaternThreeHalves, "matern12": tfkern.MaternOneHalf}[kernel]
     kernel = cls(amplitude=amp, length_scale=ls)
+    if scale_diag is not None:
+        init = np.log(np.expm1(np.asarray(scale_diag, dtype=np.float64)))
+        kernel = tfkern.FeatureScaled(kernel, Softplus(Variable(init, name="scale_diag"),
+                                                       offset=0.0))
     noise = Softplus(Variable(0.54, name="observation_noise_variance"), offset=0.0)
     Zv = Variable(Z, name="inducing_index_points")
     loc, scale = tfd.VariationalGaussianProcess.optimal_variational_posterior(
