@@ -494,6 +494,36 @@ int vgposp_greedy_condition(const double* Sigma, int64_t n, int64_t lda, int kma
                             int batch, const int64_t* placed, int64_t* selected, void* ws,
                             size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Speculative mat-vec of vgposp_greedy_step.  q_a = M^T (M e_a) depends on M = L^-1 and a alone,
+ * so a pass over L^-1 can carry, beside the pick's column, the columns the next rounds will
+ * probably ask for, and a round whose pick is already cached reads nothing of L^-1.
+ *   vgposp_greedy_set_speculation(width)  process-wide; width 1, 2, 4 or 8 columns per pass
+ *        (anything else: -1).  Width 1 makes exactly the launches of a library without the
+ *        feature.  vgposp_greedy_speculation() returns the current width.
+ *   The guarantee: every output of every round (selected, sel_delta, evals, and the whole state
+ *        in the workspace) is bit for bit the same at every width.  The multi-column kernel and
+ *        the single-column one compile from one source of the row loop, a cached column is summed
+ *        in the order the update would sum it, and the prediction (the largest fresh deltas of
+ *        the previous round among the unselected, unmasked, not yet cached candidates) decides
+ *        speed only.  Everything is decided on the device: a round is the same launch sequence
+ *        on a hit and on a miss, with no synchronisation, so the rounds stay capturable.
+ *   Only vgposp_greedy_step at rounds >= 1 speculates; vgposp_greedy_update(_ex), _extract, the
+ *        slab entry points and vgposp_greedy_condition are as before.  vgposp_greedy_init(_ex),
+ *        _prepare, _init_slab and _finish_slab clear the cache; vgposp_greedy_workspace_bytes is
+ *        sized for width 8 whatever the current width.
+ *   vgposp_greedy_spec_stats  reads the counters of the workspace's current run (synchronous copy;
+ *        call it after the stream has been synchronised): passes over L^-1 made by speculating
+ *        rounds, rounds served from the cache, columns cached.  Each pointer may be NULL.
+ *   vgposp_greedy_spec_table  device pointers of the table: column[s] is the candidate whose q
+ *        sits in slot s, fill_round[s] the round whose pass formed it (s < cached); *slots is
+ *        the capacity (4 kmax; a full table ends the speculation, nothing is evicted). */
+int vgposp_greedy_set_speculation(int width);
+int vgposp_greedy_speculation(void);
+int vgposp_greedy_spec_stats(void* ws, int64_t n, int kmax, int64_t* passes, int64_t* hits,
+                             int64_t* cached);
+int vgposp_greedy_spec_table(void* ws, int64_t n, int kmax, int64_t** column,
+                             int64_t** fill_round, int64_t* slots);
+
 /* Placement algorithm 3, the local-kernel greedy (snippets_a3.sparse_placement_algorithm_3,
  * snippets_a3.py:43-330; with vgposp_greedy_init_ex(..., 1e-6, 1e-7, 1e8, ...) as its tf_nominator
  * constants).  Per round, after vgposp_greedy_update(round): round 0 scores every candidate into

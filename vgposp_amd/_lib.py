@@ -145,6 +145,12 @@ SIGNATURES = {
     "vgposp_greedy_condition_workspace_bytes": (_size, [_i64, _i32]),
     "vgposp_greedy_condition": (_i32, [_c_void_p, _i64, _i64, _i32, _i32, _i32, _i32, _c_void_p,
                                        _c_void_p, _c_void_p, _size, _c_void_p, _size, _c_void_p]),
+    "vgposp_greedy_set_speculation": (_i32, [_i32]),
+    "vgposp_greedy_speculation": (_i32, []),
+    "vgposp_greedy_spec_stats": (_i32, [_c_void_p, _i64, _i32, ctypes.POINTER(_i64),
+                                        ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "vgposp_greedy_spec_table": (_i32, [_c_void_p, _i64, _i32, ctypes.POINTER(_c_void_p),
+                                        ctypes.POINTER(_c_void_p), ctypes.POINTER(_i64)]),
     "vgposp_greedy_select_window": (_i32, [_i64, _i32, _i32, _i64, _i64, _i64, _i32, _i64, _i64,
                                            _c_void_p, _c_void_p, _c_void_p, _c_void_p, _size,
                                            _c_void_p]),

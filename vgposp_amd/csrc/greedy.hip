@@ -16,6 +16,7 @@
 // all of them before it could stop), and the remaining re-score loop runs in one workgroup over
 // per-chunk maxima.  Keys order by value, ties by LOWER index (argmax_cache_linear, :53-67).
 #include <algorithm>
+#include <atomic>
 #include <cfloat>
 
 #include "dense.h"
@@ -28,6 +29,18 @@ constexpr int CH = 1024;    // candidates per chunk / per update workgroup
 constexpr int MAXCH = 2048; // chunks held in LDS by the select kernel -> n <= 2^21
 constexpr double DELTA_EPS = 1e-8;  // placement_algorithm2.py:198
 
+// Speculative mat-vec of vgposp_greedy_step (vgposp_greedy_set_speculation): a pass over L^-1
+// forms q_a for the pick and for up to width - 1 columns the next rounds will probably ask for;
+// q_c = M^T (M e_c) depends on M and c alone, so a cached column serves any later round.
+constexpr int SPEC_TMAX = 8;   // largest width; the workspace is sized for it
+constexpr int SPEC_HDR = 32;   // int64 words ahead of the table
+// header words (device memory, written by greedy_spec_plan_kernel only)
+enum { H_COUNT = 0, H_PASSES = 1, H_HITS = 2, H_HIT = 3, H_SLOT = 4, H_NB = 5, H_COL = 6,
+       H_CSLOT = H_COL + SPEC_TMAX };
+static_assert(H_CSLOT + SPEC_TMAX <= SPEC_HDR, "header words");
+static int64_t spec_slots(int kmax) { return 4 * (int64_t)kmax; }
+static std::atomic<int> g_spec_width{8};
+
 // Variant parameters, written by vgposp_greedy_init_ex into the workspace (device memory) so the
 // per-round entry points keep their signatures:
 //   prm[0] jitter  eps added to the diagonal of Sigma_AA and Sigma_AbarAbar (0 for
@@ -38,7 +51,14 @@ struct GreedyWS {
   double *prm, *sdiag, *nom, *prec, *delta, *cache, *W, *V, *part, *xcol, *piv, *fval, *cval;
   long long *fidx, *cidx, *cnt;
   unsigned char *fresh, *selmask;
-  size_t bytes;
+  // speculation: partial slices of columns 1 .. SPEC_TMAX-1 of a pass (slice 0 is `part`), the
+  // row-interleaved right-hand sides, the cached columns q_c (these three overlay the
+  // factorization scratch), and header + table (cached index and fill round per slot) followed
+  // by one "is cached" byte per candidate
+  double *spart, *X, *qc;
+  long long* spec;
+  unsigned char* cmask;
+  size_t fact_off, bytes;
 };
 
 static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -71,13 +91,22 @@ static GreedyWS greedy_layout(void* base, int64_t n, int kmax) {
   w.cnt = (long long*)take(8 * 8);
   w.fresh = (unsigned char*)take(n);
   w.selmask = (unsigned char*)take(n);
-  (void)take(potrf_ws_bytes(n));  // factorization scratch (last)
+  const int64_t slots = spec_slots(kmax);
+  w.spec = (long long*)take((size_t)(SPEC_HDR + 2 * slots) * 8 + n);
+  w.cmask = (unsigned char*)(p ? (char*)(w.spec + SPEC_HDR + 2 * slots) : nullptr);
+  // factorization scratch (last).  The rounds come after the factorization, so the large areas of
+  // the speculation live in the same bytes: the workspace grows by the table alone.
+  w.fact_off = off;
+  w.spart = (double*)take((size_t)(SPEC_TMAX - 1) * nrc * n * 8);
+  w.X = (double*)take((size_t)SPEC_TMAX * n * 8);
+  w.qc = (double*)take((size_t)slots * n * 8);
+  off = w.fact_off + std::max(off - w.fact_off, align_up(potrf_ws_bytes(n)));
   w.bytes = off;
   return w;
 }
 
-static void* greedy_fact_ws(void* base, const GreedyWS& w, int64_t n) {
-  return static_cast<char*>(base) + w.bytes - align_up(potrf_ws_bytes(n));
+static void* greedy_fact_ws(void* base, const GreedyWS& w, int64_t) {
+  return static_cast<char*>(base) + w.fact_off;
 }
 
 // Block-wide (value, index) arg-max for blockDim == 1024.  Result valid in all threads.
@@ -110,7 +139,9 @@ __global__ void greedy_init_kernel(double* S, int64_t n, int64_t lda, double jit
     if (jitter != 0.0) S[i * lda + i] = d + jitter;
     w.cache[i] = cinit;
     w.selmask[i] = 0;
+    w.cmask[i] = 0;
   }
+  if (i < SPEC_HDR) w.spec[i] = 0;  // no column of the previous M survives
   if (i < 8) w.cnt[i] = 0;
   if (i == 0) {
     w.prm[0] = jitter;
@@ -138,29 +169,31 @@ __global__ void greedy_extract_kernel(const double* M, int64_t n, int64_t lda,
 // per round), four rows in flight; the pair's diagonal row contributes to its first column only.
 constexpr int TRMV_COLS = 2 * CT;  // columns per workgroup
 
-template <bool SQ>
-__device__ __forceinline__ double trmv_f(double m, const double* xcol, int64_t r) {
-  return SQ ? m * m : m * xcol[r];
+// f for right-hand side j; the NR values of row r sit XS doubles apart from the next row's.
+template <bool SQ, int XS>
+__device__ __forceinline__ double trmv_f(double m, const double* x, int64_t r, int j) {
+  return SQ ? m * m : m * x[r * XS + j];
 }
 
-template <bool SQ>
-__global__ __launch_bounds__(CT) void greedy_trmv_kernel(const double* M, int64_t n, int64_t lda,
-                                                         const int64_t* selected, int round,
-                                                         const double* xcol, double* part,
-                                                         int64_t cbeg, int64_t cend, int vec) {
+// The row loop of the mat-vec kernels: rows [r, r1) of the column pair (c, c + 1) against NR
+// right-hand sides, sc[j] / tc[j] = the sums of column c / c + 1.  Per right-hand side the order
+// is fixed: the diagonal element alone into s0, then groups of four rows from the origin r
+// (s0 += f(r) + f(r+2), s1 += f(r+1) + f(r+3)), the tail rows into s0, result s0 + s1.  Every
+// kernel that must agree bit for bit on a column instantiates this one source.  UNI: the caller
+// guarantees c + 1 < r (a tile below the diagonal) and a workgroup-uniform r, so the x values are
+// scalar loads.
+template <bool SQ, int NR, int XS, bool UNI>
+__device__ __forceinline__ void trmv_rows(const double* M, int64_t n, int64_t lda, int64_t c,
+                                          int64_t r, int64_t r1, const double* x, int vec,
+                                          double (&sc)[NR], double (&tc)[NR]) {
   typedef double d2v __attribute__((ext_vector_type(2)));
-  const int64_t cb = (cbeg & ~(int64_t)1) + (int64_t)blockIdx.x * TRMV_COLS;
-  const int64_t r0 = (int64_t)blockIdx.y * RC;
-  const int64_t r1 = min(r0 + RC, n);
-  if (cb >= r1) return;  // tile strictly above the diagonal: never read by the reducer
-  const int64_t a = SQ ? 0 : selected[round - 1];
-  const int64_t c = cb + 2 * threadIdx.x;
-  if (c >= cend) return;
-  const bool two = c + 1 < cend;
-  double s0 = 0.0, s1 = 0.0, t0 = 0.0, t1 = 0.0;  // column c: s, column c + 1: t
-  int64_t r = max(max(r0, a), c);
-  if (r == c && r < r1) {  // diagonal of column c; (c, c + 1) is above the diagonal
-    s0 += trmv_f<SQ>(M[r * lda + c], xcol, r);
+  double s0[NR], s1[NR], t0[NR], t1[NR];  // column c: s, column c + 1: t
+#pragma unroll
+  for (int j = 0; j < NR; ++j) s0[j] = s1[j] = t0[j] = t1[j] = 0.0;
+  if (!UNI && r == c && r < r1) {  // diagonal of column c; (c, c + 1) is above the diagonal
+    const double m = M[r * lda + c];
+#pragma unroll
+    for (int j = 0; j < NR; ++j) s0[j] += trmv_f<SQ, XS>(m, x, r, j);
     ++r;
   }
   const double* p = M + r * lda + c;
@@ -170,24 +203,227 @@ __global__ __launch_bounds__(CT) void greedy_trmv_kernel(const double* M, int64_
       const d2v m1 = __builtin_nontemporal_load(reinterpret_cast<const d2v*>(p + lda));
       const d2v m2 = __builtin_nontemporal_load(reinterpret_cast<const d2v*>(p + 2 * lda));
       const d2v m3 = __builtin_nontemporal_load(reinterpret_cast<const d2v*>(p + 3 * lda));
-      s0 += trmv_f<SQ>(m0.x, xcol, r) + trmv_f<SQ>(m2.x, xcol, r + 2);
-      s1 += trmv_f<SQ>(m1.x, xcol, r + 1) + trmv_f<SQ>(m3.x, xcol, r + 3);
-      t0 += trmv_f<SQ>(m0.y, xcol, r) + trmv_f<SQ>(m2.y, xcol, r + 2);
-      t1 += trmv_f<SQ>(m1.y, xcol, r + 1) + trmv_f<SQ>(m3.y, xcol, r + 3);
+#pragma unroll
+      for (int j = 0; j < NR; ++j) {
+        s0[j] += trmv_f<SQ, XS>(m0.x, x, r, j) + trmv_f<SQ, XS>(m2.x, x, r + 2, j);
+        s1[j] += trmv_f<SQ, XS>(m1.x, x, r + 1, j) + trmv_f<SQ, XS>(m3.x, x, r + 3, j);
+        t0[j] += trmv_f<SQ, XS>(m0.y, x, r, j) + trmv_f<SQ, XS>(m2.y, x, r + 2, j);
+        t1[j] += trmv_f<SQ, XS>(m1.y, x, r + 1, j) + trmv_f<SQ, XS>(m3.y, x, r + 3, j);
+      }
     }
     for (; r < r1; ++r, p += lda) {
       const d2v m0 = *reinterpret_cast<const d2v*>(p);
-      s0 += trmv_f<SQ>(m0.x, xcol, r);
-      t0 += trmv_f<SQ>(m0.y, xcol, r);
+#pragma unroll
+      for (int j = 0; j < NR; ++j) {
+        s0[j] += trmv_f<SQ, XS>(m0.x, x, r, j);
+        t0[j] += trmv_f<SQ, XS>(m0.y, x, r, j);
+      }
     }
   } else {
     for (; r < r1; ++r, p += lda) {
-      s0 += trmv_f<SQ>(p[0], xcol, r);
-      if (c + 1 < n) t0 += trmv_f<SQ>(p[1], xcol, r);
+#pragma unroll
+      for (int j = 0; j < NR; ++j) {
+        s0[j] += trmv_f<SQ, XS>(p[0], x, r, j);
+        if (c + 1 < n) t0[j] += trmv_f<SQ, XS>(p[1], x, r, j);
+      }
     }
   }
-  if (c >= cbeg) part[blockIdx.y * n + c] = s0 + s1;
-  if (two) part[blockIdx.y * n + c + 1] = t0 + t1;
+#pragma unroll
+  for (int j = 0; j < NR; ++j) {
+    sc[j] = s0[j] + s1[j];
+    tc[j] = t0[j] + t1[j];
+  }
+}
+
+template <bool SQ>
+__global__ __launch_bounds__(CT) void greedy_trmv_kernel(const double* M, int64_t n, int64_t lda,
+                                                         const int64_t* selected, int round,
+                                                         const double* xcol, double* part,
+                                                         int64_t cbeg, int64_t cend, int vec) {
+  const int64_t cb = (cbeg & ~(int64_t)1) + (int64_t)blockIdx.x * TRMV_COLS;
+  const int64_t r0 = (int64_t)blockIdx.y * RC;
+  const int64_t r1 = min(r0 + RC, n);
+  if (cb >= r1) return;  // tile strictly above the diagonal: never read by the reducer
+  const int64_t a = SQ ? 0 : selected[round - 1];
+  const int64_t c = cb + 2 * threadIdx.x;
+  if (c >= cend) return;
+  const bool two = c + 1 < cend;
+  double s[1], t[1];
+  trmv_rows<SQ, 1, 1, false>(M, n, lda, c, max(max(r0, a), c), r1, xcol, vec, s, t);
+  if (c >= cbeg) part[blockIdx.y * n + c] = s[0];
+  if (two) part[blockIdx.y * n + c + 1] = t[0];
+}
+
+// greedy_trmv_kernel<false> for the up to T columns of a speculative pass (header words H_COL:
+// the pick first, n for an unused entry), right-hand sides row-interleaved in X.  Column j's
+// partials are bit for bit what the classic kernel writes for a = col[j]: its origin in row chunk
+// [r0, r1) is max(r0, col[j], c), which depends on col[j] only in the chunk that holds it.  Every
+// chunk runs the T-wide loop once with the shared origin max(r0, c) (r0, uniform, with scalar x
+// below the diagonal tile); that is the result of every column above the chunk (X is zero above
+// col[j]; a column's chunks above its own are never read by the reducers and not written).  A
+// column whose col[j] lies inside the chunk then runs the single-column loop with its own origin:
+// one partial re-read of a 512-row band per column and pass.  Nothing runs on a hit.  Slice 0
+// is `part0` (the classic partials), slice j > 0 is spart[j - 1].
+template <int T>
+__global__ __launch_bounds__(CT) void greedy_trmv_spec_kernel(
+    const double* __restrict__ M, int64_t n, int64_t lda, const long long* __restrict__ h,
+    const double* __restrict__ X, double* __restrict__ part0, double* __restrict__ spart,
+    int vec) {
+  const int64_t cb = (int64_t)blockIdx.x * TRMV_COLS;
+  const int64_t r0 = (int64_t)blockIdx.y * RC;
+  const int64_t r1 = min(r0 + RC, n);
+  if (cb >= r1) return;  // tile strictly above the diagonal: never read by the reducers
+  if (h[H_HIT]) return;
+  int64_t col[T], amin = n;
+  bool own = false;  // some col[j] lies in this row chunk
+#pragma unroll
+  for (int j = 0; j < T; ++j) {
+    col[j] = h[H_COL + j];
+    amin = min(amin, col[j]);
+    own = own || (col[j] >= r0 && col[j] < r1);
+  }
+  if (amin >= r1) return;  // rows above every column: no reducer starts here
+  const int64_t c = cb + 2 * threadIdx.x;
+  if (c >= n) return;
+  const bool two = c + 1 < n;
+  const bool below = blockIdx.x < blockIdx.y;  // every column of the tile is left of row r0
+  const int64_t slice = ((n + RC - 1) / RC) * n;
+  auto out = [&](int j) {
+    return (j == 0 ? part0 : spart + (int64_t)(j - 1) * slice) + blockIdx.y * n + c;
+  };
+  {
+    double s[T], t[T];
+    if (below)
+      trmv_rows<false, T, T, true>(M, n, lda, c, r0, r1, X, vec, s, t);
+    else
+      trmv_rows<false, T, T, false>(M, n, lda, c, max(r0, c), r1, X, vec, s, t);
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+      if (col[j] < r0) {
+        double* o = out(j);
+        o[0] = s[j];
+        if (two) o[1] = t[j];
+      }
+    }
+  }
+  if (own) {
+#pragma unroll 1
+    for (int j = 0; j < T; ++j) {
+      const int64_t aj = h[H_COL + j];
+      if (aj < r0 || aj >= r1) continue;
+      double s[1], t[1];
+      if (below)
+        trmv_rows<false, 1, T, true>(M, n, lda, c, aj, r1, X + j, vec, s, t);
+      else
+        trmv_rows<false, 1, T, false>(M, n, lda, c, max(aj, c), r1, X + j, vec, s, t);
+      double* o = out(j);
+      o[0] = s[0];
+      if (two) o[1] = t[0];
+    }
+  }
+}
+
+// One workgroup decides a round of vgposp_greedy_step with speculation, on the device: a =
+// selected[round - 1] is looked up among the cached columns.  Hit: the slot is recorded and every
+// later kernel of the pass returns at once.  Miss: the pass list is a, then up to width - 1
+// columns that are unselected, unmasked and not yet cached, the largest fresh deltas of the
+// previous round first (exact top-(width-1): one strided scan of delta per column, n / 1024
+// loads a thread, against a pass over the triangle of L^-1); each gets the next free slot, and a
+// full table only ends the list — nothing is evicted, so nothing a round computes depends on the
+// table's history.
+__global__ __launch_bounds__(CH) void greedy_spec_plan_kernel(int64_t n, int round, int width,
+                                                              int64_t slots,
+                                                              const int64_t* selected,
+                                                              GreedyWS w) {
+  __shared__ long long hit_slot;
+  long long* h = w.spec;
+  long long* tcol = h + SPEC_HDR;
+  long long* tround = tcol + slots;
+  // (clamped: selected[] holds -1 once no candidate was left, and nothing here may index with it)
+  const long long a = min(max(selected[round - 1], (int64_t)0), n - 1);
+  long long cnt = h[H_COUNT];
+  if (threadIdx.x == 0) hit_slot = -1;
+  __syncthreads();
+  if (w.cmask[a])
+    for (long long e = threadIdx.x; e < cnt; e += blockDim.x)
+      if (tcol[e] == a) hit_slot = e;
+  __syncthreads();
+  if (hit_slot >= 0) {
+    if (threadIdx.x == 0) {
+      h[H_HIT] = 1;
+      h[H_SLOT] = hit_slot;
+      h[H_NB] = 0;
+      h[H_HITS] += 1;
+    }
+    return;
+  }
+  int nb = 1;
+  for (int t = 1; t < width && cnt < slots; ++t) {
+    double bv = -DBL_MAX;
+    long long bi = -1;
+    for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
+      if (w.selmask[i] || w.cmask[i]) continue;
+      const double d = w.delta[i];
+      if (key_gt(d, i, bv, bi)) {
+        bv = d;
+        bi = i;
+      }
+    }
+    block_keymax(bv, bi);
+    if (bi < 0) break;  // no candidate left (uniform)
+    if (threadIdx.x == 0) {
+      w.cmask[bi] = 1;
+      tcol[cnt] = bi;
+      tround[cnt] = round;
+      h[H_COL + nb] = bi;
+      h[H_CSLOT + nb] = cnt;
+    }
+    ++nb;
+    ++cnt;
+    __syncthreads();  // the next scan sees cmask[bi]
+  }
+  if (threadIdx.x == 0) {
+    h[H_HIT] = 0;
+    h[H_SLOT] = -1;
+    h[H_NB] = nb;
+    h[H_COL] = a;
+    h[H_CSLOT] = -1;
+    for (int j = nb; j < SPEC_TMAX; ++j) {
+      h[H_COL + j] = n;  // unused: above every row
+      h[H_CSLOT + j] = -1;
+    }
+    h[H_COUNT] = cnt;
+    h[H_PASSES] += 1;
+  }
+}
+
+// X[r][j] = (M e_{col[j]})_r for r >= col[j], else 0 (all zero for an unused entry).
+template <int T>
+__global__ void greedy_extract_spec_kernel(const double* M, int64_t n, int64_t lda,
+                                           const long long* h, double* X) {
+  if (h[H_HIT]) return;
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n * T) return;
+  const int64_t r = e / T;
+  const int64_t a = h[H_COL + (int)(e % T)];
+  X[e] = (a < n && r >= a) ? M[r * lda + a] : 0.0;
+}
+
+// q_c[i] of the speculated columns j >= 1 of a pass into their slots, in exactly the order of
+// greedy_update_kernel: q = 0; for rc = max(i, c) / RC .. nrc-1: q += part[rc][i].
+__global__ __launch_bounds__(CH) void greedy_spec_reduce_kernel(int64_t n, GreedyWS w) {
+  const long long* h = w.spec;
+  if (h[H_HIT]) return;
+  const int j = (int)blockIdx.y + 1;
+  if (j >= h[H_NB]) return;
+  const int64_t i = (int64_t)blockIdx.x * CH + threadIdx.x;
+  if (i >= n) return;
+  const int64_t c = h[H_COL + j], slot = h[H_CSLOT + j];
+  const int64_t nrc = (n + RC - 1) / RC;
+  const double* sp = w.spart + (int64_t)(j - 1) * nrc * n;
+  double q = 0.0;
+  for (int64_t rc = max(i, c) / RC; rc < nrc; ++rc) q += sp[rc * n + i];
+  w.qc[slot * n + i] = q;
 }
 
 // denom = conditional variance of y given V \ (A u {y}) with eps on that block's diagonal:
@@ -199,10 +435,12 @@ __device__ __forceinline__ double delta_of(double nom, double prec, double eps, 
 }
 
 // Round 0: nom = diag(Sigma), prec = Q_ii.  Round t>0: rank-1 updates with a = selected[t-1].
+// spec: a round of vgposp_greedy_step with speculation, whose q comes from the cache on a hit.
 // Then delta for every unselected candidate and per-workgroup best fresh key.
 __global__ __launch_bounds__(CH) void greedy_update_kernel(const double* S, int64_t n, int64_t lda,
                                                            const int64_t* selected, int round,
-                                                           GreedyWS w, int64_t cbeg, int64_t cend) {
+                                                           GreedyWS w, int64_t cbeg, int64_t cend,
+                                                           int spec) {
   const int64_t i = (cbeg / CH + (int64_t)blockIdx.x) * CH + threadIdx.x;
   const double eps = w.prm[0], thr = w.prm[1];
   if (i >= cbeg && i < cend) {
@@ -215,7 +453,10 @@ __global__ __launch_bounds__(CH) void greedy_update_kernel(const double* S, int6
     } else {
       const int64_t a = selected[round - 1];
       const int t1 = round - 1;  // new row index in W / V
-      for (int64_t rc = max(i, a) / RC; rc < nrc; ++rc) q += w.part[rc * n + i];
+      if (spec && w.spec[H_HIT])  // q_a was formed by an earlier pass, in this same order
+        q = w.qc[w.spec[H_SLOT] * n + i];
+      else
+        for (int64_t rc = max(i, a) / RC; rc < nrc; ++rc) q += w.part[rc * n + i];
       double s = (i < a) ? S[i * lda + a] : (i > a ? S[a * lda + i] : w.sdiag[a]);
       for (int t = 0; t < t1; ++t) {
         s -= w.piv[2 + t] * w.W[(int64_t)t * n + i];
@@ -538,7 +779,7 @@ extern "C" int vgposp_greedy_update_ex(const double* Sigma, int64_t n, int64_t l
     const int64_t b0 = c0 / CH, b1 = ceil_div(c1, CH);
     // grid covers the CH-aligned blocks spanning [c0, c1); blockIdx is offset by b0
     hipLaunchKernelGGL(greedy_update_kernel, dim3((unsigned)(b1 - b0)), dim3(CH), 0, s, Sigma, n,
-                       lda, selected, round, w, c0, c1);
+                       lda, selected, round, w, c0, c1, 0);
     VG_LAUNCH_CHECK();
   }
   return 0;
@@ -640,6 +881,8 @@ extern "C" int vgposp_greedy_finish_slab(double* Sigma, int64_t n, int64_t lda, 
   VG_CHECK_WS(ws_bytes, w.bytes);
   if (c1 == c0) return 0;
   hipStream_t s = as_stream(stream);
+  // M changes here: no cached column survives (header, table and the "is cached" bytes)
+  VG_HIP(vg_memset(w.spec, 0, (size_t)(SPEC_HDR + 2 * spec_slots(kmax)) * 8 + n, s));
   int rc = partial_inverse(Sigma, n, lda, c0, c1, tmp, greedy_fact_ws(ws, w, n), s);
   if (rc) return rc;
   // Q_ii = |M e_i|^2 for the slab's columns -> part (reduced in the round-0 update)
@@ -746,13 +989,96 @@ extern "C" int vgposp_greedy_select_window(int64_t n, int kmax, int round, int64
   return 0;
 }
 
+namespace vgposp {
+// The mat-vec part of a speculative round: plan, the T right-hand sides, one pass (or none), the
+// speculated columns into their slots.  A fixed launch sequence, hit or miss.
+template <int T>
+static void launch_spec_pass(const double* Sigma, int64_t n, int64_t lda, int kmax, int round,
+                             const int64_t* selected, const GreedyWS& w, hipStream_t s) {
+  hipLaunchKernelGGL(greedy_spec_plan_kernel, dim3(1), dim3(CH), 0, s, n, round, T,
+                     spec_slots(kmax), selected, w);
+  hipLaunchKernelGGL(greedy_extract_spec_kernel<T>, dim3((unsigned)ceil_div(n * T, 256)),
+                     dim3(256), 0, s, Sigma, n, lda, w.spec, w.X);
+  {
+    dim3 g((unsigned)ceil_div(n, TRMV_COLS), (unsigned)ceil_div(n, RC));
+    const int vec = (reinterpret_cast<uintptr_t>(Sigma) % 16 == 0) && (lda % 2 == 0);
+    ProfScope ps("greedy_trmv_spec", s, 0.0, 8.0 * (0.5 * (double)n * (n + 1) + (double)T * n));
+    hipLaunchKernelGGL(greedy_trmv_spec_kernel<T>, g, dim3(CT), 0, s, Sigma, n, lda, w.spec, w.X,
+                       w.part, w.spart, vec);
+  }
+  hipLaunchKernelGGL(greedy_spec_reduce_kernel, dim3((unsigned)ceil_div(n, CH), T - 1), dim3(CH),
+                     0, s, n, w);
+}
+}  // namespace vgposp
+
 extern "C" int vgposp_greedy_step(const double* Sigma, int64_t n, int64_t lda, int kmax, int round,
                                   int lazy, int64_t* selected, double* sel_delta, int64_t* evals,
                                   void* ws, size_t ws_bytes, void* stream) {
-  int rc = vgposp_greedy_update(Sigma, n, lda, kmax, round, 0, n, selected, ws, ws_bytes, stream);
+  const int width = g_spec_width.load(std::memory_order_relaxed);
+  int rc;
+  if (width == 1 || round <= 0) {
+    rc = vgposp_greedy_update(Sigma, n, lda, kmax, round, 0, n, selected, ws, ws_bytes, stream);
+  } else {
+    clear_error();
+    GreedyWS w;
+    rc = greedy_check(__func__, Sigma, n, lda, kmax, round, ws, ws_bytes, &w);
+    if (rc) return rc;
+    VG_CHECK_ARG(selected != nullptr, 7);
+    hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL(greedy_extract_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s,
+                       Sigma, n, lda, selected, round, w.xcol, (int64_t)0, n);
+    VG_LAUNCH_CHECK();
+    if (width == 2)
+      launch_spec_pass<2>(Sigma, n, lda, kmax, round, selected, w, s);
+    else if (width == 4)
+      launch_spec_pass<4>(Sigma, n, lda, kmax, round, selected, w, s);
+    else
+      launch_spec_pass<8>(Sigma, n, lda, kmax, round, selected, w, s);
+    VG_LAUNCH_CHECK();
+    ProfScope psu("greedy_update", s, 0.0, 8.0 * (double)n * (6 + 2.0 * round));
+    hipLaunchKernelGGL(greedy_update_kernel, dim3((unsigned)ceil_div(n, CH)), dim3(CH), 0, s,
+                       Sigma, n, lda, selected, round, w, (int64_t)0, n, 1);
+    VG_LAUNCH_CHECK();
+  }
   if (rc) return rc;
   return vgposp_greedy_select(n, kmax, round, lazy, 0, n, selected, sel_delta, evals, ws, ws_bytes,
                               stream);
+}
+
+extern "C" int vgposp_greedy_set_speculation(int width) {
+  clear_error();
+  VG_CHECK_ARG(width == 1 || width == 2 || width == 4 || width == 8, 1);
+  g_spec_width.store(width, std::memory_order_relaxed);
+  return 0;
+}
+
+extern "C" int vgposp_greedy_speculation(void) { return g_spec_width.load(); }
+
+extern "C" int vgposp_greedy_spec_stats(void* ws, int64_t n, int kmax, int64_t* passes,
+                                        int64_t* hits, int64_t* cached) {
+  clear_error();
+  VG_CHECK_ARG(ws != nullptr, 1);
+  VG_CHECK_ARG(n >= 1, 2);
+  VG_CHECK_ARG(kmax >= 1, 3);
+  long long h[3];
+  VG_HIP(hipMemcpy(h, greedy_layout(ws, n, kmax).spec, sizeof(h), hipMemcpyDeviceToHost));
+  if (cached) *cached = h[H_COUNT];
+  if (passes) *passes = h[H_PASSES];
+  if (hits) *hits = h[H_HITS];
+  return 0;
+}
+
+extern "C" int vgposp_greedy_spec_table(void* ws, int64_t n, int kmax, int64_t** column,
+                                        int64_t** fill_round, int64_t* slots) {
+  clear_error();
+  VG_CHECK_ARG(ws != nullptr, 1);
+  VG_CHECK_ARG(n >= 1, 2);
+  VG_CHECK_ARG(kmax >= 1, 3);
+  GreedyWS w = greedy_layout(ws, n, kmax);
+  if (column) *column = (int64_t*)(w.spec + SPEC_HDR);
+  if (fill_round) *fill_round = (int64_t*)(w.spec + SPEC_HDR + spec_slots(kmax));
+  if (slots) *slots = spec_slots(kmax);
+  return 0;
 }
 
 extern "C" int vgposp_greedy_buffers(void* ws, int64_t n, int kmax, double** delta, double** piv,
@@ -1044,7 +1370,7 @@ extern "C" int vgposp_greedy_condition(const double* Sigma, int64_t n, int64_t l
       wj.part = c.part + (int64_t)j * slice;
       ProfScope psu("greedy_update", s, 0.0, 8.0 * (double)n * (6 + 2.0 * r));
       hipLaunchKernelGGL(greedy_update_kernel, dim3((unsigned)ceil_div(n, CH)), dim3(CH), 0, s,
-                         Sigma, n, lda, selected, r, wj, (int64_t)0, n);
+                         Sigma, n, lda, selected, r, wj, (int64_t)0, n, 0);
       VG_LAUNCH_CHECK();
       if ((rc = force(r))) return rc;
     }
