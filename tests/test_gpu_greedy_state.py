@@ -175,7 +175,7 @@ def _run(name, n=None, lazy=True, cache_init=None, masked=False, placed=(), batc
     m = len(placed)
     g = Greedy(K, n, m + k, (eps, thr, cinit if cache_init is None else cache_init), lda, shift)
     g.init()
-    out = {"n": n, "m": m, "k": k, "host0": g.host0, "cond": None}
+    out = {"n": n, "m": m, "k": k, "host0": g.host0, "cond": None, "placed": list(placed)}
     if lda is not None:
         out["after_init"] = g.matrix()
     blocked = R.third_mask(n) if masked else np.zeros(n, dtype=bool)
@@ -220,7 +220,7 @@ def _check_arithmetic(label, name, run):
     rounds = list(zip(range(m, m + k), recs, [True] * k))
     if m:  # the state the conditioning leaves: round m - 1; xcol is not part of it (the batched
         rounds.insert(0, (m - 1, run["cond"], False))  # kernels keep their columns in scratch)
-        assert picks[:m] == list(R.PLACED)
+        assert picks[:m] == run["placed"]
     e_cpu = _e_cpu(name, n, picks, blocked, rounds[0][0])
     tol = R.tolerance(e_cpu)
     worst = {key: 0.0 for key in R.ERROR_KEYS}
@@ -373,10 +373,60 @@ def test_slab_split_is_the_whole_step(c):
 def test_conditioning(batch):
     """vgposp_greedy_condition on six sensors (five columns: 4 + 1 with T = 4, one short batch with
     T = 8), then two free rounds: the state the conditioning leaves (A = placed[:5], pivots of
-    placed[5]), then A = placed and A = placed + pick.  The batched kernels sum in another order,
-    so the batch sizes are each held to the reference, not to each other."""
+    placed[5]), then A = placed and A = placed + pick.  The batched kernels sum in another order
+    (their own row loop: greedy_trmv_batch_kernel), so the batch sizes are each held to the
+    reference here, and to each other, to rounding, in test_conditioning_widths."""
     run = _run("F1", None, True, placed=tuple(R.PLACED), batch=batch, k=2)
     _check_arithmetic(f"F1 placed batch {batch}", "F1", run)
+
+
+# nine conditioned columns (8 + 1 with T = 8, 4 + 4 + 1 with T = 4): a sensor at index 0 and one
+# at n - 1, both sides of both row-chunk boundaries, several columns in one chunk
+PLACED_EDGES = (0, 1039, 511, 512, 513, 1024, 3, 700, 1023, 64)
+WIDTHS_RTOL = 1e-10   # the cross-width tolerance of tests/test_gpu_constrained.py
+
+
+@pytest.mark.parametrize("placed,lda,batches", [
+    pytest.param(tuple(R.PLACED), None, (1, 4, 8), id="placed"),
+    pytest.param(PLACED_EDGES, None, (1, 4, 8), id="edges"),
+    pytest.param(PLACED_EDGES, 1041, (1, 4), id="edges-lda1041"),   # the scalar-load path
+])
+def test_conditioning_widths(placed, lda, batches):
+    """The batch sizes against each other, after the conditioning and after each of two free
+    rounds (workspace and scratch start as 0xFF bytes): picks and evaluation counts are equal,
+    the extracted column of a free round is byte-equal, and delta, cache, pivots and pick deltas
+    agree to WIDTHS_RTOL (greedy_trmv_batch_kernel sums a column in another order than
+    greedy_trmv_kernel).  Every width is also held to the longdouble reference at the tolerance
+    of test_arithmetic."""
+    runs = {b: _run("F1", None, True, placed=placed, batch=b, lda=lda, k=2) for b in batches}
+    one = runs[1]
+    m, n = len(placed), one["n"]
+    for b in batches:
+        _check_arithmetic(f"F1 {m} placed lda {lda or n} batch {b}", "F1", runs[b])
+        stages = [("conditioning", m - 1, one["cond"], runs[b]["cond"])]
+        stages += [(f"round {i}", m + i, x, y)
+                   for i, (x, y) in enumerate(zip(one["recs"], runs[b]["recs"]))]
+        for when, r, want, got in stages:
+            assert _same(got["selected"], want["selected"]), (b, when)
+            assert _same(got["evals"], want["evals"]), (b, when)
+            free = np.ones(n, dtype=bool)
+            free[want["selected"][:r + 1]] = False
+            assert np.isfinite(want["delta"][free]).all(), when
+            np.testing.assert_allclose(got["delta"][free], want["delta"][free], rtol=WIDTHS_RTOL)
+            stale = np.isinf(want["cache"])            # never evaluated: the initial value
+            assert _same(got["cache"][stale], want["cache"][stale]), (b, when)
+            np.testing.assert_allclose(got["cache"][~stale], want["cache"][~stale],
+                                       rtol=WIDTHS_RTOL)
+            # pivots: nom_y, P_yy; the row of W (Sigma alone: no mat-vec in it); the row of V,
+            # differences of the q's, so to the row's scale
+            np.testing.assert_allclose(got["piv"][:2], want["piv"][:2], rtol=WIDTHS_RTOL)
+            assert _same(got["piv"][2:2 + r], want["piv"][2:2 + r]), (b, when)
+            v = want["piv"][2 + r:2 + 2 * r]
+            np.testing.assert_allclose(got["piv"][2 + r:2 + 2 * r], v, rtol=WIDTHS_RTOL,
+                                       atol=WIDTHS_RTOL * np.abs(v).max())
+            np.testing.assert_allclose(got["sel_delta"], want["sel_delta"], rtol=WIDTHS_RTOL)
+            if r >= m:
+                assert _same(got["xcol"], want["xcol"]), (b, when)
 
 
 # ---- (e) layouts at the ABI ----

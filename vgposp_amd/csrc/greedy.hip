@@ -254,6 +254,12 @@ __global__ __launch_bounds__(CT) void greedy_trmv_kernel(const double* M, int64_
   if (two) part[blockIdx.y * n + c + 1] = t[0];
 }
 
+// Indices that come from the caller arrive validated by the host (range, duplicates); the clamp
+// only keeps a corrupt value from addressing outside the matrix.
+__device__ __forceinline__ int64_t forced_index(const int64_t* forced, int64_t j, int64_t n) {
+  return min(max(forced[j], (int64_t)0), n - 1);
+}
+
 // greedy_trmv_kernel<false> for the up to T columns of a speculative pass (header words H_COL:
 // the pick first, n for an unused entry), right-hand sides row-interleaved in X.  Column j's
 // partials are bit for bit what the classic kernel writes for a = col[j]: its origin in row chunk
@@ -397,15 +403,22 @@ __global__ __launch_bounds__(CH) void greedy_spec_plan_kernel(int64_t n, int rou
   }
 }
 
-// X[r][j] = (M e_{col[j]})_r for r >= col[j], else 0 (all zero for an unused entry).
+// The right-hand sides of a multi-column pass, row-interleaved so that the mat-vec reads the T
+// values of a row with one uniform load: X[r][j] = (M e_{col[j]})_r for r >= col[j], else 0.
+// col[j] = cols[j] for j < nt and n (unused: all zero) beyond.  The speculation passes the header
+// words H_COL, where greedy_spec_plan_kernel marks its own unused entries with n, and H_HIT as
+// `skip` (nothing runs when it is set); the conditioning passes placed + j0 with clamp = 1.
 template <int T>
-__global__ void greedy_extract_spec_kernel(const double* M, int64_t n, int64_t lda,
-                                           const long long* h, double* X) {
-  if (h[H_HIT]) return;
+__global__ void greedy_extract_cols_kernel(const double* M, int64_t n, int64_t lda,
+                                           const long long* cols, int nt, int clamp,
+                                           const long long* skip, double* X) {
+  if (skip && *skip) return;
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n * T) return;
   const int64_t r = e / T;
-  const int64_t a = h[H_COL + (int)(e % T)];
+  const int j = (int)(e % T);
+  int64_t a = n;
+  if (j < nt) a = clamp ? forced_index(reinterpret_cast<const int64_t*>(cols), j, n) : cols[j];
   X[e] = (a < n && r >= a) ? M[r * lda + a] : 0.0;
 }
 
@@ -684,41 +697,69 @@ extern "C" size_t vgposp_greedy_workspace_bytes(int64_t n, int kmax) {
   return greedy_layout(nullptr, n, kmax).bytes;
 }
 
+// Grid of a mat-vec kernel over columns [c0, c1) (the tile origin is even: column pairs), and
+// whether it may load a column pair with one 16-byte access.
+static dim3 trmv_grid(int64_t n, int64_t c0, int64_t c1) {
+  return dim3((unsigned)ceil_div(c1 - (c0 & ~(int64_t)1), TRMV_COLS), (unsigned)ceil_div(n, RC));
+}
+static int trmv_vec(const double* M, int64_t lda) {
+  return (reinterpret_cast<uintptr_t>(M) % 16 == 0) && (lda % 2 == 0);
+}
+
+// Q_ii = |M e_i|^2 for columns [c0, c1) -> part (reduced in the round-0 update)
+static void launch_colsq(const double* M, int64_t n, int64_t lda, int64_t c0, int64_t c1,
+                         const GreedyWS& w, hipStream_t s) {
+  const bool whole = c0 == 0 && c1 == n;  // a slab reports no algorithmic figures
+  const double tri = 0.5 * (double)n * (n + 1);
+  ProfScope ps("greedy_colsq", s, whole ? 2.0 * tri : 0.0,
+               whole ? 8.0 * (tri + (double)ceil_div(n, RC) * n) : 0.0);
+  hipLaunchKernelGGL(greedy_trmv_kernel<true>, trmv_grid(n, c0, c1), dim3(CT), 0, s, M, n, lda,
+                     nullptr, 0, nullptr, w.part, c0, c1, trmv_vec(M, lda));
+}
+
+// The checks of vgposp_greedy_prepare, then what it does: `info` cleared and the init kernel.
+static int greedy_prepare(const char* fn, double* Sigma, int64_t n, int64_t lda, int kmax,
+                          double jitter, double threshold, double cache_init, int* info, void* ws,
+                          size_t ws_bytes, hipStream_t s, GreedyWS* w) {
+  if (Sigma == nullptr) { set_error("%s: bad argument 1", fn); return -1; }
+  if (!(n >= 1 && n <= (int64_t)MAXCH * CH)) { set_error("%s: bad argument 2", fn); return -2; }
+  if (lda < n) { set_error("%s: bad argument 3", fn); return -3; }
+  if (!(kmax >= 1 && kmax <= n)) { set_error("%s: bad argument 4", fn); return -4; }
+  if (!(jitter >= 0.0 && jitter < 1e300)) { set_error("%s: bad argument 5", fn); return -5; }
+  if (!(threshold >= 0.0)) { set_error("%s: bad argument 6", fn); return -6; }
+  if (cache_init != cache_init) { set_error("%s: bad argument 7", fn); return -7; }
+  if (info == nullptr) { set_error("%s: info is null", fn); return -8; }
+  if (ws == nullptr) { set_error("%s: workspace is null", fn); return VGPOSP_E_WS; }
+  *w = greedy_layout(ws, n, kmax);
+  if (ws_bytes < w->bytes) {
+    set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, w->bytes);
+    return VGPOSP_E_WS;
+  }
+  VG_HIP(vg_memset(info, 0, sizeof(int), s));
+  hipLaunchKernelGGL(greedy_init_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, Sigma,
+                     n, lda, jitter, threshold, cache_init, *w);
+  VG_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int vgposp_greedy_init_ex(double* Sigma, int64_t n, int64_t lda, int kmax,
                                      double jitter, double threshold, double cache_init, int* info,
                                      void* ws, size_t ws_bytes, void* stream) {
   clear_error();
-  VG_CHECK_ARG(Sigma != nullptr, 1);
-  VG_CHECK_ARG(n >= 1 && n <= (int64_t)MAXCH * CH, 2);
-  VG_CHECK_ARG(lda >= n, 3);
-  VG_CHECK_ARG(kmax >= 1 && kmax <= n, 4);
-  VG_CHECK_ARG(jitter >= 0.0 && jitter < 1e300, 5);
-  VG_CHECK_ARG(threshold >= 0.0, 6);
-  VG_CHECK_ARG(cache_init == cache_init, 7);
-  VG_CHECK_ARG(info != nullptr, 8);
+  VG_CHECK_ARG(info != nullptr, 8);  // by position here; the workspace text names the family
   VG_CHECK_ARG(ws != nullptr, 9);
-  GreedyWS w = greedy_layout(ws, n, kmax);
-  if (ws_bytes < w.bytes) {
-    set_error("vgposp_greedy_init: workspace %zu < %zu bytes", ws_bytes, w.bytes);
-    return VGPOSP_E_WS;
-  }
   hipStream_t s = as_stream(stream);
-  VG_HIP(vg_memset(info, 0, sizeof(int), s));
-  hipLaunchKernelGGL(greedy_init_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, Sigma,
-                     n, lda, jitter, threshold, cache_init, w);
-  VG_LAUNCH_CHECK();
+  GreedyWS w;
+  int rc = greedy_prepare("vgposp_greedy_init", Sigma, n, lda, kmax, jitter, threshold,
+                          cache_init, info, ws, ws_bytes, s, &w);
+  if (rc) return rc;
   // early: after a failed pivot (a singular cov_vv) every later launch of the factorization and
   // inverse reads `info` on the device and exits, so the host's jitter retry does not pay for a
   // whole O(n^3) factorization + inverse first — and nothing here synchronises the host
-  int rc = potrf_one(Sigma, n, lda, /*invert=*/1, nullptr, info, greedy_fact_ws(ws, w, n), s,
-                     /*early=*/true);
+  rc = potrf_one(Sigma, n, lda, /*invert=*/1, nullptr, info, greedy_fact_ws(ws, w, n), s,
+                 /*early=*/true);
   if (rc) return rc;
-  // Q_ii = |M e_i|^2 -> part (reduced in the round-0 update)
-  dim3 g((unsigned)ceil_div(n, TRMV_COLS), (unsigned)ceil_div(n, RC));
-  const int vec = (reinterpret_cast<uintptr_t>(Sigma) % 16 == 0) && (lda % 2 == 0);
-  ProfScope ps("greedy_colsq", s, (double)n * (n + 1), 8.0 * (0.5 * (double)n * (n + 1) + (double)ceil_div(n, RC) * n));
-  hipLaunchKernelGGL(greedy_trmv_kernel<true>, g, dim3(CT), 0, s, Sigma, n, lda, nullptr, 0,
-                     nullptr, w.part, (int64_t)0, n, vec);
+  launch_colsq(Sigma, n, lda, 0, n, w, s);
   VG_LAUNCH_CHECK();
   return 0;
 }
@@ -765,13 +806,11 @@ extern "C" int vgposp_greedy_update_ex(const double* Sigma, int64_t n, int64_t l
                          Sigma, n, lda, selected, round, w.xcol, (int64_t)0, n);
       VG_LAUNCH_CHECK();
     }
-    dim3 g((unsigned)ceil_div(c1 - (c0 & ~(int64_t)1), TRMV_COLS), (unsigned)ceil_div(n, RC));
-    const int vec = (reinterpret_cast<uintptr_t>(Sigma) % 16 == 0) && (lda % 2 == 0);
     // algorithmic: the lower triangle of L^-1 in rows >= a, columns [c0, c1) (a is device-side;
     // bench.py recomputes the exact bytes from the selections)
     ProfScope ps("greedy_trmv", s, 0.0, 8.0 * (0.5 * (double)n * (n + 1) + 2.0 * n));
-    hipLaunchKernelGGL(greedy_trmv_kernel<false>, g, dim3(CT), 0, s, Sigma, n, lda, selected,
-                       round, w.xcol, w.part, c0, c1, vec);
+    hipLaunchKernelGGL(greedy_trmv_kernel<false>, trmv_grid(n, c0, c1), dim3(CT), 0, s, Sigma, n,
+                       lda, selected, round, w.xcol, w.part, c0, c1, trmv_vec(Sigma, lda));
     VG_LAUNCH_CHECK();
   }
   {
@@ -815,50 +854,30 @@ extern "C" size_t vgposp_greedy_slab_tmp_bytes(int64_t n, int64_t c0, int64_t c1
   return partial_inverse_tmp_bytes(n, c0, c1);
 }
 
-static int check_prepare(const char* fn, double* Sigma, int64_t n, int64_t lda, int kmax,
-                         double jitter, double threshold, double cache_init, int* info, void* ws,
-                         size_t ws_bytes, GreedyWS* w) {
-  if (Sigma == nullptr) { set_error("%s: bad argument 1", fn); return -1; }
-  if (!(n >= 1 && n <= (int64_t)MAXCH * CH)) { set_error("%s: bad argument 2", fn); return -2; }
-  if (lda < n) { set_error("%s: bad argument 3", fn); return -3; }
-  if (!(kmax >= 1 && kmax <= n)) { set_error("%s: bad argument 4", fn); return -4; }
-  if (!(jitter >= 0.0 && jitter < 1e300)) { set_error("%s: bad argument 5", fn); return -5; }
-  if (!(threshold >= 0.0)) { set_error("%s: bad argument 6", fn); return -6; }
-  if (cache_init != cache_init) { set_error("%s: bad argument 7", fn); return -7; }
-  if (info == nullptr) { set_error("%s: info is null", fn); return -8; }
-  if (ws == nullptr) { set_error("%s: workspace is null", fn); return VGPOSP_E_WS; }
-  *w = greedy_layout(ws, n, kmax);
-  if (ws_bytes < w->bytes) {
-    set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, w->bytes);
-    return VGPOSP_E_WS;
-  }
-  return 0;
-}
-
 extern "C" int vgposp_greedy_prepare(double* Sigma, int64_t n, int64_t lda, int kmax,
                                      double jitter, double threshold, double cache_init, int* info,
                                      void* ws, size_t ws_bytes, void* stream) {
   clear_error();
   GreedyWS w;
-  if (int rc = check_prepare(__func__, Sigma, n, lda, kmax, jitter, threshold, cache_init, info,
-                             ws, ws_bytes, &w))
-    return rc;
-  hipStream_t s = as_stream(stream);
-  VG_HIP(vg_memset(info, 0, sizeof(int), s));
-  hipLaunchKernelGGL(greedy_init_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, Sigma,
-                     n, lda, jitter, threshold, cache_init, w);
-  VG_LAUNCH_CHECK();
+  return greedy_prepare(__func__, Sigma, n, lda, kmax, jitter, threshold, cache_init, info, ws,
+                        ws_bytes, as_stream(stream), &w);
+}
+
+// The preamble of the entry points that only look into a workspace: (ws, n, kmax) -> its layout.
+static int greedy_ws(const char* fn, void* ws, int64_t n, int kmax, GreedyWS* w) {
+  clear_error();
+  if (ws == nullptr) { set_error("%s: bad argument 1 (ws != nullptr)", fn); return -1; }
+  if (!(n >= 1)) { set_error("%s: bad argument 2 (n >= 1)", fn); return -2; }
+  if (!(kmax >= 1)) { set_error("%s: bad argument 3 (kmax >= 1)", fn); return -3; }
+  *w = greedy_layout(ws, n, kmax);
   return 0;
 }
 
 extern "C" int vgposp_greedy_fact_ws(void* ws, int64_t n, int kmax, void** fws,
                                      size_t* fws_bytes) {
-  clear_error();
-  VG_CHECK_ARG(ws != nullptr, 1);
-  VG_CHECK_ARG(n >= 1, 2);
-  VG_CHECK_ARG(kmax >= 1, 3);
+  GreedyWS w;
+  if (int rc = greedy_ws(__func__, ws, n, kmax, &w)) return rc;
   VG_CHECK_ARG(fws != nullptr && fws_bytes != nullptr, 4);
-  GreedyWS w = greedy_layout(ws, n, kmax);
   *fws = greedy_fact_ws(ws, w, n);
   *fws_bytes = potrf_ws_bytes(n);
   return 0;
@@ -885,12 +904,7 @@ extern "C" int vgposp_greedy_finish_slab(double* Sigma, int64_t n, int64_t lda, 
   VG_HIP(vg_memset(w.spec, 0, (size_t)(SPEC_HDR + 2 * spec_slots(kmax)) * 8 + n, s));
   int rc = partial_inverse(Sigma, n, lda, c0, c1, tmp, greedy_fact_ws(ws, w, n), s);
   if (rc) return rc;
-  // Q_ii = |M e_i|^2 for the slab's columns -> part (reduced in the round-0 update)
-  dim3 g((unsigned)ceil_div(c1 - (c0 & ~(int64_t)1), TRMV_COLS), (unsigned)ceil_div(n, RC));
-  const int vec = (reinterpret_cast<uintptr_t>(Sigma) % 16 == 0) && (lda % 2 == 0);
-  ProfScope ps("greedy_colsq", s, 0.0, 0.0);
-  hipLaunchKernelGGL(greedy_trmv_kernel<true>, g, dim3(CT), 0, s, Sigma, n, lda, nullptr, 0,
-                     nullptr, w.part, c0, c1, vec);
+  launch_colsq(Sigma, n, lda, c0, c1, w, s);
   VG_LAUNCH_CHECK();
   return 0;
 }
@@ -917,12 +931,10 @@ extern "C" int vgposp_greedy_init_slab(double* Sigma, int64_t n, int64_t lda, in
 }
 
 extern "C" int vgposp_greedy_xcol(void* ws, int64_t n, int kmax, double** xcol) {
-  clear_error();
-  VG_CHECK_ARG(ws != nullptr, 1);
-  VG_CHECK_ARG(n >= 1, 2);
-  VG_CHECK_ARG(kmax >= 1, 3);
+  GreedyWS w;
+  if (int rc = greedy_ws(__func__, ws, n, kmax, &w)) return rc;
   VG_CHECK_ARG(xcol != nullptr, 4);
-  *xcol = greedy_layout(ws, n, kmax).xcol;
+  *xcol = w.xcol;
   return 0;
 }
 
@@ -997,14 +1009,12 @@ static void launch_spec_pass(const double* Sigma, int64_t n, int64_t lda, int km
                              const int64_t* selected, const GreedyWS& w, hipStream_t s) {
   hipLaunchKernelGGL(greedy_spec_plan_kernel, dim3(1), dim3(CH), 0, s, n, round, T,
                      spec_slots(kmax), selected, w);
-  hipLaunchKernelGGL(greedy_extract_spec_kernel<T>, dim3((unsigned)ceil_div(n * T, 256)),
-                     dim3(256), 0, s, Sigma, n, lda, w.spec, w.X);
+  hipLaunchKernelGGL(greedy_extract_cols_kernel<T>, dim3((unsigned)ceil_div(n * T, 256)),
+                     dim3(256), 0, s, Sigma, n, lda, w.spec + H_COL, T, 0, w.spec + H_HIT, w.X);
   {
-    dim3 g((unsigned)ceil_div(n, TRMV_COLS), (unsigned)ceil_div(n, RC));
-    const int vec = (reinterpret_cast<uintptr_t>(Sigma) % 16 == 0) && (lda % 2 == 0);
     ProfScope ps("greedy_trmv_spec", s, 0.0, 8.0 * (0.5 * (double)n * (n + 1) + (double)T * n));
-    hipLaunchKernelGGL(greedy_trmv_spec_kernel<T>, g, dim3(CT), 0, s, Sigma, n, lda, w.spec, w.X,
-                       w.part, w.spart, vec);
+    hipLaunchKernelGGL(greedy_trmv_spec_kernel<T>, trmv_grid(n, 0, n), dim3(CT), 0, s, Sigma, n,
+                       lda, w.spec, w.X, w.part, w.spart, trmv_vec(Sigma, lda));
   }
   hipLaunchKernelGGL(greedy_spec_reduce_kernel, dim3((unsigned)ceil_div(n, CH), T - 1), dim3(CH),
                      0, s, n, w);
@@ -1056,12 +1066,10 @@ extern "C" int vgposp_greedy_speculation(void) { return g_spec_width.load(); }
 
 extern "C" int vgposp_greedy_spec_stats(void* ws, int64_t n, int kmax, int64_t* passes,
                                         int64_t* hits, int64_t* cached) {
-  clear_error();
-  VG_CHECK_ARG(ws != nullptr, 1);
-  VG_CHECK_ARG(n >= 1, 2);
-  VG_CHECK_ARG(kmax >= 1, 3);
+  GreedyWS w;
+  if (int rc = greedy_ws(__func__, ws, n, kmax, &w)) return rc;
   long long h[3];
-  VG_HIP(hipMemcpy(h, greedy_layout(ws, n, kmax).spec, sizeof(h), hipMemcpyDeviceToHost));
+  VG_HIP(hipMemcpy(h, w.spec, sizeof(h), hipMemcpyDeviceToHost));
   if (cached) *cached = h[H_COUNT];
   if (passes) *passes = h[H_PASSES];
   if (hits) *hits = h[H_HITS];
@@ -1070,11 +1078,8 @@ extern "C" int vgposp_greedy_spec_stats(void* ws, int64_t n, int kmax, int64_t* 
 
 extern "C" int vgposp_greedy_spec_table(void* ws, int64_t n, int kmax, int64_t** column,
                                         int64_t** fill_round, int64_t* slots) {
-  clear_error();
-  VG_CHECK_ARG(ws != nullptr, 1);
-  VG_CHECK_ARG(n >= 1, 2);
-  VG_CHECK_ARG(kmax >= 1, 3);
-  GreedyWS w = greedy_layout(ws, n, kmax);
+  GreedyWS w;
+  if (int rc = greedy_ws(__func__, ws, n, kmax, &w)) return rc;
   if (column) *column = (int64_t*)(w.spec + SPEC_HDR);
   if (fill_round) *fill_round = (int64_t*)(w.spec + SPEC_HDR + spec_slots(kmax));
   if (slots) *slots = spec_slots(kmax);
@@ -1083,11 +1088,8 @@ extern "C" int vgposp_greedy_spec_table(void* ws, int64_t n, int kmax, int64_t**
 
 extern "C" int vgposp_greedy_buffers(void* ws, int64_t n, int kmax, double** delta, double** piv,
                                      int64_t* piv_len) {
-  clear_error();
-  VG_CHECK_ARG(ws != nullptr, 1);
-  VG_CHECK_ARG(n >= 1, 2);
-  VG_CHECK_ARG(kmax >= 1, 3);
-  GreedyWS w = greedy_layout(ws, n, kmax);
+  GreedyWS w;
+  if (int rc = greedy_ws(__func__, ws, n, kmax, &w)) return rc;
   if (delta) *delta = w.delta;
   if (piv) *piv = w.piv;
   if (piv_len) *piv_len = 2 + 2 * (int64_t)kmax;
@@ -1095,12 +1097,10 @@ extern "C" int vgposp_greedy_buffers(void* ws, int64_t n, int kmax, double** del
 }
 
 extern "C" int vgposp_greedy_cache(void* ws, int64_t n, int kmax, double** cache) {
-  clear_error();
-  VG_CHECK_ARG(ws != nullptr, 1);
-  VG_CHECK_ARG(n >= 1, 2);
-  VG_CHECK_ARG(kmax >= 1, 3);
+  GreedyWS w;
+  if (int rc = greedy_ws(__func__, ws, n, kmax, &w)) return rc;
   VG_CHECK_ARG(cache != nullptr, 4);
-  *cache = greedy_layout(ws, n, kmax).cache;
+  *cache = w.cache;
   return 0;
 }
 
@@ -1110,12 +1110,9 @@ __global__ void greedy_exclude_kernel(unsigned char* selmask, int64_t idx) { sel
 
 extern "C" int vgposp_greedy_exclude(void* ws, int64_t n, int kmax, int64_t idx, void* stream) {
   using namespace vgposp;
-  clear_error();
-  VG_CHECK_ARG(ws != nullptr, 1);
-  VG_CHECK_ARG(n >= 1, 2);
-  VG_CHECK_ARG(kmax >= 1, 3);
+  GreedyWS w;
+  if (int rc = greedy_ws(__func__, ws, n, kmax, &w)) return rc;
   VG_CHECK_ARG(idx >= 0 && idx < n, 4);
-  GreedyWS w = greedy_layout(ws, n, kmax);
   hipLaunchKernelGGL(greedy_exclude_kernel, dim3(1), dim3(1), 0, as_stream(stream), w.selmask, idx);
   VG_LAUNCH_CHECK();
   return 0;
@@ -1131,12 +1128,6 @@ __global__ void greedy_mask_kernel(int64_t n, const unsigned char* allowed,
                                    unsigned char* selmask) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n && !allowed[i]) selmask[i] = 1;
-}
-
-// Indices come validated from the host (range, duplicates); the clamp only keeps a corrupt value
-// from addressing outside the matrix.
-__device__ __forceinline__ int64_t forced_index(const int64_t* forced, int64_t j, int64_t n) {
-  return min(max(forced[j], (int64_t)0), n - 1);
 }
 
 // The tail of greedy_select_kernel for a pick given by the caller: y = forced[j] instead of the
@@ -1157,29 +1148,17 @@ __global__ __launch_bounds__(256) void greedy_force_kernel(int64_t n, int round,
   }
 }
 
-// X[r][j] = (M e_{a_j})_r for r >= a_j, else 0, a_j = forced[j0 + j], j < nt; columns nt..T-1 are
-// zero.  Row-interleaved so the mat-vec reads the T values of a row with one uniform load.
-template <int T>
-__global__ void greedy_extract_batch_kernel(const double* M, int64_t n, int64_t lda,
-                                            const int64_t* forced, int64_t j0, int nt, double* X) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= n * T) return;
-  const int64_t r = e / T;
-  const int j = (int)(e % T);
-  double x = 0.0;
-  if (j < nt) {
-    const int64_t a = forced_index(forced, j0 + j, n);
-    if (r >= a) x = M[r * lda + a];
-  }
-  X[e] = x;
-}
-
 // greedy_trmv_kernel<false> for T right-hand sides in one pass over M = L^-1:
 //   part[j][rc][c] = sum_{r in chunk rc, r >= max(c, a_j)} M[r][c] * X[r][j]
 // Same tiling and the same 16-byte non-temporal column-pair loads; rows start at
 // max(c, min_j a_j) (X[.][j] is zero above a_j).  The row index is uniform over the workgroup, so
 // the T values of X for a row are wave-uniform operands; the diagonal tile (RC == TRMV_COLS, all
 // columns) masks the entries above the diagonal, which hold Sigma.
+// Its own row loop, not trmv_rows, and so equal to the classic kernel to rounding only: two
+// accumulators per column and right-hand side where trmv_rows' fixed order needs four, and a
+// uniform row index in the diagonal tile too.  Conditioning through greedy_trmv_spec_kernel's
+// pass was measured and is slower (profiles/cond_unified_ab.json; batch 8, 256 sensors): by
+// 18 % at N = 65,536 and 2.4 x at 16,384 with its own-origin loops, by 12 % and 42 % without.
 static_assert(RC == TRMV_COLS, "the batched mat-vec takes tile (b, b) as the diagonal tile");
 
 template <int T, bool VEC>
@@ -1261,18 +1240,17 @@ static bool cond_batch_ok(int batch) { return batch == 1 || batch == 4 || batch 
 template <int T>
 static void launch_cond_batch(const double* Sigma, int64_t n, int64_t lda, const int64_t* forced,
                               int64_t j0, int nt, const CondScratch& c, hipStream_t s) {
-  hipLaunchKernelGGL(greedy_extract_batch_kernel<T>, dim3((unsigned)ceil_div(n * T, 256)),
-                     dim3(256), 0, s, Sigma, n, lda, forced, j0, nt, c.X);
-  dim3 g((unsigned)ceil_div(n, TRMV_COLS), (unsigned)ceil_div(n, RC));
-  const bool vec = (reinterpret_cast<uintptr_t>(Sigma) % 16 == 0) && (lda % 2 == 0);
+  hipLaunchKernelGGL(greedy_extract_cols_kernel<T>, dim3((unsigned)ceil_div(n * T, 256)),
+                     dim3(256), 0, s, Sigma, n, lda,
+                     reinterpret_cast<const long long*>(forced + j0), nt, 1, nullptr, c.X);
   ProfScope ps("greedy_trmv_batch", s, 2.0 * T * 0.5 * (double)n * (n + 1),
                8.0 * (0.5 * (double)n * (n + 1) + (double)T * n));
-  if (vec)
-    hipLaunchKernelGGL((greedy_trmv_batch_kernel<T, true>), g, dim3(CT), 0, s, Sigma, n, lda,
-                       forced, j0, nt, c.X, c.part);
+  if (trmv_vec(Sigma, lda))
+    hipLaunchKernelGGL((greedy_trmv_batch_kernel<T, true>), trmv_grid(n, 0, n), dim3(CT), 0, s,
+                       Sigma, n, lda, forced, j0, nt, c.X, c.part);
   else
-    hipLaunchKernelGGL((greedy_trmv_batch_kernel<T, false>), g, dim3(CT), 0, s, Sigma, n, lda,
-                       forced, j0, nt, c.X, c.part);
+    hipLaunchKernelGGL((greedy_trmv_batch_kernel<T, false>), trmv_grid(n, 0, n), dim3(CT), 0, s,
+                       Sigma, n, lda, forced, j0, nt, c.X, c.part);
 }
 
 }  // namespace vgposp
