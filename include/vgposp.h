@@ -590,6 +590,73 @@ int vgposp_greedy_buffers(void* ws, int64_t n, int kmax, double** delta, double*
                           int64_t* piv_len);
 
 /* ---------------------------------------------------------------------------------------------
+ * Greedy placement by variance reduction (A-optimal) and by entropy: the two baselines Krause,
+ * Singh & Guestrin judge the mutual-information placement against.  Sigma = cov_vv (n x n,
+ * symmetric PSD), A the sensors chosen so far (pre-installed ones first),
+ *   C = Sigma - Sigma_{:,A} Sigma_AA^-1 Sigma_{A,:}       the conditional covariance given A.
+ *   VGPOSP_CRIT_VARIANCE  delta_y = sum_{v in T} C_vy^2 / C_yy, which is tr_T(C) - tr_T(C after
+ *                         adding y): the deltas of a run sum to the total reduction of the
+ *                         targets' posterior variance.  T: the targets (default: every location).
+ *   VGPOSP_CRIT_ENTROPY   delta_y = C_yy (the largest conditional variance).
+ * C_yy < threshold gives delta_y = 0 under both rules.  The arg-max runs over S \ A (S: the
+ * candidates, default every location; T need not intersect S); ties go to the lowest index.
+ * Every round scores every free candidate: no lazy cache, the variance rule is not submodular.
+ * Nothing is factored, so a singular PSD Sigma needs no jitter.  The state is nom_y = C_yy,
+ * score_y = sum_{v in T} C_vy^2 and the rows W of the pivoted Cholesky of Sigma given A
+ * (C = Sigma - W^T W); with a the pick, t the 0/1 target mask and w.t the element-wise product a
+ * round does
+ *   w_y      = (Sigma_ay - sum_u W_u[a] W_u[y]) / sqrt(nom_a)        (0 when nom_a < threshold)
+ *   g        = Sigma (w.t) - W^T (W (w.t))                           (the one pass over Sigma)
+ *   score_y -= 2 w_y g_y - w_y^2 |w.t|^2,     nom_y -= w_y^2
+ * from score_y = sum_{v in T} Sigma_vy^2, nom = diag Sigma; entropy keeps nom and W only and never
+ * passes over Sigma.
+ *
+ * Only the entries j >= i of Sigma are read, Sigma is never written, and a non-NULL diag[n]
+ * replaces its diagonal: exactly what a buffer factored in place by vgposp_greedy_init still holds
+ * (Sigma strictly above the diagonal, L^-1 below it) plus the diagonal the caller saved, so both
+ * rules run on the MI path's buffer without a second copy of Sigma.
+ *
+ *   vgposp_symv_upper     y = A x for a symmetric row-major A of which only the entries j >= i are
+ *                         read (diag as above), lda >= n.  Every element of the triangle is loaded
+ *                         once per launch and serves y_i and y_j; 16-byte non-temporal loads when
+ *                         lda is even and A is 16-byte aligned, 8-byte loads otherwise.  No float
+ *                         atomics: per-tile partial sums go to ws
+ *                         (vgposp_symv_upper_workspace_bytes(n) bytes; 0 for n <= 0) and are
+ *                         reduced in a fixed order, so two runs are bit-identical.  No host
+ *                         synchronisation.  n == 0 returns 0 without device work.
+ *   vgposp_symv_upper_sq  the same pass with every entry squared: y_j = sum_i x_i A_ij^2 (the
+ *                         initial score for x = t).
+ *   vgposp_crit_init      nom, score (variance rule: one vgposp_symv_upper_sq pass), the masks.
+ *                         targets / allowed: device byte masks [n] or NULL (= all ones).
+ *   vgposp_crit_step      one round: delta for every location, the arg-max over the free
+ *                         candidates — or forced[j] (device array) when forced is non-NULL, as
+ *                         vgposp_greedy_force —, selected[round] and sel_delta[round] (NULL: not
+ *                         written) = delta of the pick, then the updates above.  Rounds run 0, 1,
+ *                         ... < kmax; with no candidate left selected[round] = -1 and the state is
+ *                         left alone.  The criterion lives in the workspace: a round is the same
+ *                         launch sequence under both rules.
+ *   vgposp_crit_buffers   device pointers into the workspace (each may be NULL): nom [n],
+ *                         score [n], delta [n] (as scored by the last round, before its pick) and
+ *                         W [kmax][n] (row r written by round r).
+ * Argument errors return -(position) before any device work. */
+#define VGPOSP_CRIT_VARIANCE 0
+#define VGPOSP_CRIT_ENTROPY 1
+size_t vgposp_symv_upper_workspace_bytes(int64_t n);
+int vgposp_symv_upper(const double* A, int64_t n, int64_t lda, const double* diag,
+                      const double* x, double* y, void* ws, size_t ws_bytes, void* stream);
+int vgposp_symv_upper_sq(const double* A, int64_t n, int64_t lda, const double* diag,
+                         const double* x, double* y, void* ws, size_t ws_bytes, void* stream);
+size_t vgposp_crit_workspace_bytes(int64_t n, int kmax);
+int vgposp_crit_init(const double* Sigma, int64_t n, int64_t lda, const double* diag, int kmax,
+                     int criterion, double threshold, const unsigned char* targets,
+                     const unsigned char* allowed, void* ws, size_t ws_bytes, void* stream);
+int vgposp_crit_step(const double* Sigma, int64_t n, int64_t lda, const double* diag, int kmax,
+                     int round, const int64_t* forced, int64_t j, int64_t* selected,
+                     double* sel_delta, void* ws, size_t ws_bytes, void* stream);
+int vgposp_crit_buffers(void* ws, int64_t n, int kmax, double** nom, double** score,
+                        double** delta, double** W);
+
+/* ---------------------------------------------------------------------------------------------
  * Exact algorithm 3 at grid sizes where cov_vv cannot be dense (config C4, 128^3): the beta-decay
  * tapered covariance (main_architecture_2_sampledistribution.py:355-421) is a sparse SPD stencil
  * matrix, and snippets_a3.sparse_placement_algorithm_3 (snippets_a3.py:43-364) with tf_nominator /

@@ -243,6 +243,17 @@ SIGNATURES = {
                                      ctypes.POINTER(_c_void_p), ctypes.POINTER(_i64)]),
     "vgposp_greedy_step": (_i32, [_c_void_p, _i64, _i64, _i32, _i32, _i32, _c_void_p, _c_void_p,
                                   _c_void_p, _c_void_p, _size, _c_void_p]),
+    "vgposp_symv_upper_workspace_bytes": (_size, [_i64]),
+    "vgposp_symv_upper": (_i32, [_c_void_p, _i64, _i64, _c_void_p, _c_void_p, _c_void_p,
+                                 _c_void_p, _size, _c_void_p]),
+    "vgposp_symv_upper_sq": (_i32, [_c_void_p, _i64, _i64, _c_void_p, _c_void_p, _c_void_p,
+                                    _c_void_p, _size, _c_void_p]),
+    "vgposp_crit_workspace_bytes": (_size, [_i64, _i32]),
+    "vgposp_crit_init": (_i32, [_c_void_p, _i64, _i64, _c_void_p, _i32, _i32, _f64, _c_void_p,
+                                _c_void_p, _c_void_p, _size, _c_void_p]),
+    "vgposp_crit_step": (_i32, [_c_void_p, _i64, _i64, _c_void_p, _i32, _i32, _c_void_p, _i64,
+                                _c_void_p, _c_void_p, _c_void_p, _size, _c_void_p]),
+    "vgposp_crit_buffers": (_i32, [_c_void_p, _i64, _i32] + [ctypes.POINTER(_c_void_p)] * 4),
 }
 
 _lock = threading.Lock()
@@ -308,6 +319,7 @@ KERNEL_SOURCES = {
     "gemm_f64": ["gemm.hip", "potrf.hip", "common.h", "Makefile"],
     "greedy_trmv": ["greedy.hip", "common.h", "Makefile"],
     "greedy_colsq": ["greedy.hip", "common.h", "Makefile"],
+    "criteria_symv": ["criteria.hip", "common.h", "Makefile"],
     "kernel_matrix": ["kernel_matrix.hip", "psd.h", "common.h", "Makefile"],
     "exact": ["exact_greedy.hip", "psd.h", "common.h", "Makefile"],
 }

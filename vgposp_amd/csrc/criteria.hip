@@ -1,0 +1,514 @@
+// Greedy sensor placement by variance reduction (A-optimal) and by entropy, all on device: the two
+// rules Krause, Singh & Guestrin compare the mutual-information placement (greedy.hip) with.
+//
+// Sigma = cov_vv (n x n, symmetric PSD), A the sensors chosen so far (`placed` first), and
+//   C = Sigma - Sigma_{:,A} Sigma_AA^-1 Sigma_{A,:}         the conditional covariance given A.
+// Per round, for every y:
+//   variance:  delta_y = sum_{v in T} C_vy^2 / C_yy   ( = tr_T(C) - tr_T(C after adding y): the
+//              deltas of a run sum to the total reduction of the targets' posterior variance)
+//   entropy:   delta_y = C_yy
+//   C_yy < threshold -> delta_y = 0 (both rules).  The arg-max runs over S \ A (S the candidates),
+//   ties to the LOWER index (wave_keymax).  Every round scores every free candidate: there is no
+//   lazy cache, the variance rule is not submodular.
+// Nothing is factored: the state is nom_y = C_yy, s_y = sum_{v in T} C_vy^2 and the rows W of the
+// pivoted Cholesky of Sigma given A (W_u = C^{(u)}_{a_u,:} / sqrt(C^{(u)}_{a_u a_u}), so that
+// C = Sigma - W^T W).  With a the pick, w the new row and t the 0/1 target mask, a round does
+//   1. w_y   = (Sigma_ay - sum_u W_u[a] W_u[y]) / sqrt(nom_a)
+//   2. g     = Sigma (w.t) - W^T (W (w.t))                    the one pass over Sigma
+//   3. s_y  -= 2 w_y g_y - w_y^2 |w.t|^2
+//   4. nom_y -= w_y^2
+// from s_y = sum_{v in T} Sigma_vy^2, nom = diag Sigma.  Entropy needs 1 and 4 only.
+//
+// Only the entries j >= i of Sigma are read, and `diag` (when given) replaces its diagonal: that is
+// what a buffer factored in place by vgposp_greedy_init still holds (Sigma strictly above the
+// diagonal, L^-1 below), so the rules run on the MI path's buffer without a second copy of Sigma.
+// The heavy step is vgposp_symv_upper: y = Sigma x from the upper triangle, every element loaded
+// once and used for y_i and for y_j.  No float atomics anywhere: partial sums go to the workspace
+// and are reduced in a fixed order, so two runs are bit-identical; nothing synchronises the host.
+#include <cfloat>
+
+#include "common.h"
+
+namespace vgposp {
+
+constexpr int SY_T = 512;     // rows and columns of a mat-vec tile
+constexpr int SY_TH = 256;    // threads of a tile: one column pair each
+constexpr int CR_CH = 1024;   // candidates per scoring workgroup
+constexpr int CR_B = 256;     // elements per workgroup of the O(n t) kernels
+constexpr int64_t CR_NMAX = (int64_t)1 << 21;
+
+static size_t cr_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+struct SymvWS {
+  double *cpart, *rpart;  // [nt][n] each: column-direction sums per row tile, row-direction sums
+  size_t bytes;           // per column tile
+};
+
+static SymvWS symv_layout(void* base, int64_t n) {
+  SymvWS w{};
+  const size_t slab = cr_align((size_t)ceil_div(n, SY_T) * n * 8);
+  char* p = static_cast<char*>(base);
+  w.cpart = (double*)p;
+  w.rpart = (double*)(p ? p + slab : nullptr);
+  w.bytes = 2 * slab;
+  return w;
+}
+
+// One tile (bi, bj), bj >= bi, of y = A x for symmetric A given by its upper triangle:
+//   cpart[bi][c] = sum_{r in tile rows, r <= c} e(r, c) x[r]        (towards y_c)
+//   rpart[bj][r] = sum_{c in tile columns, c > r} e(r, c) x[c]      (towards y_r)
+// e = A[r][c] (SQ: its square), the diagonal entry taken from `diag` when given and counted once,
+// in the column sum.  Each thread owns the column pair (c, c + 1): one 16-byte non-temporal load
+// per row (VEC: even lda, 16-byte aligned base; else two 8-byte loads), four rows in flight; its
+// column sums stay in registers over the tile's rows, the row sums are wave reductions, one per
+// row, collected in LDS and written once per tile (waves summed in a fixed order).  Below the
+// diagonal nothing is loaded: in the diagonal tile a lane loads row r only for r < c, and the
+// three entries (c, c), (c, c + 1), (c + 1, c + 1) of its pair one by one.  DT: the diagonal tile.
+static_assert(SY_T == 2 * SY_TH && SY_TH == 256, "a column pair per thread, four waves per tile");
+
+template <bool SQ, bool VEC, bool DT>
+__device__ __forceinline__ void symv_tile(const double* __restrict__ A, int64_t n, int64_t lda,
+                                          const double* __restrict__ diag,
+                                          const double* __restrict__ x, int64_t r0, int64_t r1,
+                                          int64_t c, double* __restrict__ cout,
+                                          double* __restrict__ rout, double (*rows)[SY_T]) {
+  typedef double d2v __attribute__((ext_vector_type(2)));
+  const bool in0 = c < n, in1 = c + 1 < n;
+  const double x0 = in0 ? x[c] : 0.0, x1 = in1 ? x[c + 1] : 0.0;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  double s0 = 0.0, s1 = 0.0, u0 = 0.0, u1 = 0.0;  // column c: s0 + s1, column c + 1: u0 + u1
+  // the pair (r, c), (r, c + 1), zero where it is not an entry strictly above the diagonal
+  auto load = [&](int64_t r) -> d2v {
+    d2v m = {0.0, 0.0};
+    if (!in0 || (DT && r > c)) return m;
+    const double* p = A + r * lda + c;
+    if (DT && r == c) {  // (c, c) is added after the loop; (c, c + 1) alone
+      if (in1) m.y = p[1];
+      return m;
+    }
+    if (VEC && in1) return __builtin_nontemporal_load(reinterpret_cast<const d2v*>(p));
+    m.x = __builtin_nontemporal_load(p);
+    if (in1) m.y = __builtin_nontemporal_load(p + 1);
+    return m;
+  };
+  auto row = [&](d2v m, int64_t r, double& a, double& b) {
+    if (SQ) m = m * m;
+    const double xr = x[r];
+    a = fma(m.x, xr, a);
+    b = fma(m.y, xr, b);
+    const double v = wave_sum(fma(m.x, x0, m.y * x1));
+    if (lane == 0) rows[wv][r - r0] = v;
+  };
+  int64_t r = r0;
+  for (; r + 3 < r1; r += 4) {
+    const d2v m0 = load(r), m1 = load(r + 1), m2 = load(r + 2), m3 = load(r + 3);
+    row(m0, r, s0, u0);
+    row(m1, r + 1, s1, u1);
+    row(m2, r + 2, s0, u0);
+    row(m3, r + 3, s1, u1);
+  }
+  for (; r < r1; ++r) row(load(r), r, s0, u0);
+  double sc = s0 + s1, uc = u0 + u1;
+  if (DT && in0) {  // the two diagonal entries of the pair: counted once, in the column sums
+    double d00 = diag ? diag[c] : A[c * lda + c];
+    if (SQ) d00 *= d00;
+    sc = fma(d00, x0, sc);
+    if (in1) {
+      double d11 = diag ? diag[c + 1] : A[(c + 1) * lda + c + 1];
+      if (SQ) d11 *= d11;
+      uc = fma(d11, x1, uc);
+    }
+  }
+  if (in0) cout[c] = sc;
+  if (in1) cout[c + 1] = uc;
+  __syncthreads();
+  for (int64_t i = threadIdx.x; i < r1 - r0; i += SY_TH)
+    rout[r0 + i] = (rows[0][i] + rows[1][i]) + (rows[2][i] + rows[3][i]);
+}
+
+// gate: a device flag or NULL; the kernel does nothing when *gate != 0 (the entropy rule's rounds).
+template <bool SQ, bool VEC>
+__global__ __launch_bounds__(SY_TH) void symv_upper_kernel(
+    const double* __restrict__ A, int64_t n, int64_t lda, const double* __restrict__ diag,
+    const double* __restrict__ x, SymvWS w, const double* __restrict__ gate) {
+  __shared__ double rows[SY_TH / 64][SY_T];  // the waves' row sums
+  const int64_t bi = blockIdx.y, bj = blockIdx.x;
+  if (bj < bi) return;  // below the diagonal
+  if (gate && *gate != 0.0) return;
+  const int64_t r0 = bi * SY_T, r1 = min(r0 + SY_T, n);
+  const int64_t c = bj * SY_T + 2 * threadIdx.x;
+  if (bi == bj)
+    symv_tile<SQ, VEC, true>(A, n, lda, diag, x, r0, r1, c, w.cpart + bi * n, w.rpart + bj * n,
+                             rows);
+  else
+    symv_tile<SQ, VEC, false>(A, n, lda, diag, x, r0, r1, c, w.cpart + bi * n, w.rpart + bj * n,
+                              rows);
+}
+
+// y_i = (sum of the column-direction partials of the row tiles 0 .. i / SY_T, ascending)
+//     + (sum of the row-direction partials of the column tiles i / SY_T .. nt - 1, ascending)
+__global__ __launch_bounds__(CR_B) void symv_reduce_kernel(int64_t n, SymvWS w,
+                                                           double* __restrict__ y,
+                                                           const double* __restrict__ gate) {
+  if (gate && *gate != 0.0) return;
+  const int64_t i = (int64_t)blockIdx.x * CR_B + threadIdx.x;
+  if (i >= n) return;
+  const int64_t nt = (n + SY_T - 1) / SY_T, ti = i / SY_T;
+  double cs = 0.0, rs = 0.0;
+  for (int64_t b = 0; b <= ti; ++b) cs += w.cpart[b * n + i];
+  for (int64_t b = ti; b < nt; ++b) rs += w.rpart[b * n + i];
+  y[i] = cs + rs;
+}
+
+static bool symv_vec(const double* A, int64_t lda) {
+  return (reinterpret_cast<uintptr_t>(A) % 16 == 0) && (lda % 2 == 0);
+}
+
+template <bool SQ>
+static void symv_launch(const double* A, int64_t n, int64_t lda, const double* diag,
+                        const double* x, double* y, const SymvWS& w, const double* gate,
+                        hipStream_t s) {
+  const unsigned nt = (unsigned)ceil_div(n, SY_T);
+  {
+    const double tri = 0.5 * (double)n * (n + 1);
+    ProfScope ps(SQ ? "criteria_symv_sq" : "criteria_symv", s, (SQ ? 5.0 : 4.0) * tri, 8.0 * tri);
+    if (symv_vec(A, lda))
+      hipLaunchKernelGGL((symv_upper_kernel<SQ, true>), dim3(nt, nt), dim3(SY_TH), 0, s, A, n, lda,
+                         diag, x, w, gate);
+    else
+      hipLaunchKernelGGL((symv_upper_kernel<SQ, false>), dim3(nt, nt), dim3(SY_TH), 0, s, A, n,
+                         lda, diag, x, w, gate);
+  }
+  hipLaunchKernelGGL(symv_reduce_kernel, dim3((unsigned)ceil_div(n, CR_B)), dim3(CR_B), 0, s, n, w,
+                     y, gate);
+}
+
+// ---- the greedy rounds ----
+// prm (device): [0] threshold, [1] criterion (the gate of the variance-only kernels: non-zero for
+// entropy).  piv: [0] nom_a of the pick, [1 + u] W_u[a].  dot: [u] = W_u . (w.t) for u <= round
+// (u = round: |w.t|^2), from the per-workgroup partials dpart[u][chunk].
+struct CritWS {
+  double *prm, *nom, *s, *delta, *W, *wt, *g, *tvec, *piv, *dot, *dpart, *fval;
+  long long* fidx;
+  unsigned char* selmask;
+  void* symv;
+  size_t bytes;
+};
+
+static CritWS crit_layout(void* base, int64_t n, int kmax) {
+  CritWS w{};
+  const int64_t nb = ceil_div(n, CR_B), nch = ceil_div(n, CR_CH);
+  char* p = static_cast<char*>(base);
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char* r = p ? p + off : nullptr;
+    off += cr_align(bytes);
+    return r;
+  };
+  w.prm = (double*)take(8 * 8);
+  w.nom = (double*)take(n * 8);
+  w.s = (double*)take(n * 8);
+  w.delta = (double*)take(n * 8);
+  w.W = (double*)take((size_t)kmax * n * 8);
+  w.wt = (double*)take(n * 8);
+  w.g = (double*)take(n * 8);
+  w.tvec = (double*)take(n * 8);
+  w.piv = (double*)take((1 + (size_t)kmax) * 8);
+  w.dot = (double*)take((size_t)kmax * 8);
+  w.dpart = (double*)take((size_t)kmax * nb * 8);
+  w.fval = (double*)take(nch * 8);
+  w.fidx = (long long*)take(nch * 8);
+  w.selmask = (unsigned char*)take(n);
+  w.symv = take(symv_layout(nullptr, n).bytes);
+  w.bytes = off;
+  return w;
+}
+
+// Block-wide (value, index) arg-max for blockDim == 1024; the result is valid in all threads.
+__device__ __forceinline__ void crit_block_keymax(double& v, long long& i) {
+  __shared__ double sv[16];
+  __shared__ long long si[16];
+  wave_keymax(v, i);
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+  __syncthreads();
+  if (l == 0) {
+    sv[w] = v;
+    si[w] = i;
+  }
+  __syncthreads();
+  v = (l < 16) ? sv[l] : -DBL_MAX;
+  i = (l < 16) ? si[l] : -1;
+  wave_keymax(v, i);
+}
+
+// Block-wide sum for blockDim == CR_B, waves added in a fixed order; valid in all threads.
+__device__ __forceinline__ double crit_block_sum(double v) {
+  __shared__ double sw[CR_B / 64];
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (sw[0] + sw[1]) + (sw[2] + sw[3]);
+}
+static_assert(CR_B == 256, "crit_block_sum adds four waves");
+
+__global__ void crit_init_kernel(const double* S, int64_t n, int64_t lda, const double* diag,
+                                 int criterion, double thr, const unsigned char* targets,
+                                 const unsigned char* allowed, CritWS w) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {
+    w.nom[i] = diag ? diag[i] : S[i * lda + i];
+    w.tvec[i] = (!targets || targets[i]) ? 1.0 : 0.0;
+    w.selmask[i] = (allowed && !allowed[i]) ? 1 : 0;
+    w.delta[i] = 0.0;
+    if (criterion != VGPOSP_CRIT_VARIANCE) w.s[i] = 0.0;
+  }
+  if (i == 0) {
+    w.prm[0] = thr;
+    w.prm[1] = criterion == VGPOSP_CRIT_VARIANCE ? 0.0 : 1.0;
+  }
+}
+
+// delta for every location, and the best key of the workgroup over the free candidates.
+__global__ __launch_bounds__(CR_CH) void crit_score_kernel(int64_t n, CritWS w) {
+  const int64_t i = (int64_t)blockIdx.x * CR_CH + threadIdx.x;
+  const double thr = w.prm[0];
+  const bool entropy = w.prm[1] != 0.0;
+  double bv = -DBL_MAX;
+  long long bi = -1;
+  if (i < n) {
+    const double nom = w.nom[i];
+    const double d = nom < thr ? 0.0 : (entropy ? nom : w.s[i] / nom);
+    w.delta[i] = d;
+    if (!w.selmask[i]) {
+      bv = d;
+      bi = i;
+    }
+  }
+  crit_block_keymax(bv, bi);
+  if (threadIdx.x == 0) {
+    w.fval[blockIdx.x] = bv;
+    w.fidx[blockIdx.x] = bi;
+  }
+}
+
+// One workgroup: the arg-max over the chunk keys, or forced[j]; then the pivot data of the pick.
+// No candidate left: selected[round] = -1, and the update kernels of the round do nothing.
+__global__ __launch_bounds__(CR_CH) void crit_select_kernel(int64_t n, int round,
+                                                            const int64_t* forced, int64_t j,
+                                                            int64_t* selected, double* sel_delta,
+                                                            CritWS w) {
+  const int64_t nch = (n + CR_CH - 1) / CR_CH;
+  double v = -DBL_MAX;
+  long long y = -1;
+  if (forced) {
+    y = min(max(forced[j], (int64_t)0), n - 1);  // validated by the host; never outside
+  } else {
+    for (int64_t e = threadIdx.x; e < nch; e += blockDim.x) {
+      if (w.fidx[e] >= 0 && key_gt(w.fval[e], w.fidx[e], v, y)) {
+        v = w.fval[e];
+        y = w.fidx[e];
+      }
+    }
+    crit_block_keymax(v, y);
+  }
+  if (threadIdx.x == 0) {
+    selected[round] = y;
+    if (sel_delta) sel_delta[round] = y >= 0 ? w.delta[y] : 0.0;
+    if (y >= 0) {
+      w.selmask[y] = 1;
+      w.piv[0] = w.nom[y];
+    }
+  }
+  if (y >= 0)
+    for (int t = threadIdx.x; t < round; t += blockDim.x) w.piv[1 + t] = w.W[(int64_t)t * n + y];
+}
+
+// Step 1 and 4: the new row w of W, w.t, and nom -= w^2.  Sigma_ay comes from the upper triangle
+// (column a above row a, row a beyond it).  A pick whose conditional variance is below the
+// threshold adds nothing: w = 0.
+__global__ __launch_bounds__(CR_B) void crit_row_kernel(const double* S, int64_t n, int64_t lda,
+                                                        const double* diag,
+                                                        const int64_t* selected, int round,
+                                                        CritWS w) {
+  const int64_t i = (int64_t)blockIdx.x * CR_B + threadIdx.x;
+  const int64_t a = selected[round];
+  if (i >= n || a < 0) return;
+  double s = i < a ? S[i * lda + a] : (i > a ? S[a * lda + i] : (diag ? diag[a] : S[a * lda + a]));
+  for (int t = 0; t < round; ++t) s -= w.piv[1 + t] * w.W[(int64_t)t * n + i];
+  const double noma = w.piv[0];
+  const double wy = noma >= w.prm[0] && noma > 0.0 ? s / sqrt(noma) : 0.0;
+  w.W[(int64_t)round * n + i] = wy;
+  w.wt[i] = wy * w.tvec[i];
+  w.nom[i] -= wy * wy;
+}
+
+// dpart[u][chunk] = sum over the chunk of W_u[i] (w.t)_i, u = blockIdx.y <= round.
+__global__ __launch_bounds__(CR_B) void crit_dots_kernel(int64_t n, const int64_t* selected,
+                                                         int round, CritWS w) {
+  if (w.prm[1] != 0.0 || selected[round] < 0) return;
+  const int64_t i = (int64_t)blockIdx.x * CR_B + threadIdx.x;
+  const int u = blockIdx.y;
+  double v = i < n ? w.W[(int64_t)u * n + i] * w.wt[i] : 0.0;
+  v = crit_block_sum(v);
+  if (threadIdx.x == 0) w.dpart[(int64_t)u * gridDim.x + blockIdx.x] = v;
+}
+
+// dot[u] = the chunks of dpart[u] in a fixed order: strided per thread, then the block sum.
+__global__ __launch_bounds__(CR_B) void crit_fold_kernel(int64_t nb, const int64_t* selected,
+                                                         int round, CritWS w) {
+  if (w.prm[1] != 0.0 || selected[round] < 0) return;
+  const int u = blockIdx.x;
+  double v = 0.0;
+  for (int64_t e = threadIdx.x; e < nb; e += CR_B) v += w.dpart[(int64_t)u * nb + e];
+  v = crit_block_sum(v);
+  if (threadIdx.x == 0) w.dot[u] = v;
+}
+
+// Step 2 (second half) and 3: g = Sigma (w.t) - W^T dot, s -= 2 w g - w^2 |w.t|^2.
+__global__ __launch_bounds__(CR_B) void crit_update_kernel(int64_t n, const int64_t* selected,
+                                                           int round, CritWS w) {
+  if (w.prm[1] != 0.0 || selected[round] < 0) return;
+  const int64_t i = (int64_t)blockIdx.x * CR_B + threadIdx.x;
+  if (i >= n) return;
+  double g = w.g[i];
+  for (int t = 0; t < round; ++t) g -= w.dot[t] * w.W[(int64_t)t * n + i];
+  w.g[i] = g;
+  const double wy = w.W[(int64_t)round * n + i];
+  w.s[i] -= 2.0 * wy * g - wy * wy * w.dot[round];
+}
+
+}  // namespace vgposp
+
+using namespace vgposp;
+
+extern "C" size_t vgposp_symv_upper_workspace_bytes(int64_t n) {
+  if (n <= 0) return 0;
+  return symv_layout(nullptr, n).bytes;
+}
+
+template <bool SQ>
+static int symv_entry(const char* fn, const double* A, int64_t n, int64_t lda, const double* diag,
+                      const double* x, double* y, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  if (n == 0) return 0;
+  if (A == nullptr) { set_error("%s: bad argument 1", fn); return -1; }
+  if (!(n >= 1 && n <= CR_NMAX)) { set_error("%s: bad argument 2", fn); return -2; }
+  if (lda < n) { set_error("%s: bad argument 3", fn); return -3; }
+  if (x == nullptr) { set_error("%s: bad argument 5", fn); return -5; }
+  if (y == nullptr) { set_error("%s: bad argument 6", fn); return -6; }
+  if (ws == nullptr) { set_error("%s: workspace is null", fn); return VGPOSP_E_WS; }
+  const SymvWS w = symv_layout(ws, n);
+  if (ws_bytes < w.bytes) {
+    set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, w.bytes);
+    return VGPOSP_E_WS;
+  }
+  symv_launch<SQ>(A, n, lda, diag, x, y, w, nullptr, as_stream(stream));
+  VG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int vgposp_symv_upper(const double* A, int64_t n, int64_t lda, const double* diag,
+                                 const double* x, double* y, void* ws, size_t ws_bytes,
+                                 void* stream) {
+  return symv_entry<false>(__func__, A, n, lda, diag, x, y, ws, ws_bytes, stream);
+}
+
+extern "C" int vgposp_symv_upper_sq(const double* A, int64_t n, int64_t lda, const double* diag,
+                                    const double* x, double* y, void* ws, size_t ws_bytes,
+                                    void* stream) {
+  return symv_entry<true>(__func__, A, n, lda, diag, x, y, ws, ws_bytes, stream);
+}
+
+extern "C" size_t vgposp_crit_workspace_bytes(int64_t n, int kmax) {
+  if (n <= 0 || kmax <= 0) return 0;
+  return crit_layout(nullptr, n, kmax).bytes;
+}
+
+extern "C" int vgposp_crit_init(const double* Sigma, int64_t n, int64_t lda, const double* diag,
+                                int kmax, int criterion, double threshold,
+                                const unsigned char* targets, const unsigned char* allowed,
+                                void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  VG_CHECK_ARG(Sigma != nullptr, 1);
+  VG_CHECK_ARG(n >= 1 && n <= CR_NMAX, 2);
+  VG_CHECK_ARG(lda >= n, 3);
+  VG_CHECK_ARG(kmax >= 1 && kmax <= n, 5);
+  VG_CHECK_ARG(criterion == VGPOSP_CRIT_VARIANCE || criterion == VGPOSP_CRIT_ENTROPY, 6);
+  VG_CHECK_ARG(threshold >= 0.0, 7);
+  VG_CHECK_ARG(ws != nullptr, 10);
+  const CritWS w = crit_layout(ws, n, kmax);
+  VG_CHECK_WS(ws_bytes, w.bytes);
+  hipStream_t s = as_stream(stream);
+  hipLaunchKernelGGL(crit_init_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, Sigma, n,
+                     lda, diag, criterion, threshold, targets, allowed, w);
+  VG_LAUNCH_CHECK();
+  if (criterion == VGPOSP_CRIT_VARIANCE) {  // s_y = sum_v t_v Sigma_vy^2
+    symv_launch<true>(Sigma, n, lda, diag, w.tvec, w.s, symv_layout(w.symv, n), nullptr, s);
+    VG_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+extern "C" int vgposp_crit_step(const double* Sigma, int64_t n, int64_t lda, const double* diag,
+                                int kmax, int round, const int64_t* forced, int64_t j,
+                                int64_t* selected, double* sel_delta, void* ws, size_t ws_bytes,
+                                void* stream) {
+  clear_error();
+  VG_CHECK_ARG(Sigma != nullptr, 1);
+  VG_CHECK_ARG(n >= 1 && n <= CR_NMAX, 2);
+  VG_CHECK_ARG(lda >= n, 3);
+  VG_CHECK_ARG(kmax >= 1 && kmax <= n, 5);
+  VG_CHECK_ARG(round >= 0 && round < kmax, 6);
+  VG_CHECK_ARG(forced == nullptr || j >= 0, 8);
+  VG_CHECK_ARG(selected != nullptr, 9);
+  VG_CHECK_ARG(ws != nullptr, 11);
+  const CritWS w = crit_layout(ws, n, kmax);
+  VG_CHECK_WS(ws_bytes, w.bytes);
+  hipStream_t s = as_stream(stream);
+  const unsigned nb = (unsigned)ceil_div(n, CR_B);
+  {
+    ProfScope ps("criteria_select", s, 0.0, 8.0 * 3.0 * n);
+    hipLaunchKernelGGL(crit_score_kernel, dim3((unsigned)ceil_div(n, CR_CH)), dim3(CR_CH), 0, s, n,
+                       w);
+    hipLaunchKernelGGL(crit_select_kernel, dim3(1), dim3(CR_CH), 0, s, n, round, forced, j,
+                       selected, sel_delta, w);
+    VG_LAUNCH_CHECK();
+  }
+  {
+    ProfScope ps("criteria_row", s, 0.0, 8.0 * (double)n * (5 + round));
+    hipLaunchKernelGGL(crit_row_kernel, dim3(nb), dim3(CR_B), 0, s, Sigma, n, lda, diag, selected,
+                       round, w);
+    VG_LAUNCH_CHECK();
+  }
+  // the variance rule's part: every kernel below returns at once under the entropy rule (the
+  // criterion lives in the workspace, so the launch sequence does not depend on it)
+  const double* gate = w.prm + 1;
+  hipLaunchKernelGGL(crit_dots_kernel, dim3(nb, (unsigned)round + 1), dim3(CR_B), 0, s, n,
+                     selected, round, w);
+  hipLaunchKernelGGL(crit_fold_kernel, dim3((unsigned)round + 1), dim3(CR_B), 0, s, (int64_t)nb,
+                     selected, round, w);
+  VG_LAUNCH_CHECK();
+  symv_launch<false>(Sigma, n, lda, diag, w.wt, w.g, symv_layout(w.symv, n), gate, s);
+  VG_LAUNCH_CHECK();
+  {
+    ProfScope ps("criteria_update", s, 0.0, 8.0 * (double)n * (4 + round));
+    hipLaunchKernelGGL(crit_update_kernel, dim3(nb), dim3(CR_B), 0, s, n, selected, round, w);
+    VG_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+extern "C" int vgposp_crit_buffers(void* ws, int64_t n, int kmax, double** nom, double** score,
+                                   double** delta, double** W) {
+  clear_error();
+  VG_CHECK_ARG(ws != nullptr, 1);
+  VG_CHECK_ARG(n >= 1, 2);
+  VG_CHECK_ARG(kmax >= 1, 3);
+  const CritWS w = crit_layout(ws, n, kmax);
+  if (nom) *nom = w.nom;
+  if (score) *score = w.s;
+  if (delta) *delta = w.delta;
+  if (W) *W = w.W;
+  return 0;
+}

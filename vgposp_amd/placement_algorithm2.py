@@ -300,8 +300,26 @@ def dg_create_random_cov(n, rng=None):
 
 
 def placement_from_points(X, k, kind="eq", amp=1.0, ls=1.0, noise=1e-2, jitter=1e-6, lazy=True,
-                          candidates=None, placed=None):
-    """Assemble Sigma = K(X, X) + (noise + jitter) I on device and place k sensors."""
+                          candidates=None, placed=None, criterion="mi", targets=None):
+    """Assemble Sigma = K(X, X) + (noise + jitter) I on device and place k sensors.
+
+    ``criterion``: ``"mi"`` (mutual information, the default), or ``"variance"`` / ``"entropy"``
+    (placement_criteria.CriterionPlacement on the same assembled matrix).  ``targets``, the
+    locations whose posterior variance counts, belongs to ``"variance"`` alone."""
+    if criterion == "mi":
+        if targets is not None:
+            raise ValueError("targets apply to criterion='variance'; the mutual-information "
+                             "placement has no target set")
+    else:
+        from .placement_criteria import CRITERIA
+        if criterion not in CRITERIA:
+            raise ValueError(f"unknown criterion {criterion!r}; expected 'mi' or one of "
+                             f"{list(CRITERIA)}")
     K = linalg.kernel_matrix(kind, X, None, amp, ls, diag_shift=noise + jitter)[0]
+    if criterion != "mi":
+        from .placement_criteria import CriterionPlacement
+        g = CriterionPlacement(K, k, criterion, candidates=candidates, placed=placed,
+                               targets=targets).run(k)
+        return g.result()[0]
     g = GreedyPlacement(K, k, candidates=candidates, placed=placed).run(k, lazy=lazy)
     return g.result()[0]

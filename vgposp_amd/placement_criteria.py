@@ -1,0 +1,183 @@
+"""Greedy sensor placement by variance reduction (A-optimal) and by entropy on MI355X: the two
+baselines Krause, Singh & Guestrin judge the mutual-information placement against, and the rule
+to use when the posterior variance of the field is what matters.
+
+With Sigma = ``cov_vv``, A the sensors chosen so far (``placed`` included) and
+C = Sigma - Sigma_{:,A} Sigma_AA^-1 Sigma_{A,:} the conditional covariance:
+
+* ``criterion="variance"``: delta_y = sum_{v in T} C_vy^2 / C_yy — the drop of the targets' total
+  posterior variance when y is added, so the deltas of a run sum to the total reduction;
+* ``criterion="entropy"``:  delta_y = C_yy — the largest conditional variance.
+
+C_yy < ``threshold`` gives delta_y = 0; the arg-max runs over ``candidates`` minus A, ties to the
+lowest index; every round scores every free candidate.  ``candidates`` and ``placed`` mean what
+they mean in ``placement_algorithm_2``; ``targets`` (index list or boolean mask, default every
+location) are the locations whose uncertainty counts and need not intersect the candidates.
+
+Nothing is factored (csrc/criteria.hip keeps nom = diag C, s_y = sum_T C_vy^2 and the pivoted
+Cholesky rows W; the variance rule passes once per round over the upper triangle of Sigma with
+``vgposp_symv_upper``), so a singular PSD covariance needs no jitter, and Sigma is only read.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+import torch
+
+from . import linalg
+from ._lib import call, query
+from .constraints import _index_array, normalize_constraints
+from .linalg import _p, _stream
+
+CRITERIA = {"variance": 0, "entropy": 1}   # VGPOSP_CRIT_VARIANCE / VGPOSP_CRIT_ENTROPY
+
+
+def normalize_targets(N, targets):
+    """-> bool mask [N], or None when ``targets`` is None (every location counts).  ``targets`` is
+    an index list or a boolean mask of length N; raises ValueError as
+    ``constraints.normalize_constraints`` does for ``candidates``."""
+    if targets is None:
+        return None
+    t = np.asarray(targets)
+    if t.dtype == np.bool_:
+        if t.shape != (N,):
+            raise ValueError(f"a targets mask must have length {N}, got shape {t.shape}")
+        return t.copy()
+    mask = np.zeros(N, dtype=bool)
+    mask[_index_array("targets", targets, N)] = True
+    return mask
+
+
+def _criterion_id(criterion):
+    try:
+        return CRITERIA[criterion]
+    except (KeyError, TypeError):
+        raise ValueError(f"unknown criterion {criterion!r}; expected one of {list(CRITERIA)}")
+
+
+class CriterionPlacement:
+    """Device-resident greedy placement by ``criterion`` on an [N, N] covariance held in HBM.
+
+    ``Sigma`` (float64, unit column stride, row stride >= N) is only read, never copied, and only
+    its entries j >= i: a buffer that ``GreedyPlacement.init()`` factored in place serves as well
+    when ``diag`` is the diagonal of Sigma saved before.  ``placed`` runs as forced rounds in
+    ``init()``; ``kmax``, ``rounds`` and ``result()`` count the new picks only.
+    """
+
+    def __init__(self, Sigma, kmax, criterion="variance", candidates=None, placed=None,
+                 targets=None, threshold=1e-8, diag=None):
+        self.criterion = criterion
+        self.crit = _criterion_id(criterion)
+        if (isinstance(Sigma, torch.Tensor) and Sigma.device.type == "cuda" and Sigma.dim() == 2
+                and Sigma.dtype == torch.float64 and Sigma.stride(1) == 1
+                and Sigma.stride(0) >= Sigma.shape[1]):
+            S = Sigma                                # a view with a row pitch: used where it is
+        else:
+            S = linalg.as_device(Sigma)
+        if S.dim() != 2 or S.shape[0] != S.shape[1]:
+            raise ValueError("cov_vv must be a square matrix")
+        self.S = S
+        self.N = self.n = int(S.shape[0])
+        if not (1 <= kmax <= self.N):
+            raise ValueError(f"k must be in [1, {self.N}], got {kmax}")
+        self.allowed, self.placed = normalize_constraints(self.N, kmax, candidates, placed)
+        self.targets = normalize_targets(self.N, targets)
+        if self.targets is not None and self.crit != CRITERIA["variance"]:
+            raise ValueError("targets apply to criterion='variance' only")
+        if not threshold >= 0.0:
+            raise ValueError(f"threshold must not be negative, got {threshold}")
+        self.threshold = float(threshold)
+        self.m = len(self.placed)
+        self.k = int(kmax)
+        self.kmax = self.k + self.m
+        dev = S.device
+        self.diag = None
+        if diag is not None:
+            self.diag = linalg.as_device(diag).reshape(-1)
+            if self.diag.numel() != self.N:
+                raise ValueError(f"diag must have length {self.N}, got {self.diag.numel()}")
+
+        def mask(b):
+            return None if b is None else torch.as_tensor(b.astype(np.uint8), device=dev)
+        self._allowed_dev, self._targets_dev = mask(self.allowed), mask(self.targets)
+        self._placed_dev = (torch.as_tensor(self.placed, dtype=torch.int64, device=dev)
+                            if self.m else None)
+        self.ws = linalg.workspace(query("vgposp_crit_workspace_bytes", self.n, self.kmax))
+        self.selected = torch.full((self.kmax,), -1, dtype=torch.int64, device=dev)
+        self.sel_delta = torch.zeros(self.kmax, dtype=torch.float64, device=dev)
+        self.rounds = 0
+
+    def _step(self, r, forced=None, j=0):
+        call("vgposp_crit_step", _p(self.S), self.n, self.S.stride(0), _p(self.diag), self.kmax,
+             r, _p(forced), j, _p(self.selected), _p(self.sel_delta), _p(self.ws),
+             self.ws.numel(), _stream())
+
+    def init(self):
+        call("vgposp_crit_init", _p(self.S), self.n, self.S.stride(0), _p(self.diag), self.kmax,
+             self.crit, self.threshold, _p(self._targets_dev), _p(self._allowed_dev), _p(self.ws),
+             self.ws.numel(), _stream())
+        for j in range(self.m):
+            self._step(j, self._placed_dev, j)
+        self.rounds = 0
+        return self
+
+    def step(self):
+        if self.rounds >= self.k:
+            raise RuntimeError("all k sensors already placed")
+        self._step(self.m + self.rounds)
+        self.rounds += 1
+
+    def run(self, k=None):
+        k = self.k if k is None else k
+        self.init()
+        for _ in range(k):
+            self.step()
+        return self
+
+    def state(self):
+        """Device views into the workspace: ``nom`` [N] (C_yy), ``s`` [N] (sum_T C_vy^2), ``delta``
+        [N] (as scored by the last round, before its pick) and ``W`` [placed + rounds, N]."""
+        ptr = [ctypes.c_void_p() for _ in range(4)]
+        call("vgposp_crit_buffers", _p(self.ws), self.n, self.kmax, *map(ctypes.byref, ptr))
+
+        def view(p, count):
+            off = p.value - self.ws.data_ptr()
+            return self.ws[off:off + 8 * count].view(torch.float64)
+        rows = self.m + self.rounds
+        return {"nom": view(ptr[0], self.N), "s": view(ptr[1], self.N),
+                "delta": view(ptr[2], self.N), "W": view(ptr[3], rows * self.N).view(rows, self.N)}
+
+    def result(self):
+        """``(picks, deltas)``: the new picks (host list of np.int64; ``placed`` is not part of
+        them) and the delta each had when it was picked."""
+        new = slice(self.m, self.m + self.rounds)
+        sel = self.selected[new].cpu().numpy()
+        if (sel < 0).any():
+            raise RuntimeError("greedy placement found no candidate (all deltas NaN?)")
+        return [np.int64(s) for s in sel], self.sel_delta[new].cpu().numpy()
+
+
+def _place(cov_vv, k, criterion, candidates, placed, targets):
+    if k < 1:
+        N = int(np.shape(cov_vv)[0])
+        normalize_constraints(N, max(int(k), 0), candidates, placed)
+        normalize_targets(N, targets)
+        return []
+    g = CriterionPlacement(cov_vv, k, criterion, candidates=candidates, placed=placed,
+                           targets=targets)
+    return g.run(k).result()[0]
+
+
+def placement_variance_reduction(cov_vv, k, candidates=None, placed=None, targets=None):
+    """k sensors by greedy variance reduction: each pick minimises the total posterior variance of
+    ``targets`` (default: every location).  Returns a list of ``np.int64`` like
+    ``placement_algorithm_2``; ``candidates`` / ``placed`` as there.  A singular PSD ``cov_vv``
+    needs no retry: nothing is factored."""
+    return _place(cov_vv, k, "variance", candidates, placed, targets)
+
+
+def placement_entropy(cov_vv, k, candidates=None, placed=None):
+    """k sensors by the entropy rule: each pick has the largest conditional variance given the
+    sensors so far (the pivots of a diagonal-pivoted Cholesky of ``cov_vv``)."""
+    return _place(cov_vv, k, "entropy", candidates, placed, None)
