@@ -657,6 +657,54 @@ int vgposp_crit_buffers(void* ws, int64_t n, int kmax, double** nom, double** sc
                         double** delta, double** W);
 
 /* ---------------------------------------------------------------------------------------------
+ * The variance rule for targets outside V: sensors go on the n locations of Sigma, the field is
+ * judged at P targets that are no rows of Sigma (a finer mesh, the latent field without sensor
+ * noise).  R = cross_cov (P x n, row-major fp64, row pitch ldr >= n, only read) is the covariance
+ * between the targets and the locations, omega [P] >= 0 the targets' weights (NULL: all ones),
+ *   D = R - R_{:,A} Sigma_AA^-1 Sigma_{A,:},     delta_y = sum_v omega_v D_vy^2 / C_yy:
+ * the drop of the weighted total posterior variance of the targets when y is added.  Threshold,
+ * candidate mask, forced rounds, ties and "no candidate left -> -1" are those of
+ * vgposp_crit_step.  The state is nom, score, W as above and the target-side rows U [kmax][P]
+ * (D = R - U^T W); with a the pick a round does
+ *   w_y      as above
+ *   u_v      = (R_va - sum_t U_t[v] W_t[a]) / sqrt(nom_a)            (0 when nom_a < threshold)
+ *   g        = R^T (omega.u) - W^T (U (omega.u))                     (the one pass over R)
+ *   score_y -= 2 w_y g_y - w_y^2 sum_v omega_v u_v^2,     nom_y -= w_y^2
+ * from score_y = sum_v omega_v R_vy^2, nom = diag Sigma.  sum_r U_r[v]^2 is the variance removed
+ * at target v.  Nothing is factored, so a singular joint covariance works.
+ *
+ *   vgposp_gemv_t         y_j = sum_v x_v R_vj for a P x n row-major R, ldr >= n: a pure stream of
+ *                         8 P n bytes, 16-byte non-temporal loads when ldr is even and R is
+ *                         16-byte aligned, 8-byte loads otherwise.  No float atomics: one partial
+ *                         per (512-row tile, column) goes to ws
+ *                         (vgposp_gemv_t_workspace_bytes(P, n) bytes; 0 when P <= 0 or n <= 0) and
+ *                         the partials are added in ascending row-tile order, so two runs are
+ *                         bit-identical.  No host synchronisation.  P == 0 or n == 0 returns 0
+ *                         without device work.
+ *   vgposp_gemv_t_sq      the same pass with every entry squared: y_j = sum_v x_v R_vj^2.
+ *   vgposp_critx_init     nom, omega, score (one vgposp_gemv_t_sq pass), the candidate mask.
+ *   vgposp_critx_step     one round, as vgposp_crit_step.
+ *   vgposp_critx_buffers  device pointers into the workspace (each may be NULL): nom, score,
+ *                         delta [n], W [kmax][n], U [kmax][P] (row r written by round r).
+ * Argument errors return -(position) before any device work. */
+size_t vgposp_gemv_t_workspace_bytes(int64_t P, int64_t n);
+int vgposp_gemv_t(const double* R, int64_t P, int64_t n, int64_t ldr, const double* x, double* y,
+                  void* ws, size_t ws_bytes, void* stream);
+int vgposp_gemv_t_sq(const double* R, int64_t P, int64_t n, int64_t ldr, const double* x,
+                     double* y, void* ws, size_t ws_bytes, void* stream);
+size_t vgposp_critx_workspace_bytes(int64_t n, int64_t P, int kmax);
+int vgposp_critx_init(const double* Sigma, int64_t n, int64_t lda, const double* diag,
+                      const double* R, int64_t P, int64_t ldr, const double* weights, int kmax,
+                      double threshold, const unsigned char* allowed, void* ws, size_t ws_bytes,
+                      void* stream);
+int vgposp_critx_step(const double* Sigma, int64_t n, int64_t lda, const double* diag,
+                      const double* R, int64_t P, int64_t ldr, int kmax, int round,
+                      const int64_t* forced, int64_t j, int64_t* selected, double* sel_delta,
+                      void* ws, size_t ws_bytes, void* stream);
+int vgposp_critx_buffers(void* ws, int64_t n, int64_t P, int kmax, double** nom, double** score,
+                         double** delta, double** W, double** U);
+
+/* ---------------------------------------------------------------------------------------------
  * Exact algorithm 3 at grid sizes where cov_vv cannot be dense (config C4, 128^3): the beta-decay
  * tapered covariance (main_architecture_2_sampledistribution.py:355-421) is a sparse SPD stencil
  * matrix, and snippets_a3.sparse_placement_algorithm_3 (snippets_a3.py:43-364) with tf_nominator /

@@ -254,6 +254,19 @@ SIGNATURES = {
     "vgposp_crit_step": (_i32, [_c_void_p, _i64, _i64, _c_void_p, _i32, _i32, _c_void_p, _i64,
                                 _c_void_p, _c_void_p, _c_void_p, _size, _c_void_p]),
     "vgposp_crit_buffers": (_i32, [_c_void_p, _i64, _i32] + [ctypes.POINTER(_c_void_p)] * 4),
+    "vgposp_gemv_t_workspace_bytes": (_size, [_i64, _i64]),
+    "vgposp_gemv_t": (_i32, [_c_void_p, _i64, _i64, _i64, _c_void_p, _c_void_p, _c_void_p, _size,
+                             _c_void_p]),
+    "vgposp_gemv_t_sq": (_i32, [_c_void_p, _i64, _i64, _i64, _c_void_p, _c_void_p, _c_void_p,
+                                _size, _c_void_p]),
+    "vgposp_critx_workspace_bytes": (_size, [_i64, _i64, _i32]),
+    "vgposp_critx_init": (_i32, [_c_void_p, _i64, _i64, _c_void_p, _c_void_p, _i64, _i64,
+                                 _c_void_p, _i32, _f64, _c_void_p, _c_void_p, _size, _c_void_p]),
+    "vgposp_critx_step": (_i32, [_c_void_p, _i64, _i64, _c_void_p, _c_void_p, _i64, _i64, _i32,
+                                 _i32, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _size,
+                                 _c_void_p]),
+    "vgposp_critx_buffers": (_i32, [_c_void_p, _i64, _i64, _i32]
+                             + [ctypes.POINTER(_c_void_p)] * 5),
 }
 
 _lock = threading.Lock()
@@ -320,6 +333,8 @@ KERNEL_SOURCES = {
     "greedy_trmv": ["greedy.hip", "common.h", "Makefile"],
     "greedy_colsq": ["greedy.hip", "common.h", "Makefile"],
     "criteria_symv": ["criteria.hip", "common.h", "Makefile"],
+    "criteria_gemv_t": ["criteria.hip", "common.h", "Makefile"],
+    "criteria_gemv_t_sq": ["criteria.hip", "common.h", "Makefile"],
     "kernel_matrix": ["kernel_matrix.hip", "psd.h", "common.h", "Makefile"],
     "exact": ["exact_greedy.hip", "psd.h", "common.h", "Makefile"],
 }

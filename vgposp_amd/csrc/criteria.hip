@@ -378,6 +378,161 @@ __global__ __launch_bounds__(CR_B) void crit_update_kernel(int64_t n, const int6
   w.s[i] -= 2.0 * wy * g - wy * wy * w.dot[round];
 }
 
+// ---- targets outside V: the variance rule on a rectangular cross-covariance ----
+// R = cross_cov (P x n, row-major, pitch ldr >= n, only read): the covariance between the P targets
+// and the n locations; omega [P] >= 0 the targets' weights.  With D = R - R_{:,A} Sigma_AA^-1
+// Sigma_{A,:} the rule is delta_y = sum_v omega_v D_vy^2 / C_yy.  The state gains the target-side
+// rows U [kmax][P] (D = R - U^T W); with a the pick, a round does
+//   1. w_y as above
+//   2. u_v   = (R_va - sum_t U_t[v] W_t[a]) / sqrt(nom_a)          (0 when nom_a < threshold)
+//   3. g     = R^T (omega.u) - W^T (U (omega.u))                   the one pass over R
+//   4. s_y  -= 2 w_y g_y - w_y^2 sum_v omega_v u_v^2
+//   5. nom_y -= w_y^2
+// from s_y = sum_v omega_v R_vy^2, nom = diag Sigma.  sum_r U_r[v]^2 is the variance removed at v.
+// The location side is the CritWS of the in-V rule with t = 1, so scoring, selection, the w-row
+// and the update are its kernels; the dots U_t . (omega.u) are crit_dots / crit_fold on a view of
+// the workspace whose W / wt / dpart are the target side's U / omega.u / partials (n -> P).
+constexpr int64_t CRX_PMAX = (int64_t)1 << 24;  // 32,768 row tiles: within a grid's y extent
+
+static size_t gemv_t_bytes(int64_t P, int64_t n) {
+  return cr_align((size_t)ceil_div(P, SY_T) * n * 8);
+}
+
+// One 512 x 512 tile of y = R^T x (SQ: of the squared entries): symv_tile without its row-direction
+// half.  part[blockIdx.y][c] = sum over the tile's rows of e(r, c) x[r]; a thread owns the column
+// pair (c, c + 1), one 16-byte non-temporal load per row (VEC) or two 8-byte ones, four rows in
+// flight, x[r] workgroup-uniform, the two column sums in registers.  Nothing is shared between
+// threads, so there is no LDS and no barrier.
+template <bool SQ, bool VEC>
+__global__ __launch_bounds__(SY_TH) void gemv_t_kernel(const double* __restrict__ R, int64_t P,
+                                                       int64_t n, int64_t ldr,
+                                                       const double* __restrict__ x,
+                                                       double* __restrict__ part,
+                                                       const double* __restrict__ gate) {
+  typedef double d2v __attribute__((ext_vector_type(2)));
+  if (gate && *gate != 0.0) return;
+  const int64_t r0 = (int64_t)blockIdx.y * SY_T, r1 = min(r0 + SY_T, P);
+  const int64_t c = (int64_t)blockIdx.x * SY_T + 2 * threadIdx.x;
+  if (c >= n) return;
+  const bool in1 = c + 1 < n;
+  auto load = [&](int64_t r) -> d2v {
+    const double* p = R + r * ldr + c;
+    if (VEC && in1) return __builtin_nontemporal_load(reinterpret_cast<const d2v*>(p));
+    d2v m = {__builtin_nontemporal_load(p), 0.0};
+    if (in1) m.y = __builtin_nontemporal_load(p + 1);
+    return m;
+  };
+  auto row = [&](d2v m, int64_t r, double& a, double& b) {
+    if (SQ) m = m * m;
+    const double xr = x[r];
+    a = fma(m.x, xr, a);
+    b = fma(m.y, xr, b);
+  };
+  double s0 = 0.0, s1 = 0.0, u0 = 0.0, u1 = 0.0;  // column c: s0 + s1, column c + 1: u0 + u1
+  int64_t r = r0;
+  for (; r + 3 < r1; r += 4) {
+    const d2v m0 = load(r), m1 = load(r + 1), m2 = load(r + 2), m3 = load(r + 3);
+    row(m0, r, s0, u0);
+    row(m1, r + 1, s1, u1);
+    row(m2, r + 2, s0, u0);
+    row(m3, r + 3, s1, u1);
+  }
+  for (; r < r1; ++r) row(load(r), r, s0, u0);
+  double* out = part + (int64_t)blockIdx.y * n;
+  out[c] = s0 + s1;
+  if (in1) out[c + 1] = u0 + u1;
+}
+
+// y_j = the partials of the row tiles 0 .. nt - 1, ascending.
+__global__ __launch_bounds__(CR_B) void gemv_t_reduce_kernel(int64_t nt, int64_t n,
+                                                             const double* __restrict__ part,
+                                                             double* __restrict__ y,
+                                                             const double* __restrict__ gate) {
+  if (gate && *gate != 0.0) return;
+  const int64_t j = (int64_t)blockIdx.x * CR_B + threadIdx.x;
+  if (j >= n) return;
+  double s = 0.0;
+#pragma unroll 8
+  for (int64_t b = 0; b < nt; ++b) s += part[b * n + j];
+  y[j] = s;
+}
+
+template <bool SQ>
+static void gemv_t_launch(const double* R, int64_t P, int64_t n, int64_t ldr, const double* x,
+                          double* y, double* part, const double* gate, hipStream_t s) {
+  const unsigned ntr = (unsigned)ceil_div(P, SY_T), ntc = (unsigned)ceil_div(n, SY_T);
+  {
+    const double pn = (double)P * (double)n;
+    ProfScope ps(SQ ? "criteria_gemv_t_sq" : "criteria_gemv_t", s, (SQ ? 3.0 : 2.0) * pn,
+                 8.0 * pn);
+    if (symv_vec(R, ldr))
+      hipLaunchKernelGGL((gemv_t_kernel<SQ, true>), dim3(ntc, ntr), dim3(SY_TH), 0, s, R, P, n,
+                         ldr, x, part, gate);
+    else
+      hipLaunchKernelGGL((gemv_t_kernel<SQ, false>), dim3(ntc, ntr), dim3(SY_TH), 0, s, R, P, n,
+                         ldr, x, part, gate);
+  }
+  hipLaunchKernelGGL(gemv_t_reduce_kernel, dim3((unsigned)ceil_div(n, CR_B)), dim3(CR_B), 0, s,
+                     (int64_t)ntr, n, part, y, gate);
+}
+
+// c: the location side (its tvec all ones, its dot shared with the target side).  wu = omega.u;
+// dpart [kmax][ceil(P / CR_B)]: the partials of the dots over P; gemv: the partials of the pass.
+struct CritXWS {
+  CritWS c;
+  double *U, *wu, *omega, *dpart, *gemv;
+  size_t bytes;
+};
+
+static CritXWS critx_layout(void* base, int64_t n, int64_t P, int kmax) {
+  CritXWS w{};
+  w.c = crit_layout(base, n, kmax);
+  char* p = static_cast<char*>(base);
+  size_t off = w.c.bytes;
+  auto take = [&](size_t bytes) {
+    char* r = p ? p + off : nullptr;
+    off += cr_align(bytes);
+    return (double*)r;
+  };
+  w.U = take((size_t)kmax * P * 8);
+  w.wu = take((size_t)P * 8);
+  w.omega = take((size_t)P * 8);
+  w.dpart = take((size_t)kmax * ceil_div(P, CR_B) * 8);
+  w.gemv = take(gemv_t_bytes(P, n));
+  w.bytes = off;
+  return w;
+}
+
+// The workspace as crit_dots / crit_fold see the target side: rows U, vector omega.u, length P.
+static CritWS critx_target_view(const CritXWS& w) {
+  CritWS t = w.c;
+  t.W = w.U;
+  t.wt = w.wu;
+  t.dpart = w.dpart;
+  return t;
+}
+
+__global__ void critx_init_kernel(int64_t P, const double* weights, CritXWS w) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v < P) w.omega[v] = weights ? weights[v] : 1.0;
+}
+
+// Step 2: the new row u of U and omega.u; R_va is a strided read of column a.  As crit_row_kernel:
+// a pick below the threshold adds nothing.
+__global__ __launch_bounds__(CR_B) void critx_urow_kernel(const double* R, int64_t P, int64_t ldr,
+                                                          const int64_t* selected, int round,
+                                                          CritXWS w) {
+  const int64_t v = (int64_t)blockIdx.x * CR_B + threadIdx.x;
+  const int64_t a = selected[round];
+  if (v >= P || a < 0) return;
+  double s = R[v * ldr + a];
+  for (int t = 0; t < round; ++t) s -= w.c.piv[1 + t] * w.U[(int64_t)t * P + v];
+  const double noma = w.c.piv[0];
+  const double u = noma >= w.c.prm[0] && noma > 0.0 ? s / sqrt(noma) : 0.0;
+  w.U[(int64_t)round * P + v] = u;
+  w.wu[v] = w.omega[v] * u;
+}
+
 }  // namespace vgposp
 
 using namespace vgposp;
@@ -510,5 +665,146 @@ extern "C" int vgposp_crit_buffers(void* ws, int64_t n, int kmax, double** nom, 
   if (score) *score = w.s;
   if (delta) *delta = w.delta;
   if (W) *W = w.W;
+  return 0;
+}
+
+extern "C" size_t vgposp_gemv_t_workspace_bytes(int64_t P, int64_t n) {
+  if (P <= 0 || n <= 0) return 0;
+  return gemv_t_bytes(P, n);
+}
+
+template <bool SQ>
+static int gemv_t_entry(const char* fn, const double* R, int64_t P, int64_t n, int64_t ldr,
+                        const double* x, double* y, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  if (P == 0 || n == 0) return 0;
+  if (R == nullptr) { set_error("%s: bad argument 1", fn); return -1; }
+  if (!(P >= 1 && P <= CRX_PMAX)) { set_error("%s: bad argument 2", fn); return -2; }
+  if (!(n >= 1 && n <= CR_NMAX)) { set_error("%s: bad argument 3", fn); return -3; }
+  if (ldr < n) { set_error("%s: bad argument 4", fn); return -4; }
+  if (x == nullptr) { set_error("%s: bad argument 5", fn); return -5; }
+  if (y == nullptr) { set_error("%s: bad argument 6", fn); return -6; }
+  if (ws == nullptr) { set_error("%s: workspace is null", fn); return VGPOSP_E_WS; }
+  const size_t need = gemv_t_bytes(P, n);
+  if (ws_bytes < need) {
+    set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, need);
+    return VGPOSP_E_WS;
+  }
+  gemv_t_launch<SQ>(R, P, n, ldr, x, y, static_cast<double*>(ws), nullptr, as_stream(stream));
+  VG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int vgposp_gemv_t(const double* R, int64_t P, int64_t n, int64_t ldr, const double* x,
+                             double* y, void* ws, size_t ws_bytes, void* stream) {
+  return gemv_t_entry<false>(__func__, R, P, n, ldr, x, y, ws, ws_bytes, stream);
+}
+
+extern "C" int vgposp_gemv_t_sq(const double* R, int64_t P, int64_t n, int64_t ldr,
+                                const double* x, double* y, void* ws, size_t ws_bytes,
+                                void* stream) {
+  return gemv_t_entry<true>(__func__, R, P, n, ldr, x, y, ws, ws_bytes, stream);
+}
+
+extern "C" size_t vgposp_critx_workspace_bytes(int64_t n, int64_t P, int kmax) {
+  if (n <= 0 || P <= 0 || kmax <= 0) return 0;
+  return critx_layout(nullptr, n, P, kmax).bytes;
+}
+
+extern "C" int vgposp_critx_init(const double* Sigma, int64_t n, int64_t lda, const double* diag,
+                                 const double* R, int64_t P, int64_t ldr, const double* weights,
+                                 int kmax, double threshold, const unsigned char* allowed,
+                                 void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  VG_CHECK_ARG(Sigma != nullptr, 1);
+  VG_CHECK_ARG(n >= 1 && n <= CR_NMAX, 2);
+  VG_CHECK_ARG(lda >= n, 3);
+  VG_CHECK_ARG(R != nullptr, 5);
+  VG_CHECK_ARG(P >= 1 && P <= CRX_PMAX, 6);
+  VG_CHECK_ARG(ldr >= n, 7);
+  VG_CHECK_ARG(kmax >= 1 && kmax <= n, 9);
+  VG_CHECK_ARG(threshold >= 0.0, 10);
+  VG_CHECK_ARG(ws != nullptr, 12);
+  const CritXWS w = critx_layout(ws, n, P, kmax);
+  VG_CHECK_WS(ws_bytes, w.bytes);
+  hipStream_t s = as_stream(stream);
+  hipLaunchKernelGGL(crit_init_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, Sigma, n,
+                     lda, diag, VGPOSP_CRIT_VARIANCE, threshold, nullptr, allowed, w.c);
+  hipLaunchKernelGGL(critx_init_kernel, dim3((unsigned)ceil_div(P, 256)), dim3(256), 0, s, P,
+                     weights, w);
+  VG_LAUNCH_CHECK();
+  // s_y = sum_v omega_v R_vy^2
+  gemv_t_launch<true>(R, P, n, ldr, w.omega, w.c.s, w.gemv, nullptr, s);
+  VG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int vgposp_critx_step(const double* Sigma, int64_t n, int64_t lda, const double* diag,
+                                 const double* R, int64_t P, int64_t ldr, int kmax, int round,
+                                 const int64_t* forced, int64_t j, int64_t* selected,
+                                 double* sel_delta, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  VG_CHECK_ARG(Sigma != nullptr, 1);
+  VG_CHECK_ARG(n >= 1 && n <= CR_NMAX, 2);
+  VG_CHECK_ARG(lda >= n, 3);
+  VG_CHECK_ARG(R != nullptr, 5);
+  VG_CHECK_ARG(P >= 1 && P <= CRX_PMAX, 6);
+  VG_CHECK_ARG(ldr >= n, 7);
+  VG_CHECK_ARG(kmax >= 1 && kmax <= n, 8);
+  VG_CHECK_ARG(round >= 0 && round < kmax, 9);
+  VG_CHECK_ARG(forced == nullptr || j >= 0, 11);
+  VG_CHECK_ARG(selected != nullptr, 12);
+  VG_CHECK_ARG(ws != nullptr, 14);
+  const CritXWS w = critx_layout(ws, n, P, kmax);
+  VG_CHECK_WS(ws_bytes, w.bytes);
+  const CritWS tv = critx_target_view(w);
+  hipStream_t s = as_stream(stream);
+  const unsigned nb = (unsigned)ceil_div(n, CR_B), nbp = (unsigned)ceil_div(P, CR_B);
+  {
+    ProfScope ps("criteria_select", s, 0.0, 8.0 * 3.0 * n);
+    hipLaunchKernelGGL(crit_score_kernel, dim3((unsigned)ceil_div(n, CR_CH)), dim3(CR_CH), 0, s, n,
+                       w.c);
+    hipLaunchKernelGGL(crit_select_kernel, dim3(1), dim3(CR_CH), 0, s, n, round, forced, j,
+                       selected, sel_delta, w.c);
+    VG_LAUNCH_CHECK();
+  }
+  {
+    ProfScope ps("criteria_row", s, 0.0,
+                 8.0 * ((double)n * (5 + round) + (double)P * (4 + round)));
+    hipLaunchKernelGGL(crit_row_kernel, dim3(nb), dim3(CR_B), 0, s, Sigma, n, lda, diag, selected,
+                       round, w.c);
+    hipLaunchKernelGGL(critx_urow_kernel, dim3(nbp), dim3(CR_B), 0, s, R, P, ldr, selected, round,
+                       w);
+    VG_LAUNCH_CHECK();
+  }
+  // dot[t] = U_t . (omega.u) for t <= round (t = round: sum_v omega_v u_v^2), over P
+  hipLaunchKernelGGL(crit_dots_kernel, dim3(nbp, (unsigned)round + 1), dim3(CR_B), 0, s, P,
+                     selected, round, tv);
+  hipLaunchKernelGGL(crit_fold_kernel, dim3((unsigned)round + 1), dim3(CR_B), 0, s, (int64_t)nbp,
+                     selected, round, tv);
+  VG_LAUNCH_CHECK();
+  gemv_t_launch<false>(R, P, n, ldr, w.wu, w.c.g, w.gemv, w.c.prm + 1, s);
+  VG_LAUNCH_CHECK();
+  {
+    ProfScope ps("criteria_update", s, 0.0, 8.0 * (double)n * (4 + round));
+    hipLaunchKernelGGL(crit_update_kernel, dim3(nb), dim3(CR_B), 0, s, n, selected, round, w.c);
+    VG_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+extern "C" int vgposp_critx_buffers(void* ws, int64_t n, int64_t P, int kmax, double** nom,
+                                    double** score, double** delta, double** W, double** U) {
+  clear_error();
+  VG_CHECK_ARG(ws != nullptr, 1);
+  VG_CHECK_ARG(n >= 1, 2);
+  VG_CHECK_ARG(P >= 1, 3);
+  VG_CHECK_ARG(kmax >= 1, 4);
+  const CritXWS w = critx_layout(ws, n, P, kmax);
+  if (nom) *nom = w.c.nom;
+  if (score) *score = w.c.s;
+  if (delta) *delta = w.c.delta;
+  if (W) *W = w.c.W;
+  if (U) *U = w.U;
   return 0;
 }

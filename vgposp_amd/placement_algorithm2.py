@@ -300,12 +300,30 @@ def dg_create_random_cov(n, rng=None):
 
 
 def placement_from_points(X, k, kind="eq", amp=1.0, ls=1.0, noise=1e-2, jitter=1e-6, lazy=True,
-                          candidates=None, placed=None, criterion="mi", targets=None):
+                          candidates=None, placed=None, criterion="mi", targets=None,
+                          target_points=None, target_weights=None):
     """Assemble Sigma = K(X, X) + (noise + jitter) I on device and place k sensors.
 
     ``criterion``: ``"mi"`` (mutual information, the default), or ``"variance"`` / ``"entropy"``
     (placement_criteria.CriterionPlacement on the same assembled matrix).  ``targets``, the
-    locations whose posterior variance counts, belongs to ``"variance"`` alone."""
+    locations whose posterior variance counts, belongs to ``"variance"`` alone.
+
+    ``target_points`` Xt [P, d] (``"variance"`` alone, instead of ``targets``): the posterior
+    variance of the latent field counts at these points, which need not be rows of X; the cross-
+    covariance K(Xt, X) is assembled without noise.  ``target_weights`` [P] >= 0 weigh them."""
+    if target_points is not None:
+        if criterion != "variance":
+            raise ValueError("target_points apply to criterion='variance' only")
+        if targets is not None:
+            raise ValueError("target_points and targets exclude each other")
+        Xt = np.asarray(target_points, dtype=np.float64) if not isinstance(
+            target_points, torch.Tensor) else target_points
+        Xt = Xt[:, None] if Xt.ndim == 1 else Xt
+        d = 1 if np.ndim(X) == 1 else np.shape(X)[1]
+        if Xt.ndim != 2 or Xt.shape[1] != d:
+            raise ValueError(f"target_points must be [P, {d}], got shape {tuple(Xt.shape)}")
+    elif target_weights is not None:
+        raise ValueError("target_weights need target_points")
     if criterion == "mi":
         if targets is not None:
             raise ValueError("targets apply to criterion='variance'; the mutual-information "
@@ -318,8 +336,12 @@ def placement_from_points(X, k, kind="eq", amp=1.0, ls=1.0, noise=1e-2, jitter=1
     K = linalg.kernel_matrix(kind, X, None, amp, ls, diag_shift=noise + jitter)[0]
     if criterion != "mi":
         from .placement_criteria import CriterionPlacement
+        R = None
+        if target_points is not None:
+            R = linalg.kernel_matrix(kind, Xt, X, amp, ls)[0]
         g = CriterionPlacement(K, k, criterion, candidates=candidates, placed=placed,
-                               targets=targets).run(k)
+                               targets=targets, cross_cov=R,
+                               target_weights=target_weights).run(k)
         return g.result()[0]
     g = GreedyPlacement(K, k, candidates=candidates, placed=placed).run(k, lazy=lazy)
     return g.result()[0]

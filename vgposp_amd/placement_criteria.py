@@ -17,6 +17,13 @@ location) are the locations whose uncertainty counts and need not intersect the 
 Nothing is factored (csrc/criteria.hip keeps nom = diag C, s_y = sum_T C_vy^2 and the pivoted
 Cholesky rows W; the variance rule passes once per round over the upper triangle of Sigma with
 ``vgposp_symv_upper``), so a singular PSD covariance needs no jitter, and Sigma is only read.
+
+Targets outside V: with ``cross_cov`` = R [P, N], the covariance between P targets that are no
+rows of ``cov_vv`` (a finer mesh, the latent field without sensor noise) and the N locations, and
+``target_weights`` = omega [P] >= 0 (default ones; cell volumes of an uneven mesh), the variance
+rule is delta_y = sum_v omega_v D_vy^2 / C_yy with D = R - R_{:,A} Sigma_AA^-1 Sigma_{A,:}: the drop
+of the weighted total posterior variance of the targets.  One pass per round over R
+(``vgposp_gemv_t``) replaces the pass over Sigma; the state gains the target-side rows U.
 """
 from __future__ import annotations
 
@@ -56,6 +63,42 @@ def _criterion_id(criterion):
         raise ValueError(f"unknown criterion {criterion!r}; expected one of {list(CRITERIA)}")
 
 
+def check_cross_arguments(criterion, targets, cross_cov, target_weights):
+    """The combinations ``cross_cov`` / ``target_weights`` do not allow (ValueError)."""
+    if target_weights is not None and cross_cov is None:
+        raise ValueError("target_weights need cross_cov: targets inside V are not weighted")
+    if cross_cov is None:
+        return
+    if criterion != "variance":
+        raise ValueError("cross_cov and target_weights apply to criterion='variance' only")
+    if targets is not None:
+        raise ValueError("cross_cov and targets exclude each other: the rows of cross_cov are "
+                         "the targets")
+
+
+def normalize_weights(P, target_weights):
+    """-> device float64 [P], or None (all ones).  Weights are finite and not negative."""
+    if target_weights is None:
+        return None
+    w = (target_weights.detach().cpu().numpy() if isinstance(target_weights, torch.Tensor)
+         else np.asarray(target_weights))
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    if w.shape != (P,):
+        raise ValueError(f"target_weights must have length {P}, got shape {w.shape}")
+    if not np.isfinite(w).all() or (w < 0.0).any():
+        raise ValueError("target_weights must be finite and not negative")
+    return linalg.as_device(w)
+
+
+def _device_matrix(M):
+    """A device float64 matrix with unit column stride (a view with a row pitch included) is used
+    where it lies; anything else is copied to the device."""
+    if (isinstance(M, torch.Tensor) and M.device.type == "cuda" and M.dim() == 2
+            and M.dtype == torch.float64 and M.stride(1) == 1 and M.stride(0) >= M.shape[1]):
+        return M
+    return linalg.as_device(M)
+
+
 class CriterionPlacement:
     """Device-resident greedy placement by ``criterion`` on an [N, N] covariance held in HBM.
 
@@ -63,18 +106,17 @@ class CriterionPlacement:
     its entries j >= i: a buffer that ``GreedyPlacement.init()`` factored in place serves as well
     when ``diag`` is the diagonal of Sigma saved before.  ``placed`` runs as forced rounds in
     ``init()``; ``kmax``, ``rounds`` and ``result()`` count the new picks only.
+
+    ``cross_cov`` [P, N] (variance rule only, instead of ``targets``) judges the placement at P
+    targets outside V, weighted by ``target_weights`` [P] >= 0; like ``Sigma`` it is used where it
+    lies when it is a device float64 tensor with unit column stride, and only read.
     """
 
     def __init__(self, Sigma, kmax, criterion="variance", candidates=None, placed=None,
-                 targets=None, threshold=1e-8, diag=None):
+                 targets=None, threshold=1e-8, diag=None, cross_cov=None, target_weights=None):
         self.criterion = criterion
         self.crit = _criterion_id(criterion)
-        if (isinstance(Sigma, torch.Tensor) and Sigma.device.type == "cuda" and Sigma.dim() == 2
-                and Sigma.dtype == torch.float64 and Sigma.stride(1) == 1
-                and Sigma.stride(0) >= Sigma.shape[1]):
-            S = Sigma                                # a view with a row pitch: used where it is
-        else:
-            S = linalg.as_device(Sigma)
+        S = _device_matrix(Sigma)
         if S.dim() != 2 or S.shape[0] != S.shape[1]:
             raise ValueError("cov_vv must be a square matrix")
         self.S = S
@@ -85,6 +127,16 @@ class CriterionPlacement:
         self.targets = normalize_targets(self.N, targets)
         if self.targets is not None and self.crit != CRITERIA["variance"]:
             raise ValueError("targets apply to criterion='variance' only")
+        check_cross_arguments(criterion, targets, cross_cov, target_weights)
+        self.R = self.omega = None
+        self.P = 0
+        if cross_cov is not None:
+            self.R = _device_matrix(cross_cov)
+            if self.R.dim() != 2 or self.R.shape[1] != self.N or self.R.shape[0] < 1:
+                raise ValueError(f"cross_cov must be [P, {self.N}] with P >= 1, got "
+                                 f"{tuple(self.R.shape)}")
+            self.P = int(self.R.shape[0])
+            self.omega = normalize_weights(self.P, target_weights)
         if not threshold >= 0.0:
             raise ValueError(f"threshold must not be negative, got {threshold}")
         self.threshold = float(threshold)
@@ -103,20 +155,38 @@ class CriterionPlacement:
         self._allowed_dev, self._targets_dev = mask(self.allowed), mask(self.targets)
         self._placed_dev = (torch.as_tensor(self.placed, dtype=torch.int64, device=dev)
                             if self.m else None)
-        self.ws = linalg.workspace(query("vgposp_crit_workspace_bytes", self.n, self.kmax))
+        if self.R is None:
+            nbytes = query("vgposp_crit_workspace_bytes", self.n, self.kmax)
+        else:
+            nbytes = query("vgposp_critx_workspace_bytes", self.n, self.P, self.kmax)
+        self.ws = linalg.workspace(nbytes)
         self.selected = torch.full((self.kmax,), -1, dtype=torch.int64, device=dev)
         self.sel_delta = torch.zeros(self.kmax, dtype=torch.float64, device=dev)
         self.rounds = 0
 
+    def _sigma_args(self):
+        return _p(self.S), self.n, self.S.stride(0), _p(self.diag)
+
+    def _cross_args(self):
+        return _p(self.R), self.P, self.R.stride(0)
+
     def _step(self, r, forced=None, j=0):
-        call("vgposp_crit_step", _p(self.S), self.n, self.S.stride(0), _p(self.diag), self.kmax,
-             r, _p(forced), j, _p(self.selected), _p(self.sel_delta), _p(self.ws),
-             self.ws.numel(), _stream())
+        tail = (r, _p(forced), j, _p(self.selected), _p(self.sel_delta), _p(self.ws),
+                self.ws.numel(), _stream())
+        if self.R is None:
+            call("vgposp_crit_step", *self._sigma_args(), self.kmax, *tail)
+        else:
+            call("vgposp_critx_step", *self._sigma_args(), *self._cross_args(), self.kmax, *tail)
 
     def init(self):
-        call("vgposp_crit_init", _p(self.S), self.n, self.S.stride(0), _p(self.diag), self.kmax,
-             self.crit, self.threshold, _p(self._targets_dev), _p(self._allowed_dev), _p(self.ws),
-             self.ws.numel(), _stream())
+        if self.R is None:
+            call("vgposp_crit_init", *self._sigma_args(), self.kmax, self.crit, self.threshold,
+                 _p(self._targets_dev), _p(self._allowed_dev), _p(self.ws), self.ws.numel(),
+                 _stream())
+        else:
+            call("vgposp_critx_init", *self._sigma_args(), *self._cross_args(), _p(self.omega),
+                 self.kmax, self.threshold, _p(self._allowed_dev), _p(self.ws), self.ws.numel(),
+                 _stream())
         for j in range(self.m):
             self._step(j, self._placed_dev, j)
         self.rounds = 0
@@ -136,17 +206,33 @@ class CriterionPlacement:
         return self
 
     def state(self):
-        """Device views into the workspace: ``nom`` [N] (C_yy), ``s`` [N] (sum_T C_vy^2), ``delta``
-        [N] (as scored by the last round, before its pick) and ``W`` [placed + rounds, N]."""
-        ptr = [ctypes.c_void_p() for _ in range(4)]
-        call("vgposp_crit_buffers", _p(self.ws), self.n, self.kmax, *map(ctypes.byref, ptr))
+        """Device views into the workspace: ``nom`` [N] (C_yy), ``s`` [N] (sum_T C_vy^2, or
+        sum_v omega_v D_vy^2), ``delta`` [N] (as scored by the last round, before its pick),
+        ``W`` [placed + rounds, N] and, with ``cross_cov``, ``U`` [placed + rounds, P]."""
+        ptr = [ctypes.c_void_p() for _ in range(4 if self.R is None else 5)]
+        if self.R is None:
+            call("vgposp_crit_buffers", _p(self.ws), self.n, self.kmax, *map(ctypes.byref, ptr))
+        else:
+            call("vgposp_critx_buffers", _p(self.ws), self.n, self.P, self.kmax,
+                 *map(ctypes.byref, ptr))
 
         def view(p, count):
             off = p.value - self.ws.data_ptr()
             return self.ws[off:off + 8 * count].view(torch.float64)
         rows = self.m + self.rounds
-        return {"nom": view(ptr[0], self.N), "s": view(ptr[1], self.N),
-                "delta": view(ptr[2], self.N), "W": view(ptr[3], rows * self.N).view(rows, self.N)}
+        st = {"nom": view(ptr[0], self.N), "s": view(ptr[1], self.N),
+              "delta": view(ptr[2], self.N), "W": view(ptr[3], rows * self.N).view(rows, self.N)}
+        if self.R is not None:
+            st["U"] = view(ptr[4], rows * self.P).view(rows, self.P)
+        return st
+
+    def variance_removed(self):
+        """[P] device tensor: sum_r U_r[v]^2, what the sensors so far (``placed`` included) took
+        off the prior variance of target v.  Needs ``cross_cov``."""
+        if self.R is None:
+            raise ValueError("variance_removed() needs cross_cov")
+        U = self.state()["U"]
+        return (U * U).sum(dim=0)
 
     def result(self):
         """``(picks, deltas)``: the new picks (host list of np.int64; ``placed`` is not part of
@@ -158,23 +244,29 @@ class CriterionPlacement:
         return [np.int64(s) for s in sel], self.sel_delta[new].cpu().numpy()
 
 
-def _place(cov_vv, k, criterion, candidates, placed, targets):
+def _place(cov_vv, k, criterion, candidates, placed, targets, cross_cov=None,
+           target_weights=None):
     if k < 1:
         N = int(np.shape(cov_vv)[0])
         normalize_constraints(N, max(int(k), 0), candidates, placed)
         normalize_targets(N, targets)
+        check_cross_arguments(criterion, targets, cross_cov, target_weights)
         return []
     g = CriterionPlacement(cov_vv, k, criterion, candidates=candidates, placed=placed,
-                           targets=targets)
+                           targets=targets, cross_cov=cross_cov, target_weights=target_weights)
     return g.run(k).result()[0]
 
 
-def placement_variance_reduction(cov_vv, k, candidates=None, placed=None, targets=None):
+def placement_variance_reduction(cov_vv, k, candidates=None, placed=None, targets=None,
+                                 cross_cov=None, target_weights=None):
     """k sensors by greedy variance reduction: each pick minimises the total posterior variance of
     ``targets`` (default: every location).  Returns a list of ``np.int64`` like
     ``placement_algorithm_2``; ``candidates`` / ``placed`` as there.  A singular PSD ``cov_vv``
-    needs no retry: nothing is factored."""
-    return _place(cov_vv, k, "variance", candidates, placed, targets)
+    needs no retry: nothing is factored.
+
+    ``cross_cov`` [P, N] instead of ``targets``: the posterior variance counts at P targets outside
+    V whose covariance with the N locations it holds, weighted by ``target_weights`` [P] >= 0."""
+    return _place(cov_vv, k, "variance", candidates, placed, targets, cross_cov, target_weights)
 
 
 def placement_entropy(cov_vv, k, candidates=None, placed=None):
