@@ -814,7 +814,8 @@ int vgposp_front_diag(const double* QPP, int64_t p, int nf, const int* piv, doub
  *     none), CG batch size, refined-not-picked count, refinement batches, candidates refined,
  *     refinement counter, tightening list size, candidates tightened.
  *   vgposp_exact_update:  after pick `round`: the factor rows and the window re-score (upper
- *     bounds where Q_yy is still only bounded); vgposp_exact_steps issues it per round.
+ *     bounds where Q_yy is still only bounded), for a caller that issues the rounds itself;
+ *     vgposp_exact_steps does not call it (it launches the same window kernel per round).
  *   The caller issues rounds, reads the control block, and on a stall refines the pending batch
  *   and re-issues the rounds from the stalled one: one host read per refinement batch (the B best
  *   entries are refined together, one batched CG, the launches of one column; the next rounds'
@@ -823,8 +824,8 @@ int vgposp_front_diag(const double* QPP, int64_t p, int nf, const int* piv, doub
  *   vgposp_exact_buffers: device addresses of the column slots [2 kmax][b0 b1 b2] (box-local, C
  *     order, box dims b_d = min(2 radius cg_iters + 1, I_d)), their box origins int64
  *     [2 kmax][3], the CG state (int [2]: converged flag, iterations of the last solve), the
- *     column slot of every pick (int [kmax]), the arg-max candidate (int64) and the Gershgorin
- *     bounds (double [2]). */
+ *     column slot of every pick (int [kmax]), two int64 of unused scratch (`cand`, kept so that
+ *     the signature and the workspace size stay) and the Gershgorin bounds (double [2]). */
 #define VGPOSP_EXACT_ARGS                                                                         \
   int kind, const double *X, int64_t I0, int64_t I1, int64_t I2, double amp, double ls,          \
       double diag_shift, double jitter, double threshold, const int *offsets, int m,             \

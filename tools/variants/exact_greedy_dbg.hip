@@ -1,7 +1,9 @@
 // PHASE-STAMPED BUILD of vgposp_amd/csrc/exact_greedy.hip (not built into the library): the
 // product file as of round 5/6 with its -DVGPOSP_EXACT_DBG=1|2|3 instrumentation (thread 0 of the
 // per-round kernels stamps phases with s_memrealtime; vgposp_exact_dbg copies the last 64 records
-// out).  With VGPOSP_EXACT_DBG=0 it compiles to the same device code as the product file.
+// out).  Forked from the product file as of commit f7b8bfc ("Hygiene: phase-stamp instrumentation
+// moved to tools/variants"); the product file has moved on since (its host side single-sourced,
+// round leftovers dropped), so with VGPOSP_EXACT_DBG=0 the device code is no longer the same.
 // Build: SRC=../../tools/variants/exact_greedy_dbg.hip tools/build_exact_variant.sh dbg -DVGPOSP_EXACT_DBG=1
 // Exact algorithm 3 on the sparse tapered covariance (config C4): the rounds.
 //

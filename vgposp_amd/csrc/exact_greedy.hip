@@ -21,20 +21,22 @@
 // Every launch only enqueues work: the pick lives in device memory (picks[round]) and every
 // later kernel reads it there, so the whole run is free of host synchronisation.
 //
-// Bounded-lazy form (vgposp_exact_bounds / _argmax / _refine / _pick / _update): diag(Q) is not
-// factored at all.  For every candidate y, K steps of CG on (S + eps I) x = e_y from x = 0 give
-// g_K = sum_i alpha_i |r_i|^2 = e_y^T x_K <= Q_yy, and Q_yy - g_K = |x* - x_K|_A^2
+// Bounded-lazy form (vgposp_exact_coef / _bounds, then _prepare / _steps_reset / _pretighten and
+// the rounds: _steps, with _tighten_pending / _refine_pending whenever a round stalls): diag(Q) is
+// not factored at all.  For every candidate y, K steps of CG on (S + eps I) x = e_y from x = 0
+// give g_K = sum_i alpha_i |r_i|^2 = e_y^T x_K <= Q_yy, and Q_yy - g_K = |x* - x_K|_A^2
 // <= 4 rho^(2K) Q_yy (rho from a Gershgorin bound on the spectrum), so
 // Q_yy <= g_K / (1 - 4 rho^(2K)).  The K-step Krylov vectors of e_y live on the nodes within K
 // stencil steps of y (a few hundred), so one wave runs one candidate's K steps in registers + LDS.
 // The cache then holds UPPER BOUNDS of the reference's cached deltas (delta is increasing in
-// P_yy); whenever the arg-max lands on a candidate whose Q_yy is only bounded, the host refines
-// it: its full CG column (the same Krylov-box solve a pick gets) gives Q_yy, and its cache entry
+// P_yy); whenever the arg-max lands on a candidate whose Q_yy is only bounded, it is refined
+// first: its full CG column (the same Krylov-box solve a pick gets) gives Q_yy, and its cache entry
 // becomes the reference's value (re-scored with the A of its last window re-score, lastA[y]).
 // The arg-max is only taken when it lands on a refined candidate, so the picks are the
 // reference's, and every pick's column is already there when it is picked.
 #include <cmath>
 #include <type_traits>
+#include <utility>
 
 #include "common.h"
 #include "psd.h"
@@ -90,7 +92,8 @@ struct ExactWS {
   unsigned char* qexact;  // [n]: 1 = qdiag[y] is Q_yy; 0 = an upper bound from the K_lo-step
                           // bounds, 2 = a tightened (K_hi-step) upper bound
   unsigned char* lastA;   // [n]: |A| when y's cache entry was last scored (0: round 0)
-  long long* cand;    // [2]: scratch (the arg-max candidate of the round-3 host loop)
+  long long* cand;    // [2]: unused scratch, kept so that the workspace size and the `cand`
+                      // out-parameter of vgposp_exact_buffers stay as they are
   double* gersh;      // [2 + 2 CG_BLOCKS]: lambda_min / lambda_max bounds, then partials
   // device-side rounds (vgposp_exact_steps): the refine-or-pick decision never leaves the GPU
   int* ctl;           // [CTL_N]: see CTL_* below
@@ -799,6 +802,10 @@ __device__ __forceinline__ unsigned fast_div(unsigned n, FastDiv f) {
 // (exact_bounds_reg_kernel<1, 6>), 8 spilled to AGPRs at one wave per SIMD (2.1 ms)
 // (profiles/r5_c4_bounds_grouped.jsonl)
 constexpr int BND_G = 2;  // candidates per wave (4: no faster, 8: spills)
+// vgposp_exact_bounds sends every 7-point table of T <= 64 nodes to the grouped kernel, so the
+// range form of the register kernel has no rung 1 (exact_bounds_reg_kernel<1, 6, false> is not
+// compiled); with one candidate per wave that rung would have to come back.
+static_assert(BND_G >= 2, "BND_G == 1 needs rung 1 of BoundRungsRange back");
 template <int G>
 __global__ __launch_bounds__(BND_T) void exact_bounds_grp_kernel(
     const double* __restrict__ coef, long long I0, long long I1, long long I2,
@@ -2104,8 +2111,7 @@ __global__ __launch_bounds__(SEL_THREADS) void exact_refine_end_kernel(EArgs a, 
                                                                        ExactWS w, long long nblk,
                                                                        int nb, const int* slots,
                                                                        const long long* cands,
-                                                                       const long long* picks,
-                                                                       int resume) {
+                                                                       const long long* picks) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   constexpr int NWAVE = SEL_THREADS / 64;
   for (int j = wave; j < nb; j += NWAVE) {
@@ -2125,7 +2131,7 @@ __global__ __launch_bounds__(SEL_THREADS) void exact_refine_end_kernel(EArgs a, 
   __syncthreads();
   for (int j = wave; j < nb; j += NWAVE)
     if (cands[j] >= 0) wave_super_key(w.bval, w.bidx, nblk, cands[j] / EB / ESB, w.sval, w.sidx);
-  if (resume && threadIdx.x == 0) {  // device-side rounds: the stalled round may go on
+  if (threadIdx.x == 0) {  // the stalled round may go on
     int done = 0;
     for (int j = 0; j < nb; ++j) done += cands[j] >= 0;
     w.ctl[CTL_UNPICKED] += done;
@@ -2634,6 +2640,11 @@ __device__ long long block_argmax_lds(const StepLds& L, long long nsb) {
   return r;
 }
 
+union StepSm {
+  StepLds k;
+  RowsLds r;
+};
+
 // One round of the bounded-lazy rounds, decided on the device (vgposp_exact_steps).  First the
 // keys of the blocks the previous round changed (its pick and its window's re-scored entries),
 // then the arg-max of the cache; if its Q_yy is exact (a refined candidate, its CG column in a
@@ -2648,18 +2659,15 @@ __device__ long long block_argmax_lds(const StepLds& L, long long nsb) {
 // the rounds from the stalled one.  One workgroup; a round is this kernel plus the window
 // re-score (exact_window_kernel).  A stalled round refreshed the keys of round - 1's pick first,
 // so the stall / refinement kernels that run next see current keys.
-union StepSm {
-  StepLds k;
-  RowsLds r;
-};
-
-// The step of `round` by one workgroup of SEL_THREADS threads (exact_step_kernel, or the last
-// workgroup of the previous round's window kernel).
 template <int KIND>
-__device__ __forceinline__ void step_body(const EArgs& ea, double* cache, unsigned char* sel,
-                                          const ExactWS& w, long long nblk, long long nsb,
-                                          int nslots, int round, int rows, long long* picks,
-                                          double* pick_delta, StepSm& sm, int& s_slot) {
+__global__ __launch_bounds__(SEL_THREADS) void exact_step_kernel(EArgs ea, double* cache,
+                                                                 unsigned char* sel, ExactWS w,
+                                                                 long long nblk, long long nsb,
+                                                                 int nslots, int round, int rows,
+                                                                 long long* picks,
+                                                                 double* pick_delta) {
+  __shared__ int s_slot;
+  __shared__ StepSm sm;
   if (w.ctl[CTL_STALL] >= 0) return;  // an earlier round is waiting for a refinement
   const long long n = ea.n;
   long long a;
@@ -2700,19 +2708,6 @@ __device__ __forceinline__ void step_body(const EArgs& ea, double* cache, unsign
   // stall: the batch is chosen by exact_stall_kernel, which the host launches first thing in
   // the refinement (vgposp_exact_refine_pending)
   if (threadIdx.x == 0) w.ctl[CTL_STALL] = round;
-}
-
-template <int KIND>
-__global__ __launch_bounds__(SEL_THREADS) void exact_step_kernel(EArgs ea, double* cache,
-                                                                 unsigned char* sel, ExactWS w,
-                                                                 long long nblk, long long nsb,
-                                                                 int nslots, int round, int B,
-                                                                 int rows, long long* picks,
-                                                                 double* pick_delta) {
-  __shared__ int s_slot;
-  __shared__ StepSm sm;
-  (void)B;
-  step_body<KIND>(ea, cache, sel, w, nblk, nsb, nslots, round, rows, picks, pick_delta, sm, s_slot);
 }
 
 template <int KIND>
@@ -2868,6 +2863,21 @@ namespace {
   VG_CHECK_ARG(selected != nullptr, 21);                                                  \
   VG_CHECK_ARG(ws != nullptr, 22)
 
+// The reach-table arguments (24 .. 30) of the three bounds entries and the entry's own last one
+// (31: LAST_OK), after the prologue.  REG_ONLY: the entry has the register kernel only (m == 7,
+// all three tables, reported as one argument); otherwise m == 1 needs no neighbour table.
+#define VGPOSP_EXACT_CHECK_TABLES(REG_ONLY, LAST_OK)                                         \
+  VG_CHECK_ARG(tab_off != nullptr, 24);                                                    \
+  VG_CHECK_ARG(tab_nb != nullptr || (!(REG_ONLY) && m == 1), (REG_ONLY) ? 24 : 25);        \
+  VG_CHECK_ARG(tab_cnt != nullptr, (REG_ONLY) ? 24 : 26);                                  \
+  VG_CHECK_ARG(T >= 1 && T <= BND_TMAX && (int64_t)T * (m - 1) <= BND_NBMAX, 27);          \
+  VG_CHECK_ARG(K >= 1 && K <= 4 * BND_SMAX, 28);                                           \
+  VG_CHECK_ARG(hi_scale >= 1.0, 29);                                                       \
+  VG_CHECK_ARG(mu >= 0.0, 30);                                                             \
+  VG_CHECK_ARG(LAST_OK, 31);                                                               \
+  VG_CHECK_ARG(!(REG_ONLY) || a.m1 == 6, 12);                                              \
+  VG_CHECK_ARG(a.n < (1LL << 31), 3)
+
 EArgs make_eargs(const double* X, int64_t I0, int64_t I1, int64_t I2, double amp, double ls,
                  double shift, double jitter, double thr, const int* offs, int m, const double* tau,
                  int ntau, int kmax, int cutoff) {
@@ -2902,11 +2912,23 @@ int dispatch_kind(int kind, F&& f) {
   }
 }
 
+// The block keys of the whole cache, then the superblock keys.
+int launch_keys(const double* cache, const unsigned char* sel, long long n, const ExactWS& w,
+                hipStream_t s) {
+  const long long nblk = ceil_div(n, EB), nsb = ceil_div(nblk, ESB);
+  hipLaunchKernelGGL(exact_block_keys_kernel, dim3((unsigned)ceil_div(nblk, 4)), dim3(256), 0, s,
+                     cache, sel, n, w.bval, w.bidx, nblk);
+  VG_LAUNCH_CHECK();
+  hipLaunchKernelGGL(exact_super_keys_kernel, dim3((unsigned)ceil_div(nsb, 4)), dim3(256), 0, s,
+                     w.bval, w.bidx, nblk, w.sval, w.sidx, nsb);
+  VG_LAUNCH_CHECK();
+  return 0;
+}
+
 template <int KIND>
 int exact_prepare_t(const EArgs& a, const double* qdiag, double* cache, unsigned char* sel,
                     const ExactWS& w, int flags, hipStream_t s) {
   const long long n = a.n;
-  const long long nblk = ceil_div(n, EB), nsb = ceil_div(nblk, ESB);
   const bool bounded = (flags & 1) != 0;
   VG_CHECK_ARG(n < (1LL << 31), 3);  // (coef_row's 32-bit grid coordinates)
   VG_HIP(vg_memset(sel, 0, n, s));
@@ -2924,13 +2946,7 @@ int exact_prepare_t(const EArgs& a, const double* qdiag, double* cache, unsigned
                        a, qdiag, w.qexact, cache);
     VG_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(exact_block_keys_kernel, dim3((unsigned)ceil_div(nblk, 4)), dim3(256), 0, s,
-                     cache, sel, n, w.bval, w.bidx, nblk);
-  VG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(exact_super_keys_kernel, dim3((unsigned)ceil_div(nsb, 4)), dim3(256), 0, s,
-                     w.bval, w.bidx, nblk, w.sval, w.sidx, nsb);
-  VG_LAUNCH_CHECK();
-  return 0;
+  return launch_keys(cache, sel, n, w, s);
 }
 
 // cg_iters CG iterations for the nb columns centers[j] -> slots[j] (device arrays), from a
@@ -2942,43 +2958,48 @@ int exact_cg_run(const EArgs& a, const ExactWS& w, int nb, const int* slots,
   const int m = a.m1 + 1;
   ProfScope ps("exact_cg", s, 0.0, (double)nb * cg_iters * 8.0 * bv * (m + 9));
   const double tol2 = cg_tol * cg_tol;
-  // the 7-point stencil (face neighbours only): walk the Manhattan ball, not its bounding cube
-  const bool oct = a.m1 == 6 && radius == 1;  // (the 6 offsets of squared distance 1)
   // ~8 elements per thread (one per thread had 800 short workgroups per column, 42 us a batch)
   const dim3 sg((unsigned)std::min<long long>(ceil_div(bv, 256 * 8), 1024), (unsigned)nb);
-  if (oct)
-    hipLaunchKernelGGL(exact_cg_start_kernel<true>, sg, dim3(256), 0, s, w, a.I0, a.I1, a.I2, slots,
+  // the 7-point stencil (face neighbours only: the 6 offsets of squared distance 1): walk the
+  // Manhattan ball, not its bounding cube
+  const auto run = [&](auto O) {
+    constexpr bool OCT = decltype(O)::value;
+    hipLaunchKernelGGL(exact_cg_start_kernel<OCT>, sg, dim3(256), 0, s, w, a.I0, a.I1, a.I2, slots,
                        centers);
-  else
-    hipLaunchKernelGGL(exact_cg_start_kernel<false>, sg, dim3(256), 0, s, w, a.I0, a.I1, a.I2, slots,
-                       centers);
-  VG_LAUNCH_CHECK();
-  unsigned prev = 1;
-  for (int it = 0; it < cg_iters; ++it) {
-    // the unclipped active region bounds the launch: a grid that grows with the iterate's support
-    const long long side = std::min<long long>(2LL * (it + 1) * radius + 1, 2 * w.H + 1);
-    const long long R = std::min<long long>(it + 1, w.H);
-    const unsigned blocks = (unsigned)std::min<long long>(
-        CG_BLOCKS, oct ? ceil_div(2 * R * R + 2 * R + 1, (long long)(CG_T / 64 * CG_RPW))
-                       : ceil_div(side * side * side, (long long)CG_T));
-    if (oct) {
-      hipLaunchKernelGGL(exact_cg_a_kernel<true>, dim3(blocks * (unsigned)nb), dim3(CG_T), 0, s, w,
-                         a.I0, a.I1, a.I2, a.offs, a.m1, radius, slots, centers, it, (int)prev,
-                         tol2, nb);
-      VG_LAUNCH_CHECK();
-      hipLaunchKernelGGL(exact_cg_b_kernel<true>, dim3(blocks * (unsigned)nb), dim3(CG_T), 0, s, w,
-                         a.I0, a.I1, a.I2, radius, slots, centers, it, nb);
-    } else {
-      hipLaunchKernelGGL(exact_cg_a_kernel<false>, dim3(blocks * (unsigned)nb), dim3(CG_T), 0, s, w,
-                         a.I0, a.I1, a.I2, a.offs, a.m1, radius, slots, centers, it, (int)prev,
-                         tol2, nb);
-      VG_LAUNCH_CHECK();
-      hipLaunchKernelGGL(exact_cg_b_kernel<false>, dim3(blocks * (unsigned)nb), dim3(CG_T), 0, s, w,
-                         a.I0, a.I1, a.I2, radius, slots, centers, it, nb);
-    }
     VG_LAUNCH_CHECK();
-    prev = blocks;
-  }
+    unsigned prev = 1;
+    for (int it = 0; it < cg_iters; ++it) {
+      // the unclipped active region bounds the launch: a grid that grows with the iterate's support
+      const long long side = std::min<long long>(2LL * (it + 1) * radius + 1, 2 * w.H + 1);
+      const long long R = std::min<long long>(it + 1, w.H);
+      const unsigned blocks = (unsigned)std::min<long long>(
+          CG_BLOCKS, OCT ? ceil_div(2 * R * R + 2 * R + 1, (long long)(CG_T / 64 * CG_RPW))
+                         : ceil_div(side * side * side, (long long)CG_T));
+      hipLaunchKernelGGL(exact_cg_a_kernel<OCT>, dim3(blocks * (unsigned)nb), dim3(CG_T), 0, s, w,
+                         a.I0, a.I1, a.I2, a.offs, a.m1, radius, slots, centers, it, (int)prev,
+                         tol2, nb);
+      VG_LAUNCH_CHECK();
+      hipLaunchKernelGGL(exact_cg_b_kernel<OCT>, dim3(blocks * (unsigned)nb), dim3(CG_T), 0, s, w,
+                         a.I0, a.I1, a.I2, radius, slots, centers, it, nb);
+      VG_LAUNCH_CHECK();
+      prev = blocks;
+    }
+    return 0;
+  };
+  return a.m1 == 6 && radius == 1 ? run(std::true_type{}) : run(std::false_type{});
+}
+
+// candidates of a pick's re-score window: [i_d - cutoff, i_d + cutoff) in each dimension
+long long window_cands(const EArgs& a) { return 8LL * a.cutoff * a.cutoff * a.cutoff; }
+
+// The window re-score of pick `round` (which also computes the pick's factor rows).
+template <int KIND>
+int launch_window(const EArgs& a, const double* qdiag, double* cache, const unsigned char* sel,
+                  const ExactWS& w, int round, const long long* picks, hipStream_t s) {
+  hipLaunchKernelGGL(exact_window_kernel<KIND>,
+                     dim3((unsigned)ceil_div(window_cands(a), WIN_CAND)), dim3(WIN_T), 0, s, a,
+                     qdiag, cache, sel, w, round, picks);
+  VG_LAUNCH_CHECK();
   return 0;
 }
 
@@ -2987,16 +3008,11 @@ int exact_update_t(const EArgs& a, const double* qdiag, double* cache, unsigned 
                    const ExactWS& w, int round, const long long* picks, hipStream_t s) {
   const long long nblk = ceil_div(a.n, EB);
   ProfScope ps("exact_update", s, 0.0, 0.0);
-  const long long side = 2LL * a.cutoff;
-  const long long nw = side * side * side;
-  if (nw <= 0) {  // (otherwise the window kernel computes the pick's factor rows)
+  if (window_cands(a) <= 0) {  // (otherwise the window kernel computes the pick's factor rows)
     hipLaunchKernelGGL(exact_rows_kernel<KIND>, dim3(1), dim3(128), 0, s, a, w, round, picks);
     VG_LAUNCH_CHECK();
-  }
-  if (nw > 0) {
-    hipLaunchKernelGGL(exact_window_kernel<KIND>, dim3((unsigned)ceil_div(nw, WIN_CAND)), dim3(WIN_T), 0, s,
-                       a, qdiag, cache, sel, w, round, picks);
-    VG_LAUNCH_CHECK();
+  } else if (int rc = launch_window<KIND>(a, qdiag, cache, sel, w, round, picks, s)) {
+    return rc;
   }
   hipLaunchKernelGGL(exact_window_keys_kernel, dim3(1), dim3(SEL_THREADS), 0, s, a, cache, sel, w,
                      nblk, round, picks);
@@ -3027,19 +3043,46 @@ int exact_round_t(const EArgs& a, const double* qdiag, double* cache, unsigned c
 template <int KIND>
 int exact_refine_t(const EArgs& a, double* qdiag, double* cache, unsigned char* sel,
                    const ExactWS& w, int nb, const long long* cands, const int* slots,
-                   const long long* picks, int radius, int cg_iters, double cg_tol, hipStream_t s,
-                   int resume = 0) {
+                   const long long* picks, int radius, int cg_iters, double cg_tol,
+                   hipStream_t s) {
   const long long nblk = ceil_div(a.n, EB);
   if (int rc = exact_cg_run(a, w, nb, slots, cands, radius, cg_iters, cg_tol, s)) return rc;
-  hipLaunchKernelGGL(exact_refine_end_kernel<KIND>, dim3(1), dim3(SEL_THREADS), 0, s, a, qdiag, cache, sel, w,
-                     nblk, nb, slots, cands, picks, resume);
+  hipLaunchKernelGGL(exact_refine_end_kernel<KIND>, dim3(1), dim3(SEL_THREADS), 0, s, a, qdiag,
+                     cache, sel, w, nblk, nb, slots, cands, picks);
   VG_LAUNCH_CHECK();
   return 0;
 }
 
+struct BoundTabs {  // the reach table of a bounds launch (the entries' arguments 24 .. 30)
+  const int *off, *nb, *cnt;
+  int T, K;
+  double hi_scale, mu;
+};
+
+// The rungs of exact_bounds_reg_kernel<SMV, 6, LIST> (tables of up to 64 SMV nodes) that are
+// compiled: these and no others.  Range launches: T <= 64 goes to the grouped kernel and
+// T > 576 (K = 8) to the generic one; list launches: the K_hi tables, up to BND_TMAX nodes.
+using BoundRungsRange = std::integer_sequence<int, 2, 3, 4, 6, 9>;
+using BoundRungsList = std::integer_sequence<int, 4, 6, 9, 14>;
+
+// Launches the first rung that holds the table (T <= 64 SMV), on the candidates [c0, c1)
+// (LIST = false) or list[0 .. *count) (LIST = true).  False: no rung fits, nothing was launched.
+template <bool LIST, int... SMV>
+bool launch_bounds_reg(std::integer_sequence<int, SMV...>, unsigned blocks, hipStream_t s,
+                       const EArgs& a, const ExactWS& w, const BoundTabs& t, long long c0,
+                       long long c1, double* out, const long long* list, const int* count) {
+  return ((t.T <= 64 * SMV && [&] {
+            hipLaunchKernelGGL((exact_bounds_reg_kernel<SMV, 6, LIST>), dim3(blocks), dim3(BND_T),
+                               0, s, w.coef, a.I0, a.I1, a.I2, t.off, t.nb, t.cnt, t.T, t.K,
+                               t.hi_scale, t.mu, c0, c1, out, list, count);
+            return true;
+          }()) ||
+          ...);
+}
+
 }  // namespace
 
-#define VGPOSP_EXACT_PARAMS                                                                      \
+#define VGPOSP_EXACT_PARAMS                                                                     \
   int kind, const double *X, int64_t I0, int64_t I1, int64_t I2, double amp, double ls,          \
       double diag_shift, double jitter, double threshold, const int *offsets, int m,             \
       const double *tau, int ntau, int kmax, int cutoff, int radius, int cg_iters,               \
@@ -3112,16 +3155,9 @@ extern "C" int vgposp_exact_bounds(VGPOSP_EXACT_PARAMS, const int* tab_off, cons
                                    const int* tab_cnt, int T, int K, double hi_scale, double mu,
                                    int64_t c0, int64_t c1, void* stream) {
   VGPOSP_EXACT_PROLOGUE("vgposp_exact_bounds");
-  VG_CHECK_ARG(tab_off != nullptr, 24);
-  VG_CHECK_ARG(m == 1 || tab_nb != nullptr, 25);
-  VG_CHECK_ARG(tab_cnt != nullptr, 26);
-  VG_CHECK_ARG(T >= 1 && T <= BND_TMAX && (int64_t)T * (m - 1) <= BND_NBMAX, 27);
-  VG_CHECK_ARG(K >= 1 && K <= 4 * BND_SMAX, 28);
-  VG_CHECK_ARG(hi_scale >= 1.0, 29);
-  VG_CHECK_ARG(mu >= 0.0, 30);
-  VG_CHECK_ARG(c0 >= 0 && c0 <= c1 && c1 <= a.n, 31);
-  VG_CHECK_ARG(a.n < (1LL << 31), 3);
+  VGPOSP_EXACT_CHECK_TABLES(false, c0 >= 0 && c0 <= c1 && c1 <= a.n);
   if (c1 == c0) return 0;
+  const BoundTabs tabs{tab_off, tab_nb, tab_cnt, T, K, hi_scale, mu};
   ProfScope ps("exact_bounds", s, 0.0, 0.0);
   const long long waves = c1 - c0;
   const unsigned blocks =
@@ -3129,15 +3165,7 @@ extern "C" int vgposp_exact_bounds(VGPOSP_EXACT_PARAMS, const int* tab_off, cons
                                          BND_GRID / 8));
   double* out = const_cast<double*>(qdiag);
   const long long lc0 = c0, lc1 = c1;
-#define VG_BOUNDS_REG(SMV)                                                                     \
-  if (T <= 64 * SMV) {                                                                           \
-    hipLaunchKernelGGL((exact_bounds_reg_kernel<SMV, 6>), dim3(blocks), dim3(BND_T), 0, s, w.coef, \
-                       a.I0, a.I1, a.I2, tab_off, tab_nb, tab_cnt, T, K, hi_scale, mu, lc0, lc1,   \
-                       out);                                                                      \
-    VG_LAUNCH_CHECK();                                                                           \
-    return 0;                                                                                    \
-  }
-  if (a.m1 == 6 && T <= 64 && BND_G > 1) {  // K <= 3: G candidates per wave
+  if (a.m1 == 6 && T <= 64) {  // K <= 3: G candidates per wave
     constexpr int G = BND_G;
     // at most 16,384 workgroups: each wave then walks ~16 candidate pairs and the per-workgroup
     // table staging and per-wave address setup are amortised (65,536: 0.84 ms per 128^3 pass,
@@ -3151,17 +3179,11 @@ extern "C" int vgposp_exact_bounds(VGPOSP_EXACT_PARAMS, const int* tab_off, cons
     VG_LAUNCH_CHECK();
     return 0;
   }
-  if (a.m1 == 6) {  // the 7-point taper support of the reference's beta = 4
-    VG_BOUNDS_REG(1)
-    VG_BOUNDS_REG(2)
-    VG_BOUNDS_REG(3)
-    VG_BOUNDS_REG(4)
-    VG_BOUNDS_REG(6)
-    VG_BOUNDS_REG(9)
-  }
-#undef VG_BOUNDS_REG
-  hipLaunchKernelGGL(exact_bounds_kernel, dim3(blocks), dim3(BND_T), 0, s, w.coef, a.I0, a.I1, a.I2,
-                     a.m1, tab_off, tab_nb, tab_cnt, T, K, hi_scale, mu, lc0, lc1, out);
+  // the 7-point taper support of the reference's beta = 4: the register kernel where a rung fits
+  if (a.m1 != 6 || !launch_bounds_reg<false>(BoundRungsRange{}, blocks, s, a, w, tabs, lc0, lc1,
+                                             out, nullptr, nullptr))
+    hipLaunchKernelGGL(exact_bounds_kernel, dim3(blocks), dim3(BND_T), 0, s, w.coef, a.I0, a.I1,
+                       a.I2, a.m1, tab_off, tab_nb, tab_cnt, T, K, hi_scale, mu, lc0, lc1, out);
   VG_LAUNCH_CHECK();
   return 0;
 }
@@ -3184,8 +3206,7 @@ extern "C" int vgposp_exact_steps(VGPOSP_EXACT_PARAMS, int round0, int round1, i
   VG_CHECK_ARG(picks != nullptr, 28);
   const long long nblk = ceil_div(a.n, EB), nsb = ceil_div(nblk, ESB);
   long long* pk = reinterpret_cast<long long*>(picks);
-  const long long side = 2LL * a.cutoff;
-  const long long nw = side * side * side;
+  const long long nw = window_cands(a);
   return dispatch_kind(kind, [&](auto K) {
     constexpr int KD = decltype(K)::value;
     for (int r = round0; r < round1; ++r) {
@@ -3194,15 +3215,13 @@ extern "C" int vgposp_exact_steps(VGPOSP_EXACT_PARAMS, int round0, int round1, i
         ProfScope ps("exact_select", s, 0.0, 16.0 * nsb);
         // (the factor rows of pick r: in the window kernel, here only when there is no window)
         hipLaunchKernelGGL(exact_step_kernel<KD>, dim3(1), dim3(SEL_THREADS), 0, s, a, cache,
-                           selected, w, nblk, nsb, exact_slots(kmax), r, batch,
+                           selected, w, nblk, nsb, exact_slots(kmax), r,
                            (int)(more && nw <= 0), pk, pick_delta);
         VG_LAUNCH_CHECK();
       }
       if (more && nw > 0) {  // the window of pick r (no-op when the round stalled: picks[r] = -1)
         ProfScope ps("exact_update", s, 0.0, 0.0);
-        hipLaunchKernelGGL(exact_window_kernel<KD>, dim3((unsigned)ceil_div(nw, WIN_CAND)), dim3(WIN_T), 0, s,
-                           a, qdiag, cache, selected, w, r, pk);
-        VG_LAUNCH_CHECK();
+        if (int rc = launch_window<KD>(a, qdiag, cache, selected, w, r, pk, s)) return rc;
       }
     }
     // if a round stalled: choose its batch now, so ONE read of the control block tells the host
@@ -3225,7 +3244,7 @@ extern "C" int vgposp_exact_refine_pending(VGPOSP_EXACT_PARAMS, int batch, const
   return dispatch_kind(kind, [&](auto K) {
     return exact_refine_t<decltype(K)::value>(a, const_cast<double*>(qdiag), cache, selected, w,
                                               batch, w.rf_cand, w.rf_slot, pk, radius, cg_iters,
-                                              cg_tol, s, 1);
+                                              cg_tol, s);
   });
 }
 
@@ -3261,30 +3280,18 @@ extern "C" int vgposp_exact_tighten_pending(VGPOSP_EXACT_PARAMS, const int* tab_
                                             double hi_scale, double mu, const int64_t* picks,
                                             void* stream) {
   VGPOSP_EXACT_PROLOGUE("vgposp_exact_tighten_pending");
-  VG_CHECK_ARG(tab_off != nullptr && tab_nb != nullptr && tab_cnt != nullptr, 24);
-  VG_CHECK_ARG(T >= 1 && T <= BND_TMAX && (int64_t)T * (m - 1) <= BND_NBMAX, 27);
-  VG_CHECK_ARG(K >= 1 && K <= 4 * BND_SMAX, 28);
-  VG_CHECK_ARG(hi_scale >= 1.0, 29);
-  VG_CHECK_ARG(mu >= 0.0, 30);
-  VG_CHECK_ARG(picks != nullptr, 31);
-  VG_CHECK_ARG(a.m1 == 6, 12);  // the register bounds kernel (the 7-point taper)
-  VG_CHECK_ARG(a.n < (1LL << 31), 3);
+  VGPOSP_EXACT_CHECK_TABLES(true, picks != nullptr);
+  const BoundTabs tabs{tab_off, tab_nb, tab_cnt, T, K, hi_scale, mu};
   const long long nblk = ceil_div(a.n, EB);
   double* out = const_cast<double*>(qdiag);
   const unsigned blocks = (unsigned)ceil_div(CG_B, BND_WAVES);
   {
     ProfScope ps("exact_tighten", s, 0.0, 0.0);
-#define VG_TIGHT_REG(SMV)                                                                        \
-  if (T <= 64 * SMV) {                                                                           \
-    hipLaunchKernelGGL((exact_bounds_reg_kernel<SMV, 6, true>), dim3(blocks), dim3(BND_T), 0, s,   \
-                       w.coef, a.I0, a.I1, a.I2, tab_off, tab_nb, tab_cnt, T, K, hi_scale, mu,    \
-                       0LL, 0LL, out, w.rt_cand, w.ctl + CTL_NT);                                 \
-  } else
-    VG_TIGHT_REG(4) VG_TIGHT_REG(6) VG_TIGHT_REG(9) VG_TIGHT_REG(14) {
+    if (!launch_bounds_reg<true>(BoundRungsList{}, blocks, s, a, w, tabs, 0, 0, out, w.rt_cand,
+                                 w.ctl + CTL_NT)) {
       set_error("vgposp_exact_tighten_pending: reach table of %d nodes", T);
       return 27;
     }
-#undef VG_TIGHT_REG
     VG_LAUNCH_CHECK();
   }
   return dispatch_kind(kind, [&](auto KK) {
@@ -3300,15 +3307,9 @@ extern "C" int vgposp_exact_pretighten(VGPOSP_EXACT_PARAMS, const int* tab_off,
                                        const int* tab_nb, const int* tab_cnt, int T, int K,
                                        double hi_scale, double mu, int64_t M, void* stream) {
   VGPOSP_EXACT_PROLOGUE("vgposp_exact_pretighten");
-  VG_CHECK_ARG(tab_off != nullptr && tab_nb != nullptr && tab_cnt != nullptr, 24);
-  VG_CHECK_ARG(T >= 1 && T <= BND_TMAX && (int64_t)T * (m - 1) <= BND_NBMAX, 27);
-  VG_CHECK_ARG(K >= 1 && K <= 4 * BND_SMAX, 28);
-  VG_CHECK_ARG(hi_scale >= 1.0, 29);
-  VG_CHECK_ARG(mu >= 0.0, 30);
-  VG_CHECK_ARG(M >= 1 && M <= PT_MAX / 2, 31);
-  VG_CHECK_ARG(a.m1 == 6, 12);  // the register bounds kernel (the 7-point taper)
-  VG_CHECK_ARG(a.n < (1LL << 31), 3);
-  const long long n = a.n, nblk = ceil_div(n, EB), nsb = ceil_div(nblk, ESB);
+  VGPOSP_EXACT_CHECK_TABLES(true, M >= 1 && M <= PT_MAX / 2);
+  const BoundTabs tabs{tab_off, tab_nb, tab_cnt, T, K, hi_scale, mu};
+  const long long n = a.n;
   // (512 workgroups: each merges its 4,096-bin histogram into the global one with atomics)
   const unsigned sweep = (unsigned)std::min<long long>(ceil_div(n, 256), 512);
   double* out = const_cast<double*>(qdiag);
@@ -3330,30 +3331,18 @@ extern "C" int vgposp_exact_pretighten(VGPOSP_EXACT_PARAMS, const int* tab_off,
                      w.ctl);
   VG_LAUNCH_CHECK();
   const unsigned blocks = (unsigned)std::min<long long>(ceil_div(M + 4096, BND_WAVES), 2048);
-#define VG_PT_REG(SMV)                                                                           \
-  if (T <= 64 * SMV) {                                                                           \
-    hipLaunchKernelGGL((exact_bounds_reg_kernel<SMV, 6, true>), dim3(blocks), dim3(BND_T), 0, s,   \
-                       w.coef, a.I0, a.I1, a.I2, tab_off, tab_nb, tab_cnt, T, K, hi_scale, mu,    \
-                       0LL, 0LL, out, w.pt_list, w.pt_count);                                     \
-  } else
-  VG_PT_REG(4) VG_PT_REG(6) VG_PT_REG(9) VG_PT_REG(14) {
+  if (!launch_bounds_reg<true>(BoundRungsList{}, blocks, s, a, w, tabs, 0, 0, out, w.pt_list,
+                               w.pt_count)) {
     set_error("vgposp_exact_pretighten: reach table of %d nodes", T);
     return 27;
   }
-#undef VG_PT_REG
   VG_LAUNCH_CHECK();
   return dispatch_kind(kind, [&](auto KK) {
     hipLaunchKernelGGL(exact_pt_score_kernel<decltype(KK)::value>,
                        dim3((unsigned)ceil_div(PT_MAX, 256)), dim3(256), 0, s, a, qdiag, w.qexact,
                        cache, w.pt_list, w.pt_count);
     VG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(exact_block_keys_kernel, dim3((unsigned)ceil_div(nblk, 4)), dim3(256), 0, s,
-                       cache, selected, n, w.bval, w.bidx, nblk);
-    VG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(exact_super_keys_kernel, dim3((unsigned)ceil_div(nsb, 4)), dim3(256), 0, s,
-                       w.bval, w.bidx, nblk, w.sval, w.sidx, nsb);
-    VG_LAUNCH_CHECK();
-    return 0;
+    return launch_keys(cache, selected, n, w, s);
   });
 }
 

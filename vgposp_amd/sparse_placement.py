@@ -24,6 +24,7 @@ So the selections are the reference's dense algorithm 3 on the tapered covarianc
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import math
 import time
@@ -419,6 +420,12 @@ BOUND_MARGIN = 1e-12                       # relative rounding margin on the upp
 BOUND_LO_TARGET = 3e-5
 PRETIGHTEN = 2048      # two levels: candidates tightened before the rounds (at most 32,768)
 BOUND_HI_TARGET = 1e-7
+# the rounds' control block (int32 [8]): the CTL_* of csrc/exact_greedy.hip, where each is described
+(CTL_STALL, CTL_NB, CTL_UNPICKED, CTL_EVENTS, CTL_REFINED, CTL_AGE, CTL_NT,
+ CTL_TIGHT) = range(8)
+# byte offsets into the workspace, as vgposp_exact_buffers returns them
+ExactBuffers = collections.namedtuple(
+    "ExactBuffers", "qcols boxlo cgstate slot_of_round cand gersh")
 
 
 def bound_steps(offsets, lam_min, lam_max, target=1e-6, kmax=12):
@@ -525,7 +532,7 @@ class ExactWindowGreedy:
         """Stencil coefficients + Gershgorin [lambda_min, lambda_max] of Sigma + eps I (one host
         read)."""
         call("vgposp_exact_coef", *self._args(qdiag), _stream())
-        off = self._buffers()[5]
+        off = self._buffers().gersh
         g = self.ws[off: off + 16].view(torch.float64).cpu()
         return float(g[0]), float(g[1])
 
@@ -625,41 +632,40 @@ class ExactWindowGreedy:
         call("vgposp_exact_steps", *args, 0, 1, k, B, pk, pd, st)  # round 0 stalls: nothing refined
         issued, reads = 1, 0
         # every host read must show progress since the previous one: the stall moved to another
-        # round, or candidates were refined (c[4]) or tightened (c[7]), or (no stall) more rounds
-        # were issued.  A read that shows none of these would repeat forever.  (Counting reads
-        # instead is wrong: recycled slots let a candidate be refined again, and stall events per
-        # round are not bounded by the batch size.)
+        # round, or candidates were refined (CTL_REFINED) or tightened (CTL_TIGHT), or more rounds
+        # were issued (no stall).  A read that shows none of these would repeat forever.  (Counting
+        # reads instead is wrong: recycled slots let a candidate be refined again, and stall events
+        # per round are not bounded by the batch size.)
         prev = None
         while True:
-            # stall round, CG batch, refined-unpicked, events, refined, age, tightening list, tightened
             c = ctl.cpu().tolist()
             reads += 1
-            state = (c[0], c[4], c[7], issued)
+            state = (c[CTL_STALL], c[CTL_REFINED], c[CTL_TIGHT], issued)
             if state == prev:
                 raise RuntimeError(f"run_bounded: control block {c} unchanged after the previous "
                                    f"read ({reads} reads, k = {k}): the device rounds are not "
                                    "progressing")
             prev = state
-            stall = c[0]
+            stall = c[CTL_STALL]
             if stall >= 0:
-                if c[1] == 0 and c[6] == 0:
+                if c[CTL_NB] == 0 and c[CTL_NT] == 0:
                     raise RuntimeError(f"run_bounded: round {stall} stalled with neither a CG "
                                        f"batch nor a tightening list (control block {c})")
-                if c[6] > 0:
+                if c[CTL_NT] > 0:
                     if tight is None:
                         raise RuntimeError("tightening list without a K_hi table")
                     call("vgposp_exact_tighten_pending", *args, *targs, st)
-                if c[1] > 0:
+                if c[CTL_NB] > 0:
                     call("vgposp_exact_refine_pending", *args, B, pk, self.cg_tol, st)
-                r0, r1 = stall, min(k, stall + c[2] + c[1] + 1)
+                r0, r1 = stall, min(k, stall + c[CTL_UNPICKED] + c[CTL_NB] + 1)
             elif issued < k:
-                r0, r1 = issued, min(k, issued + max(c[2], 0) + 1)
+                r0, r1 = issued, min(k, issued + max(c[CTL_UNPICKED], 0) + 1)
             else:
                 break
             call("vgposp_exact_steps", *args, r0, r1, k, B, pk, pd, st)
             issued = r1
-        self.refinements, self.refine_batches, self.host_reads = c[4], c[3], reads
-        self.tightened = c[7]
+        self.refinements, self.refine_batches = c[CTL_REFINED], c[CTL_EVENTS]
+        self.host_reads, self.tightened = reads, c[CTL_TIGHT]
         return self.picks[:k]
 
     def _ctl(self):
@@ -675,12 +681,13 @@ class ExactWindowGreedy:
         call("vgposp_exact_buffers", _p(self.ws), *self.p.shape, self.p.m, self.kmax, self.radius,
              self.cg_iters, *[ctypes.byref(q) for q in ptrs])
         base = self.ws.data_ptr()
-        return [q.value - base for q in ptrs]
+        return ExactBuffers(*[q.value - base for q in ptrs])
 
     def q_columns(self):
         """The CG columns Q e_{a_t} of the picks expanded to the grid: [kmax, N] (zero outside
         each box; rows of picks without a column are zero)."""
-        qo, bo, _, so, _, _ = self._buffers()
+        buf = self._buffers()
+        qo, bo, so = buf.qcols, buf.boxlo, buf.slot_of_round
         b0, b1, b2 = self.box
         bv = b0 * b1 * b2
         cols = self.ws[qo: qo + 8 * self.nslots * bv].view(torch.float64).view(self.nslots, b0, b1,
@@ -701,7 +708,7 @@ class ExactWindowGreedy:
 
     def cg_iterations_used(self):
         """Iterations the last CG solve took (the full budget if it did not stop early)."""
-        co = self._buffers()[2]
+        co = self._buffers().cgstate
         st = self.ws[co: co + 8].view(torch.int32)
         return int(st[1]) if int(st[0]) else self.cg_iters
 
