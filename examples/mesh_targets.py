@@ -9,6 +9,10 @@ mesh.  The mesh cells may carry weights (here: all ones unless --weighted, which
 half of the domain twice).
 
     python examples/mesh_targets.py [--sites 10 10 10] [--mesh 24 24 24] [--k 20] [--weighted]
+                                    [--matrix-free]
+
+--matrix-free never assembles K(Xt, X): its entries are generated from the points in every round
+(``cross="matrix_free"``), for a mesh whose cross-covariance does not fit the device.
 """
 import argparse
 import os
@@ -37,7 +41,7 @@ def mesh_variance(X, Xt, picks, ls, chunk_points=None):
     return gprm.variance(chunk_points=chunk_points).cpu().numpy()
 
 
-def run(sites=(10, 10, 10), mesh=(24, 24, 24), k=20, weights=None):
+def run(sites=(10, 10, 10), mesh=(24, 24, 24), k=20, weights=None, matrix_free=False):
     """-> {rule: {"picks", "mean_var", "max_var", "seconds"}}: "mesh" places for the (weighted)
     posterior variance over the mesh, "in-V" for the one over the sites.  ``mean_var`` is the
     weighted mean over the mesh."""
@@ -49,6 +53,8 @@ def run(sites=(10, 10, 10), mesh=(24, 24, 24), k=20, weights=None):
     out = {}
     for rule in RULES:
         kw = {"target_points": Xt, "target_weights": weights} if rule == "mesh" else {}
+        if rule == "mesh" and matrix_free:
+            kw["cross"] = "matrix_free"
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         picks = placement_from_points(X, k, "eq", AMP, ls, NOISE, JITTER, criterion="variance",
@@ -69,12 +75,14 @@ def main():
     ap.add_argument("--k", type=int, default=20, help="sensors to place")
     ap.add_argument("--weighted", action="store_true",
                     help="count the mesh points with |x|_inf <= 1 twice")
+    ap.add_argument("--matrix-free", action="store_true",
+                    help="generate the mesh's cross-covariance in every round, never store it")
     a = ap.parse_args()
     weights = None
     if a.weighted:
         Xt = grid_points(tuple(a.mesh), jitter=0.3, seed=1)
         weights = np.where(np.abs(Xt).max(axis=1) <= 1.0, 2.0, 1.0)
-    res = run(tuple(a.sites), tuple(a.mesh), a.k, weights)
+    res = run(tuple(a.sites), tuple(a.mesh), a.k, weights, a.matrix_free)
     print(f"sites {tuple(a.sites)}, mesh {tuple(a.mesh)}, k = {a.k}, prior variance {AMP * AMP}")
     print("targets   mean variance   max variance   seconds   picks")
     for rule in RULES:

@@ -705,6 +705,53 @@ int vgposp_critx_buffers(void* ws, int64_t n, int64_t P, int kmax, double** nom,
                          double** delta, double** W, double** U);
 
 /* ---------------------------------------------------------------------------------------------
+ * The same rule on a cross-covariance that is never stored: R = diag(a_t) K(Xt, X) diag(a_s) is
+ * generated from the points in every pass.  Xt [P][d] (targets) and X [n][d] (locations) are
+ * row-major fp64, 1 <= d <= 8; kind, amp and ls (device [1]) as in vgposp_kernel_matvec;
+ * target_scale a_t [P] and site_scale a_s [n] (NULL: ones) are a per-point amplitude field.  The
+ * device holds (P + n) d doubles instead of P n.  Limits: P <= 2^24, n <= 2^21.
+ *
+ *   vgposp_kernel_gemv_t     y_j = a_s[j] sum_v x_v a_t[v] k(Xt_v, X_j): vgposp_gemv_t with the
+ *                            load of R_vj replaced by its evaluation (it replaces
+ *                            vgposp_kernel_matvec(X, Xt, x) for this shape: that one parallelises
+ *                            over its n output rows alone).  A 2-D grid of (512-column tile,
+ *                            VGPOSP_KGEMV_ROWS-target chunk) workgroups; one partial per (chunk,
+ *                            column) goes to ws (vgposp_kernel_gemv_t_workspace_bytes(P, n) bytes;
+ *                            0 when P <= 0 or n <= 0), the partials are added in ascending chunk
+ *                            order.  No float atomics, two runs are bit-identical, no host
+ *                            synchronisation.  P == 0 or n == 0 returns 0 without device work.
+ *   vgposp_kernel_gemv_t_sq  every generated entry squared (replaces vgposp_gemv_t_sq):
+ *                            y_j = a_s[j]^2 sum_v x_v a_t[v]^2 k(Xt_v, X_j)^2.
+ *   vgposp_critk_workspace_bytes / _init / _step / _buffers
+ *                            vgposp_critx_* with (R, P, ldr) replaced by (kind, Xt, P, X, d, amp,
+ *                            ls, target_scale, site_scale): the same launch sequence, the column
+ *                            R_{:,a} of a round and the pass generated by one device function.
+ * Argument errors return -(position) before any device work. */
+#define VGPOSP_KGEMV_ROWS 512
+size_t vgposp_kernel_gemv_t_workspace_bytes(int64_t P, int64_t n);
+int vgposp_kernel_gemv_t(int kind, const double* Xt, int64_t P, const double* X, int64_t n, int d,
+                         const double* amp, const double* ls, const double* target_scale,
+                         const double* site_scale, const double* x, double* y, void* ws,
+                         size_t ws_bytes, void* stream);
+int vgposp_kernel_gemv_t_sq(int kind, const double* Xt, int64_t P, const double* X, int64_t n,
+                            int d, const double* amp, const double* ls, const double* target_scale,
+                            const double* site_scale, const double* x, double* y, void* ws,
+                            size_t ws_bytes, void* stream);
+size_t vgposp_critk_workspace_bytes(int64_t n, int64_t P, int kmax);
+int vgposp_critk_init(const double* Sigma, int64_t n, int64_t lda, const double* diag, int kind,
+                      const double* Xt, int64_t P, const double* X, int d, const double* amp,
+                      const double* ls, const double* target_scale, const double* site_scale,
+                      const double* weights, int kmax, double threshold,
+                      const unsigned char* allowed, void* ws, size_t ws_bytes, void* stream);
+int vgposp_critk_step(const double* Sigma, int64_t n, int64_t lda, const double* diag, int kind,
+                      const double* Xt, int64_t P, const double* X, int d, const double* amp,
+                      const double* ls, const double* target_scale, const double* site_scale,
+                      int kmax, int round, const int64_t* forced, int64_t j, int64_t* selected,
+                      double* sel_delta, void* ws, size_t ws_bytes, void* stream);
+int vgposp_critk_buffers(void* ws, int64_t n, int64_t P, int kmax, double** nom, double** score,
+                         double** delta, double** W, double** U);
+
+/* ---------------------------------------------------------------------------------------------
  * Exact algorithm 3 at grid sizes where cov_vv cannot be dense (config C4, 128^3): the beta-decay
  * tapered covariance (main_architecture_2_sampledistribution.py:355-421) is a sparse SPD stencil
  * matrix, and snippets_a3.sparse_placement_algorithm_3 (snippets_a3.py:43-364) with tf_nominator /

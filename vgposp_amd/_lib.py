@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("VGPOSP_LIB", os.path.join(_HERE, "libvgposp.so"))
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vgposp.h")
 
 ABI_VERSION = 2
+KGEMV_ROWS = 512   # VGPOSP_KGEMV_ROWS: targets per row chunk of vgposp_kernel_gemv_t
 E_HIP = -100
 E_WS = -101
 
@@ -52,6 +53,9 @@ _size = ctypes.c_size_t
 _EXACT = [_i32, _c_void_p, _i64, _i64, _i64, _f64, _f64, _f64, _f64, _f64, _c_void_p, _i32,
           _c_void_p, _i32, _i32, _i32, _i32, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
           _size]
+
+# a cross-covariance generated from the points: kind, Xt, P, X, d, amp, ls, target_scale, site_scale
+_KGEN = [_i32, _c_void_p, _i64, _c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p]
 
 # name -> (restype, argtypes)
 SIGNATURES = {
@@ -267,6 +271,19 @@ SIGNATURES = {
                                  _c_void_p]),
     "vgposp_critx_buffers": (_i32, [_c_void_p, _i64, _i64, _i32]
                              + [ctypes.POINTER(_c_void_p)] * 5),
+    "vgposp_kernel_gemv_t_workspace_bytes": (_size, [_i64, _i64]),
+    "vgposp_kernel_gemv_t": (_i32, _KGEN[:4] + [_i64] + _KGEN[4:]
+                             + [_c_void_p, _c_void_p, _c_void_p, _size, _c_void_p]),
+    "vgposp_kernel_gemv_t_sq": (_i32, _KGEN[:4] + [_i64] + _KGEN[4:]
+                                + [_c_void_p, _c_void_p, _c_void_p, _size, _c_void_p]),
+    "vgposp_critk_workspace_bytes": (_size, [_i64, _i64, _i32]),
+    "vgposp_critk_init": (_i32, [_c_void_p, _i64, _i64, _c_void_p] + _KGEN
+                          + [_c_void_p, _i32, _f64, _c_void_p, _c_void_p, _size, _c_void_p]),
+    "vgposp_critk_step": (_i32, [_c_void_p, _i64, _i64, _c_void_p] + _KGEN
+                          + [_i32, _i32, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _size,
+                             _c_void_p]),
+    "vgposp_critk_buffers": (_i32, [_c_void_p, _i64, _i64, _i32]
+                             + [ctypes.POINTER(_c_void_p)] * 5),
 }
 
 _lock = threading.Lock()
@@ -335,6 +352,8 @@ KERNEL_SOURCES = {
     "criteria_symv": ["criteria.hip", "common.h", "Makefile"],
     "criteria_gemv_t": ["criteria.hip", "common.h", "Makefile"],
     "criteria_gemv_t_sq": ["criteria.hip", "common.h", "Makefile"],
+    "criteria_kgemv_t": ["criteria.hip", "psd.h", "common.h", "Makefile"],
+    "criteria_kgemv_t_sq": ["criteria.hip", "psd.h", "common.h", "Makefile"],
     "kernel_matrix": ["kernel_matrix.hip", "psd.h", "common.h", "Makefile"],
     "exact": ["exact_greedy.hip", "psd.h", "common.h", "Makefile"],
 }

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import linalg
-from ._lib import FULL, LOWER, call
+from ._lib import FULL, LOWER, call, query
 from .linalg import F64, _p, _stream, kind_id
 from .psd_kernels import scaled_points
 
@@ -44,6 +44,38 @@ def kernel_matvec(kind, X1, X2, amp, ls, v, out=None, beta=0.0):
     a, l = linalg._vec(amp), linalg._vec(ls)
     call("vgposp_kernel_matvec", kind_id(kind), _p(X1), X1.shape[0], _p(X2), X2.shape[0],
          X1.shape[1], _p(a), _p(l), _p(v), float(beta), _p(out), _stream())
+    return out
+
+
+def kernel_gemv_t(kind, Xt, X, amp, ls, x, squared=False, target_scale=None, site_scale=None,
+                  out=None):
+    """out = R^T x for R = diag(target_scale) K(Xt, X) diag(site_scale), R never formed
+    (``squared``: of the squared entries of R).  Xt [P, d], X [n, d], x [P]; the scales default to
+    ones.  Unlike ``kernel_matvec(kind, X, Xt, ...)`` the launch is parallel over the targets
+    too."""
+    Xt, X = linalg.as_device(Xt), linalg.as_device(X)
+    Xt = (Xt[:, None] if Xt.dim() == 1 else Xt).contiguous()
+    X = (X[:, None] if X.dim() == 1 else X).contiguous()
+    x = linalg.as_device(x).reshape(-1).contiguous()
+    P, n = Xt.shape[0], X.shape[0]
+    if x.numel() != P or Xt.shape[1] != X.shape[1]:
+        raise ValueError("kernel_gemv_t: shapes do not match")
+
+    def scale(a, count):
+        if a is None:
+            return None
+        a = linalg.as_device(a).reshape(-1).contiguous()
+        if a.numel() != count:
+            raise ValueError("kernel_gemv_t: shapes do not match")
+        return a
+    at, a_s = scale(target_scale, P), scale(site_scale, n)
+    if out is None:
+        out = torch.zeros(n, dtype=F64, device=X.device)
+    ws = linalg.workspace(query("vgposp_kernel_gemv_t_workspace_bytes", P, n))
+    a, l = linalg._vec(amp), linalg._vec(ls)   # held until the launch, as in kernel_matvec
+    call("vgposp_kernel_gemv_t_sq" if squared else "vgposp_kernel_gemv_t", kind_id(kind), _p(Xt),
+         P, _p(X), n, X.shape[1], _p(a), _p(l), _p(at), _p(a_s), _p(x), _p(out), _p(ws),
+         ws.numel(), _stream())
     return out
 
 
@@ -110,5 +142,6 @@ def cov_vv_from_vgp(vgp, locations, tp_samples, tr_mean=0.0, tr_stdev=1.0):
     return empirical_cov(vgp_tracer_samples(vgp, locations, tp_samples), tr_mean, tr_stdev)
 
 
-__all__ = ["kernel_matvec", "center_rows_", "empirical_cov", "index_taper_", "vgp_tracer_samples",
+__all__ = ["kernel_matvec", "kernel_gemv_t", "center_rows_", "empirical_cov", "index_taper_",
+           "vgp_tracer_samples",
            "cov_vv_from_vgp"]

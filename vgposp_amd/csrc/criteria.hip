@@ -28,6 +28,7 @@
 #include <cfloat>
 
 #include "common.h"
+#include "psd.h"
 
 namespace vgposp {
 
@@ -443,17 +444,21 @@ __global__ __launch_bounds__(SY_TH) void gemv_t_kernel(const double* __restrict_
   if (in1) out[c + 1] = u0 + u1;
 }
 
-// y_j = the partials of the row tiles 0 .. nt - 1, ascending.
+// y_j = the partials of the row tiles 0 .. nt - 1, ascending; with `scale` (the matrix-free pass)
+// times scale_j, or scale_j^2 when sq.
 __global__ __launch_bounds__(CR_B) void gemv_t_reduce_kernel(int64_t nt, int64_t n,
                                                              const double* __restrict__ part,
                                                              double* __restrict__ y,
-                                                             const double* __restrict__ gate) {
+                                                             const double* __restrict__ gate,
+                                                             const double* scale = nullptr,
+                                                             int sq = 0) {
   if (gate && *gate != 0.0) return;
   const int64_t j = (int64_t)blockIdx.x * CR_B + threadIdx.x;
   if (j >= n) return;
   double s = 0.0;
 #pragma unroll 8
   for (int64_t b = 0; b < nt; ++b) s += part[b * n + j];
+  if (scale) s *= sq ? scale[j] * scale[j] : scale[j];
   y[j] = s;
 }
 
@@ -484,7 +489,9 @@ struct CritXWS {
   size_t bytes;
 };
 
-static CritXWS critx_layout(void* base, int64_t n, int64_t P, int kmax) {
+// part_bytes: the partials of the pass (gemv_t_bytes for a stored R, kgemv_t_bytes for a generated
+// one).
+static CritXWS critx_layout(void* base, int64_t n, int64_t P, int kmax, size_t part_bytes) {
   CritXWS w{};
   w.c = crit_layout(base, n, kmax);
   char* p = static_cast<char*>(base);
@@ -498,7 +505,7 @@ static CritXWS critx_layout(void* base, int64_t n, int64_t P, int kmax) {
   w.wu = take((size_t)P * 8);
   w.omega = take((size_t)P * 8);
   w.dpart = take((size_t)kmax * ceil_div(P, CR_B) * 8);
-  w.gemv = take(gemv_t_bytes(P, n));
+  w.gemv = take(part_bytes);
   w.bytes = off;
   return w;
 }
@@ -531,6 +538,152 @@ __global__ __launch_bounds__(CR_B) void critx_urow_kernel(const double* R, int64
   const double u = noma >= w.c.prm[0] && noma > 0.0 ? s / sqrt(noma) : 0.0;
   w.U[(int64_t)round * P + v] = u;
   w.wu[v] = w.omega[v] * u;
+}
+
+// ---- a cross-covariance generated from the points: R = diag(a_t) K(Xt, X) diag(a_s) ----
+// Xt [P][d], X [n][d] row-major, one stationary kernel (kind, amp, ls: device [1]) under a per-point
+// amplitude field (a_t [P], a_s [n]; NULL: ones).  R is never stored: every entry is kentry<> of
+// psd.h on 2 d coordinates, in the pass, in its squared form and in the u-row of a round alike.
+struct KGen {
+  int kind, d;
+  const double *Xt, *X, *amp, *ls, *at, *as;
+};
+
+constexpr int KG_ROWS = VGPOSP_KGEMV_ROWS;  // targets per row chunk
+static_assert(KG_ROWS == SY_T, "the partials and their reduction are those of gemv_t");
+
+static size_t kgemv_t_bytes(int64_t P, int64_t n) {
+  return cr_align((size_t)ceil_div(P, KG_ROWS) * n * 8);
+}
+
+// One (512-column tile, KG_ROWS-target chunk) of y = R^T x (SQ: of the squared entries), the shape
+// of gemv_t_kernel with the load of R replaced by its evaluation:
+//   part[blockIdx.y][c] = sum over the chunk's targets v of k(Xt_v, X_c)^p x_v a_t[v]^p,  p = 1 + SQ
+// (a_s is applied once per column by the reduction).  A thread keeps the coordinates of its column
+// pair (c, c + 1) in registers; the chunk's target coordinates and x_v a_t[v]^p are staged in LDS
+// once, a row of D + 1 doubles per target, and read back as wave-uniform broadcasts.  D == 0: the
+// dimension at run time (4 .. 8), rows of 9 doubles.
+template <int KIND, int D, bool SQ>
+__global__ __launch_bounds__(SY_TH) void kgemv_t_kernel(KGen g, int64_t P, int64_t n,
+                                                        const double* __restrict__ x,
+                                                        double* __restrict__ part,
+                                                        const double* __restrict__ gate) {
+  constexpr int DW = (D > 0 ? D : 8) + 1;
+  __shared__ double rows[KG_ROWS * DW];
+  if (gate && *gate != 0.0) return;  // workgroup-uniform: no barrier is left waiting
+  const int dd = D > 0 ? D : g.d;
+  const int64_t r0 = (int64_t)blockIdx.y * KG_ROWS;
+  const int nrow = (int)min((int64_t)KG_ROWS, P - r0);
+  for (int e = threadIdx.x; e < nrow * dd; e += SY_TH) {
+    const int i = e / dd;
+    rows[i * DW + (e - i * dd)] = g.Xt[r0 * dd + e];
+  }
+  for (int i = threadIdx.x; i < nrow; i += SY_TH) {
+    const double a = g.at ? g.at[r0 + i] : 1.0;
+    rows[i * DW + DW - 1] = x[r0 + i] * (SQ ? a * a : a);
+  }
+  const int64_t c = (int64_t)blockIdx.x * SY_T + 2 * threadIdx.x;
+  const bool in0 = c < n, in1 = c + 1 < n;
+  double xa[8], xb[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    xa[k] = (k < dd && in0) ? g.X[c * dd + k] : 0.0;
+    xb[k] = (k < dd && in1) ? g.X[(c + 1) * dd + k] : 0.0;
+  }
+  const double tla = 2.0 * log(g.amp[0]), inv_l = 1.0 / g.ls[0], inv_l2 = inv_l * inv_l;
+  __syncthreads();
+  if (!in0) return;
+  double s0 = 0.0, s1 = 0.0, u0 = 0.0, u1 = 0.0;  // column c: s0 + s1, column c + 1: u0 + u1
+  auto row = [&](int i, double& a, double& b) {
+    const double* t = rows + i * DW;
+    double ka = kentry<KIND, D>(t, xa, dd, tla, inv_l, inv_l2);
+    double kb = kentry<KIND, D>(t, xb, dd, tla, inv_l, inv_l2);
+    if (SQ) {
+      ka *= ka;
+      kb *= kb;
+    }
+    const double xw = t[DW - 1];
+    a = fma(ka, xw, a);
+    b = fma(kb, xw, b);
+  };
+  int i = 0;
+  for (; i + 1 < nrow; i += 2) {
+    row(i, s0, u0);
+    row(i + 1, s1, u1);
+  }
+  if (i < nrow) row(i, s0, u0);
+  double* out = part + (int64_t)blockIdx.y * n;
+  out[c] = s0 + s1;
+  if (in1) out[c + 1] = u0 + u1;
+}
+
+template <int KIND, bool SQ>
+static void kgemv_t_launch_kind(const KGen& g, int64_t P, int64_t n, const double* x, double* part,
+                                const double* gate, hipStream_t s) {
+  const dim3 grid((unsigned)ceil_div(n, SY_T), (unsigned)ceil_div(P, KG_ROWS));
+#define KG_CASE(DD, DT)                                                                          \
+  case DD:                                                                                       \
+    hipLaunchKernelGGL((kgemv_t_kernel<KIND, DT, SQ>), grid, dim3(SY_TH), 0, s, g, P, n, x, part, \
+                       gate);                                                                    \
+    break;
+  switch (g.d) { KG_CASE(1, 1) KG_CASE(2, 2) KG_CASE(3, 3) default: KG_CASE(0, 0) }
+#undef KG_CASE
+}
+
+// y_j = a_s[j]^p sum_v x_v a_t[v]^p k(Xt_v, X_j)^p: the pass, then gemv_t's reduction of the
+// partials in ascending chunk order with the site scale.  gate as in gemv_t_launch.
+template <bool SQ>
+static void kgemv_t_launch(const KGen& g, int64_t P, int64_t n, const double* x, double* y,
+                           double* part, const double* gate, hipStream_t s) {
+  {
+    const double pn = (double)P * (double)n;
+    ProfScope ps(SQ ? "criteria_kgemv_t_sq" : "criteria_kgemv_t", s, (3.0 * g.d + 32.0) * pn,
+                 8.0 * (double)(P + n) * (g.d + 1));
+    switch (g.kind) {
+      case VGPOSP_KERNEL_EQ: kgemv_t_launch_kind<VGPOSP_KERNEL_EQ, SQ>(g, P, n, x, part, gate, s); break;
+      case VGPOSP_KERNEL_MATERN12: kgemv_t_launch_kind<VGPOSP_KERNEL_MATERN12, SQ>(g, P, n, x, part, gate, s); break;
+      case VGPOSP_KERNEL_MATERN32: kgemv_t_launch_kind<VGPOSP_KERNEL_MATERN32, SQ>(g, P, n, x, part, gate, s); break;
+      default: kgemv_t_launch_kind<VGPOSP_KERNEL_MATERN52, SQ>(g, P, n, x, part, gate, s); break;
+    }
+  }
+  hipLaunchKernelGGL(gemv_t_reduce_kernel, dim3((unsigned)ceil_div(n, CR_B)), dim3(CR_B), 0, s,
+                     ceil_div(P, KG_ROWS), n, part, y, gate, g.as, SQ ? 1 : 0);
+}
+
+// critx_urow_kernel with R_va generated: a_t[v] k(Xt_v, X_a) a_s[a], the entry the pass sums.
+template <int KIND>
+__global__ __launch_bounds__(CR_B) void critk_urow_kernel(KGen g, int64_t P,
+                                                          const int64_t* selected, int round,
+                                                          CritXWS w) {
+  const int64_t v = (int64_t)blockIdx.x * CR_B + threadIdx.x;
+  const int64_t a = selected[round];
+  if (v >= P || a < 0) return;
+  double xt[8], xa[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    xt[k] = k < g.d ? g.Xt[v * g.d + k] : 0.0;
+    xa[k] = k < g.d ? g.X[a * g.d + k] : 0.0;
+  }
+  const double tla = 2.0 * log(g.amp[0]), inv_l = 1.0 / g.ls[0], inv_l2 = inv_l * inv_l;
+  double s = kentry<KIND, 0>(xt, xa, g.d, tla, inv_l, inv_l2);
+  if (g.at) s *= g.at[v];
+  if (g.as) s *= g.as[a];
+  for (int t = 0; t < round; ++t) s -= w.c.piv[1 + t] * w.U[(int64_t)t * P + v];
+  const double noma = w.c.piv[0];
+  const double u = noma >= w.c.prm[0] && noma > 0.0 ? s / sqrt(noma) : 0.0;
+  w.U[(int64_t)round * P + v] = u;
+  w.wu[v] = w.omega[v] * u;
+}
+
+static void critk_urow_launch(const KGen& g, int64_t P, const int64_t* selected, int round,
+                              const CritXWS& w, hipStream_t s) {
+  const dim3 grid((unsigned)ceil_div(P, CR_B));
+  switch (g.kind) {
+    case VGPOSP_KERNEL_EQ: hipLaunchKernelGGL(critk_urow_kernel<VGPOSP_KERNEL_EQ>, grid, dim3(CR_B), 0, s, g, P, selected, round, w); break;
+    case VGPOSP_KERNEL_MATERN12: hipLaunchKernelGGL(critk_urow_kernel<VGPOSP_KERNEL_MATERN12>, grid, dim3(CR_B), 0, s, g, P, selected, round, w); break;
+    case VGPOSP_KERNEL_MATERN32: hipLaunchKernelGGL(critk_urow_kernel<VGPOSP_KERNEL_MATERN32>, grid, dim3(CR_B), 0, s, g, P, selected, round, w); break;
+    default: hipLaunchKernelGGL(critk_urow_kernel<VGPOSP_KERNEL_MATERN52>, grid, dim3(CR_B), 0, s, g, P, selected, round, w); break;
+  }
 }
 
 }  // namespace vgposp
@@ -708,7 +861,7 @@ extern "C" int vgposp_gemv_t_sq(const double* R, int64_t P, int64_t n, int64_t l
 
 extern "C" size_t vgposp_critx_workspace_bytes(int64_t n, int64_t P, int kmax) {
   if (n <= 0 || P <= 0 || kmax <= 0) return 0;
-  return critx_layout(nullptr, n, P, kmax).bytes;
+  return critx_layout(nullptr, n, P, kmax, gemv_t_bytes(P, n)).bytes;
 }
 
 extern "C" int vgposp_critx_init(const double* Sigma, int64_t n, int64_t lda, const double* diag,
@@ -725,7 +878,7 @@ extern "C" int vgposp_critx_init(const double* Sigma, int64_t n, int64_t lda, co
   VG_CHECK_ARG(kmax >= 1 && kmax <= n, 9);
   VG_CHECK_ARG(threshold >= 0.0, 10);
   VG_CHECK_ARG(ws != nullptr, 12);
-  const CritXWS w = critx_layout(ws, n, P, kmax);
+  const CritXWS w = critx_layout(ws, n, P, kmax, gemv_t_bytes(P, n));
   VG_CHECK_WS(ws_bytes, w.bytes);
   hipStream_t s = as_stream(stream);
   hipLaunchKernelGGL(crit_init_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, Sigma, n,
@@ -755,7 +908,7 @@ extern "C" int vgposp_critx_step(const double* Sigma, int64_t n, int64_t lda, co
   VG_CHECK_ARG(forced == nullptr || j >= 0, 11);
   VG_CHECK_ARG(selected != nullptr, 12);
   VG_CHECK_ARG(ws != nullptr, 14);
-  const CritXWS w = critx_layout(ws, n, P, kmax);
+  const CritXWS w = critx_layout(ws, n, P, kmax, gemv_t_bytes(P, n));
   VG_CHECK_WS(ws_bytes, w.bytes);
   const CritWS tv = critx_target_view(w);
   hipStream_t s = as_stream(stream);
@@ -800,7 +953,182 @@ extern "C" int vgposp_critx_buffers(void* ws, int64_t n, int64_t P, int kmax, do
   VG_CHECK_ARG(n >= 1, 2);
   VG_CHECK_ARG(P >= 1, 3);
   VG_CHECK_ARG(kmax >= 1, 4);
-  const CritXWS w = critx_layout(ws, n, P, kmax);
+  const CritXWS w = critx_layout(ws, n, P, kmax, gemv_t_bytes(P, n));
+  if (nom) *nom = w.c.nom;
+  if (score) *score = w.c.s;
+  if (delta) *delta = w.c.delta;
+  if (W) *W = w.c.W;
+  if (U) *U = w.U;
+  return 0;
+}
+
+// ---- the matrix-free pass and the rounds on a generated R ----
+extern "C" size_t vgposp_kernel_gemv_t_workspace_bytes(int64_t P, int64_t n) {
+  if (P <= 0 || n <= 0) return 0;
+  return kgemv_t_bytes(P, n);
+}
+
+template <bool SQ>
+static int kgemv_t_entry(const char* fn, int kind, const double* Xt, int64_t P, const double* X,
+                         int64_t n, int d, const double* amp, const double* ls,
+                         const double* target_scale, const double* site_scale, const double* x,
+                         double* y, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  if (P == 0 || n == 0) return 0;
+#define KG_ARG(cond, idx)                                \
+  if (!(cond)) {                                         \
+    set_error("%s: bad argument %d (%s)", fn, idx, #cond); \
+    return -(idx);                                       \
+  }
+  KG_ARG(kind >= VGPOSP_KERNEL_EQ && kind <= VGPOSP_KERNEL_MATERN52, 1)
+  KG_ARG(Xt != nullptr, 2)
+  KG_ARG(P >= 1 && P <= CRX_PMAX, 3)
+  KG_ARG(X != nullptr, 4)
+  KG_ARG(n >= 1 && n <= CR_NMAX, 5)
+  KG_ARG(d >= 1 && d <= 8, 6)
+  KG_ARG(amp != nullptr, 7)
+  KG_ARG(ls != nullptr, 8)
+  KG_ARG(x != nullptr, 11)
+  KG_ARG(y != nullptr, 12)
+#undef KG_ARG
+  if (ws == nullptr) { set_error("%s: workspace is null", fn); return VGPOSP_E_WS; }
+  const size_t need = kgemv_t_bytes(P, n);
+  if (ws_bytes < need) {
+    set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, need);
+    return VGPOSP_E_WS;
+  }
+  const KGen g{kind, d, Xt, X, amp, ls, target_scale, site_scale};
+  kgemv_t_launch<SQ>(g, P, n, x, y, static_cast<double*>(ws), nullptr, as_stream(stream));
+  VG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int vgposp_kernel_gemv_t(int kind, const double* Xt, int64_t P, const double* X,
+                                    int64_t n, int d, const double* amp, const double* ls,
+                                    const double* target_scale, const double* site_scale,
+                                    const double* x, double* y, void* ws, size_t ws_bytes,
+                                    void* stream) {
+  return kgemv_t_entry<false>(__func__, kind, Xt, P, X, n, d, amp, ls, target_scale, site_scale,
+                              x, y, ws, ws_bytes, stream);
+}
+
+extern "C" int vgposp_kernel_gemv_t_sq(int kind, const double* Xt, int64_t P, const double* X,
+                                       int64_t n, int d, const double* amp, const double* ls,
+                                       const double* target_scale, const double* site_scale,
+                                       const double* x, double* y, void* ws, size_t ws_bytes,
+                                       void* stream) {
+  return kgemv_t_entry<true>(__func__, kind, Xt, P, X, n, d, amp, ls, target_scale, site_scale, x,
+                             y, ws, ws_bytes, stream);
+}
+
+extern "C" size_t vgposp_critk_workspace_bytes(int64_t n, int64_t P, int kmax) {
+  if (n <= 0 || P <= 0 || kmax <= 0) return 0;
+  return critx_layout(nullptr, n, P, kmax, kgemv_t_bytes(P, n)).bytes;
+}
+
+extern "C" int vgposp_critk_init(const double* Sigma, int64_t n, int64_t lda, const double* diag,
+                                 int kind, const double* Xt, int64_t P, const double* X, int d,
+                                 const double* amp, const double* ls, const double* target_scale,
+                                 const double* site_scale, const double* weights, int kmax,
+                                 double threshold, const unsigned char* allowed, void* ws,
+                                 size_t ws_bytes, void* stream) {
+  clear_error();
+  VG_CHECK_ARG(Sigma != nullptr, 1);
+  VG_CHECK_ARG(n >= 1 && n <= CR_NMAX, 2);
+  VG_CHECK_ARG(lda >= n, 3);
+  VG_CHECK_ARG(kind >= VGPOSP_KERNEL_EQ && kind <= VGPOSP_KERNEL_MATERN52, 5);
+  VG_CHECK_ARG(Xt != nullptr, 6);
+  VG_CHECK_ARG(P >= 1 && P <= CRX_PMAX, 7);
+  VG_CHECK_ARG(X != nullptr, 8);
+  VG_CHECK_ARG(d >= 1 && d <= 8, 9);
+  VG_CHECK_ARG(amp != nullptr, 10);
+  VG_CHECK_ARG(ls != nullptr, 11);
+  VG_CHECK_ARG(kmax >= 1 && kmax <= n, 15);
+  VG_CHECK_ARG(threshold >= 0.0, 16);
+  VG_CHECK_ARG(ws != nullptr, 18);
+  const CritXWS w = critx_layout(ws, n, P, kmax, kgemv_t_bytes(P, n));
+  VG_CHECK_WS(ws_bytes, w.bytes);
+  hipStream_t s = as_stream(stream);
+  hipLaunchKernelGGL(crit_init_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, Sigma, n,
+                     lda, diag, VGPOSP_CRIT_VARIANCE, threshold, nullptr, allowed, w.c);
+  hipLaunchKernelGGL(critx_init_kernel, dim3((unsigned)ceil_div(P, 256)), dim3(256), 0, s, P,
+                     weights, w);
+  VG_LAUNCH_CHECK();
+  // s_y = sum_v omega_v R_vy^2
+  const KGen g{kind, d, Xt, X, amp, ls, target_scale, site_scale};
+  kgemv_t_launch<true>(g, P, n, w.omega, w.c.s, w.gemv, nullptr, s);
+  VG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int vgposp_critk_step(const double* Sigma, int64_t n, int64_t lda, const double* diag,
+                                 int kind, const double* Xt, int64_t P, const double* X, int d,
+                                 const double* amp, const double* ls, const double* target_scale,
+                                 const double* site_scale, int kmax, int round,
+                                 const int64_t* forced, int64_t j, int64_t* selected,
+                                 double* sel_delta, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  VG_CHECK_ARG(Sigma != nullptr, 1);
+  VG_CHECK_ARG(n >= 1 && n <= CR_NMAX, 2);
+  VG_CHECK_ARG(lda >= n, 3);
+  VG_CHECK_ARG(kind >= VGPOSP_KERNEL_EQ && kind <= VGPOSP_KERNEL_MATERN52, 5);
+  VG_CHECK_ARG(Xt != nullptr, 6);
+  VG_CHECK_ARG(P >= 1 && P <= CRX_PMAX, 7);
+  VG_CHECK_ARG(X != nullptr, 8);
+  VG_CHECK_ARG(d >= 1 && d <= 8, 9);
+  VG_CHECK_ARG(amp != nullptr, 10);
+  VG_CHECK_ARG(ls != nullptr, 11);
+  VG_CHECK_ARG(kmax >= 1 && kmax <= n, 14);
+  VG_CHECK_ARG(round >= 0 && round < kmax, 15);
+  VG_CHECK_ARG(forced == nullptr || j >= 0, 17);
+  VG_CHECK_ARG(selected != nullptr, 18);
+  VG_CHECK_ARG(ws != nullptr, 20);
+  const CritXWS w = critx_layout(ws, n, P, kmax, kgemv_t_bytes(P, n));
+  VG_CHECK_WS(ws_bytes, w.bytes);
+  const CritWS tv = critx_target_view(w);
+  const KGen g{kind, d, Xt, X, amp, ls, target_scale, site_scale};
+  hipStream_t s = as_stream(stream);
+  const unsigned nb = (unsigned)ceil_div(n, CR_B), nbp = (unsigned)ceil_div(P, CR_B);
+  {
+    ProfScope ps("criteria_select", s, 0.0, 8.0 * 3.0 * n);
+    hipLaunchKernelGGL(crit_score_kernel, dim3((unsigned)ceil_div(n, CR_CH)), dim3(CR_CH), 0, s, n,
+                       w.c);
+    hipLaunchKernelGGL(crit_select_kernel, dim3(1), dim3(CR_CH), 0, s, n, round, forced, j,
+                       selected, sel_delta, w.c);
+    VG_LAUNCH_CHECK();
+  }
+  {
+    ProfScope ps("criteria_row", s, 0.0,
+                 8.0 * ((double)n * (5 + round) + (double)P * (4 + d + round)));
+    hipLaunchKernelGGL(crit_row_kernel, dim3(nb), dim3(CR_B), 0, s, Sigma, n, lda, diag, selected,
+                       round, w.c);
+    critk_urow_launch(g, P, selected, round, w, s);
+    VG_LAUNCH_CHECK();
+  }
+  // dot[t] = U_t . (omega.u) for t <= round (t = round: sum_v omega_v u_v^2), over P
+  hipLaunchKernelGGL(crit_dots_kernel, dim3(nbp, (unsigned)round + 1), dim3(CR_B), 0, s, P,
+                     selected, round, tv);
+  hipLaunchKernelGGL(crit_fold_kernel, dim3((unsigned)round + 1), dim3(CR_B), 0, s, (int64_t)nbp,
+                     selected, round, tv);
+  VG_LAUNCH_CHECK();
+  kgemv_t_launch<false>(g, P, n, w.wu, w.c.g, w.gemv, w.c.prm + 1, s);
+  VG_LAUNCH_CHECK();
+  {
+    ProfScope ps("criteria_update", s, 0.0, 8.0 * (double)n * (4 + round));
+    hipLaunchKernelGGL(crit_update_kernel, dim3(nb), dim3(CR_B), 0, s, n, selected, round, w.c);
+    VG_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+extern "C" int vgposp_critk_buffers(void* ws, int64_t n, int64_t P, int kmax, double** nom,
+                                    double** score, double** delta, double** W, double** U) {
+  clear_error();
+  VG_CHECK_ARG(ws != nullptr, 1);
+  VG_CHECK_ARG(n >= 1, 2);
+  VG_CHECK_ARG(P >= 1, 3);
+  VG_CHECK_ARG(kmax >= 1, 4);
+  const CritXWS w = critx_layout(ws, n, P, kmax, kgemv_t_bytes(P, n));
   if (nom) *nom = w.c.nom;
   if (score) *score = w.c.s;
   if (delta) *delta = w.c.delta;

@@ -23,6 +23,26 @@ __device__ __forceinline__ double kfun(double d2, double two_log_amp, double inv
   return (1.0 + s + s * s * (1.0 / 3.0)) * exp(two_log_amp - s);
 }
 
+// One entry k(a, b) of a kernel matrix generated from the points: coordinates in, entry out.  D > 0:
+// the dimension at compile time; D == 0: d <= 8 at run time.  The squared distance is summed in
+// ascending coordinate order with explicit fmas, so every kernel that calls this (the matrix-free
+// pass of criteria.hip, its squared form, the u-row of a round) rounds an entry the same way.
+template <int KIND, int D>
+__device__ __forceinline__ double kentry(const double* __restrict__ a, const double* __restrict__ b,
+                                         int d, double two_log_amp, double inv_ls, double inv_ls2) {
+  const int dd = D > 0 ? D : d;
+  const double e0 = a[0] - b[0];
+  double d2 = e0 * e0;
+#pragma unroll
+  for (int k = 1; k < 8; ++k) {
+    if (k < dd) {
+      const double e = a[k] - b[k];
+      d2 = fma(e, e, d2);
+    }
+  }
+  return kfun<KIND>(d2, two_log_amp, inv_ls, inv_ls2);
+}
+
 // K, dK/dls and the coefficient c with dK/dx1 = c * (x1 - x2), for one entry.
 template <int KIND>
 __device__ __forceinline__ void kvjp_entry(double d2, double tla, double inv_l, double inv_l2,

@@ -301,7 +301,7 @@ def dg_create_random_cov(n, rng=None):
 
 def placement_from_points(X, k, kind="eq", amp=1.0, ls=1.0, noise=1e-2, jitter=1e-6, lazy=True,
                           candidates=None, placed=None, criterion="mi", targets=None,
-                          target_points=None, target_weights=None):
+                          target_points=None, target_weights=None, cross=None):
     """Assemble Sigma = K(X, X) + (noise + jitter) I on device and place k sensors.
 
     ``criterion``: ``"mi"`` (mutual information, the default), or ``"variance"`` / ``"entropy"``
@@ -310,7 +310,15 @@ def placement_from_points(X, k, kind="eq", amp=1.0, ls=1.0, noise=1e-2, jitter=1
 
     ``target_points`` Xt [P, d] (``"variance"`` alone, instead of ``targets``): the posterior
     variance of the latent field counts at these points, which need not be rows of X; the cross-
-    covariance K(Xt, X) is assembled without noise.  ``target_weights`` [P] >= 0 weigh them."""
+    covariance K(Xt, X) is assembled without noise.  ``target_weights`` [P] >= 0 weigh them.
+    ``cross``: ``"dense"`` (the default) assembles K(Xt, X) [P, N] once; ``"matrix_free"`` never
+    does and generates its entries from the points in every round (placement_criteria.CrossKernel),
+    for a mesh whose cross-covariance does not fit the device."""
+    if cross is not None:
+        if target_points is None:
+            raise ValueError("cross needs target_points")
+        if cross not in ("dense", "matrix_free"):
+            raise ValueError(f"unknown cross {cross!r}; expected 'dense' or 'matrix_free'")
     if target_points is not None:
         if criterion != "variance":
             raise ValueError("target_points apply to criterion='variance' only")
@@ -335,13 +343,15 @@ def placement_from_points(X, k, kind="eq", amp=1.0, ls=1.0, noise=1e-2, jitter=1
                              f"{list(CRITERIA)}")
     K = linalg.kernel_matrix(kind, X, None, amp, ls, diag_shift=noise + jitter)[0]
     if criterion != "mi":
-        from .placement_criteria import CriterionPlacement
-        R = None
-        if target_points is not None:
+        from .placement_criteria import CriterionPlacement, CrossKernel
+        R = gen = None
+        if cross == "matrix_free":
+            gen = CrossKernel(kind, X, Xt, amp, ls)
+        elif target_points is not None:
             R = linalg.kernel_matrix(kind, Xt, X, amp, ls)[0]
         g = CriterionPlacement(K, k, criterion, candidates=candidates, placed=placed,
-                               targets=targets, cross_cov=R,
-                               target_weights=target_weights).run(k)
+                               targets=targets, cross_cov=R, target_weights=target_weights,
+                               cross_kernel=gen).run(k)
         return g.result()[0]
     g = GreedyPlacement(K, k, candidates=candidates, placed=placed).run(k, lazy=lazy)
     return g.result()[0]

@@ -24,6 +24,11 @@ rows of ``cov_vv`` (a finer mesh, the latent field without sensor noise) and the
 rule is delta_y = sum_v omega_v D_vy^2 / C_yy with D = R - R_{:,A} Sigma_AA^-1 Sigma_{A,:}: the drop
 of the weighted total posterior variance of the targets.  One pass per round over R
 (``vgposp_gemv_t``) replaces the pass over Sigma; the state gains the target-side rows U.
+
+A mesh too fine to store R: ``cross_kernel`` = ``CrossKernel(kind, points, target_points, amp,
+ls, ...)`` instead of ``cross_cov`` runs the same rounds with every entry of R generated from the
+2 d coordinates of its target and its location (``vgposp_kernel_gemv_t``), so the device holds
+(P + N) d doubles instead of P N.
 """
 from __future__ import annotations
 
@@ -63,11 +68,75 @@ def _criterion_id(criterion):
         raise ValueError(f"unknown criterion {criterion!r}; expected one of {list(CRITERIA)}")
 
 
-def check_cross_arguments(criterion, targets, cross_cov, target_weights):
-    """The combinations ``cross_cov`` / ``target_weights`` do not allow (ValueError)."""
+class CrossKernel:
+    """A cross-covariance that is never stored: R = diag(target_scale) K(target_points, points)
+    diag(site_scale) for one stationary kernel ``kind`` (``amp``, ``ls`` scalars) under a per-point
+    amplitude field.  ``points`` [N, d] are the locations of ``cov_vv``, ``target_points`` [P, d]
+    the targets, d <= 8; the scales (default ones) are finite and positive.  Everything is held
+    on the device: (P + N) (d + 1) doubles instead of P N."""
+
+    def __init__(self, kind, points, target_points, amp, ls, site_scale=None, target_scale=None):
+        self.kind = linalg.kind_id(kind)
+
+        def pts(name, X):
+            X = linalg.as_device(X)
+            X = X[:, None] if X.dim() == 1 else X
+            if X.dim() != 2 or X.shape[0] < 1:
+                raise ValueError(f"{name} must be [count, d] with count >= 1, got "
+                                 f"{tuple(X.shape)}")
+            return X.contiguous()
+        self.X, self.Xt = pts("points", points), pts("target_points", target_points)
+        self.N, self.d = int(self.X.shape[0]), int(self.X.shape[1])
+        self.P = int(self.Xt.shape[0])
+        if not 1 <= self.d <= 8:
+            raise ValueError(f"points must have 1 <= d <= 8 coordinates, got {self.d}")
+        if self.Xt.shape[1] != self.d:
+            raise ValueError(f"target_points must be [P, {self.d}], got {tuple(self.Xt.shape)}")
+        for name, v in (("amp", amp), ("ls", ls)):
+            if not (np.ndim(v) == 0 and np.isfinite(float(v)) and float(v) > 0.0):
+                raise ValueError(f"{name} must be a finite, positive scalar, got {v!r}")
+        self.amp, self.ls = linalg._vec(float(amp)), linalg._vec(float(ls))
+
+        def scale(name, a, count):
+            if a is None:
+                return None
+            a = (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a))
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.shape != (count,):
+                raise ValueError(f"{name} must have length {count}, got shape {a.shape}")
+            if not np.isfinite(a).all() or (a <= 0.0).any():
+                raise ValueError(f"{name} must be finite and positive")
+            return linalg.as_device(a)
+        self.site_scale = scale("site_scale", site_scale, self.N)
+        self.target_scale = scale("target_scale", target_scale, self.P)
+
+    def args(self):
+        """(kind, Xt, P, X, d, amp, ls, target_scale, site_scale) as the vgposp_critk_* entries
+        take them."""
+        return (self.kind, _p(self.Xt), self.P, _p(self.X), self.d, _p(self.amp), _p(self.ls),
+                _p(self.target_scale), _p(self.site_scale))
+
+
+def check_cross_arguments(criterion, targets, cross_cov, target_weights, cross_kernel=None):
+    """The combinations ``cross_cov`` / ``cross_kernel`` / ``target_weights`` do not allow
+    (ValueError)."""
+    if cross_kernel is not None:
+        if cross_cov is not None:
+            raise ValueError("cross_kernel and cross_cov exclude each other: the one generates "
+                             "what the other stores")
+        if not isinstance(cross_kernel, CrossKernel):
+            raise ValueError("cross_kernel must be a placement_criteria.CrossKernel")
+        cross_cov = cross_kernel
     if target_weights is not None and cross_cov is None:
         raise ValueError("target_weights need cross_cov: targets inside V are not weighted")
     if cross_cov is None:
+        return
+    if cross_kernel is not None:
+        if criterion != "variance":
+            raise ValueError("cross_kernel and target_weights apply to criterion='variance' only")
+        if targets is not None:
+            raise ValueError("cross_kernel and targets exclude each other: target_points are "
+                             "the targets")
         return
     if criterion != "variance":
         raise ValueError("cross_cov and target_weights apply to criterion='variance' only")
@@ -110,10 +179,14 @@ class CriterionPlacement:
     ``cross_cov`` [P, N] (variance rule only, instead of ``targets``) judges the placement at P
     targets outside V, weighted by ``target_weights`` [P] >= 0; like ``Sigma`` it is used where it
     lies when it is a device float64 tensor with unit column stride, and only read.
+
+    ``cross_kernel`` (a ``CrossKernel``, instead of ``cross_cov``) runs the same rounds on a
+    cross-covariance generated from the points in every pass and never stored.
     """
 
     def __init__(self, Sigma, kmax, criterion="variance", candidates=None, placed=None,
-                 targets=None, threshold=1e-8, diag=None, cross_cov=None, target_weights=None):
+                 targets=None, threshold=1e-8, diag=None, cross_cov=None, target_weights=None,
+                 cross_kernel=None):
         self.criterion = criterion
         self.crit = _criterion_id(criterion)
         S = _device_matrix(Sigma)
@@ -127,9 +200,15 @@ class CriterionPlacement:
         self.targets = normalize_targets(self.N, targets)
         if self.targets is not None and self.crit != CRITERIA["variance"]:
             raise ValueError("targets apply to criterion='variance' only")
-        check_cross_arguments(criterion, targets, cross_cov, target_weights)
+        check_cross_arguments(criterion, targets, cross_cov, target_weights, cross_kernel)
         self.R = self.omega = None
+        self.gen = cross_kernel
         self.P = 0
+        if self.gen is not None:
+            if self.gen.N != self.N:
+                raise ValueError(f"cross_kernel has {self.gen.N} points, cov_vv {self.N} locations")
+            self.P = self.gen.P
+            self.omega = normalize_weights(self.P, target_weights)
         if cross_cov is not None:
             self.R = _device_matrix(cross_cov)
             if self.R.dim() != 2 or self.R.shape[1] != self.N or self.R.shape[0] < 1:
@@ -155,7 +234,9 @@ class CriterionPlacement:
         self._allowed_dev, self._targets_dev = mask(self.allowed), mask(self.targets)
         self._placed_dev = (torch.as_tensor(self.placed, dtype=torch.int64, device=dev)
                             if self.m else None)
-        if self.R is None:
+        if self.gen is not None:
+            nbytes = query("vgposp_critk_workspace_bytes", self.n, self.P, self.kmax)
+        elif self.R is None:
             nbytes = query("vgposp_crit_workspace_bytes", self.n, self.kmax)
         else:
             nbytes = query("vgposp_critx_workspace_bytes", self.n, self.P, self.kmax)
@@ -173,13 +254,19 @@ class CriterionPlacement:
     def _step(self, r, forced=None, j=0):
         tail = (r, _p(forced), j, _p(self.selected), _p(self.sel_delta), _p(self.ws),
                 self.ws.numel(), _stream())
-        if self.R is None:
+        if self.gen is not None:
+            call("vgposp_critk_step", *self._sigma_args(), *self.gen.args(), self.kmax, *tail)
+        elif self.R is None:
             call("vgposp_crit_step", *self._sigma_args(), self.kmax, *tail)
         else:
             call("vgposp_critx_step", *self._sigma_args(), *self._cross_args(), self.kmax, *tail)
 
     def init(self):
-        if self.R is None:
+        if self.gen is not None:
+            call("vgposp_critk_init", *self._sigma_args(), *self.gen.args(), _p(self.omega),
+                 self.kmax, self.threshold, _p(self._allowed_dev), _p(self.ws), self.ws.numel(),
+                 _stream())
+        elif self.R is None:
             call("vgposp_crit_init", *self._sigma_args(), self.kmax, self.crit, self.threshold,
                  _p(self._targets_dev), _p(self._allowed_dev), _p(self.ws), self.ws.numel(),
                  _stream())
@@ -208,13 +295,15 @@ class CriterionPlacement:
     def state(self):
         """Device views into the workspace: ``nom`` [N] (C_yy), ``s`` [N] (sum_T C_vy^2, or
         sum_v omega_v D_vy^2), ``delta`` [N] (as scored by the last round, before its pick),
-        ``W`` [placed + rounds, N] and, with ``cross_cov``, ``U`` [placed + rounds, P]."""
-        ptr = [ctypes.c_void_p() for _ in range(4 if self.R is None else 5)]
-        if self.R is None:
+        ``W`` [placed + rounds, N] and, with ``cross_cov`` or ``cross_kernel``, ``U``
+        [placed + rounds, P]."""
+        cross = self.R is not None or self.gen is not None
+        ptr = [ctypes.c_void_p() for _ in range(5 if cross else 4)]
+        if not cross:
             call("vgposp_crit_buffers", _p(self.ws), self.n, self.kmax, *map(ctypes.byref, ptr))
         else:
-            call("vgposp_critx_buffers", _p(self.ws), self.n, self.P, self.kmax,
-                 *map(ctypes.byref, ptr))
+            call("vgposp_critk_buffers" if self.R is None else "vgposp_critx_buffers",
+                 _p(self.ws), self.n, self.P, self.kmax, *map(ctypes.byref, ptr))
 
         def view(p, count):
             off = p.value - self.ws.data_ptr()
@@ -222,14 +311,14 @@ class CriterionPlacement:
         rows = self.m + self.rounds
         st = {"nom": view(ptr[0], self.N), "s": view(ptr[1], self.N),
               "delta": view(ptr[2], self.N), "W": view(ptr[3], rows * self.N).view(rows, self.N)}
-        if self.R is not None:
+        if cross:
             st["U"] = view(ptr[4], rows * self.P).view(rows, self.P)
         return st
 
     def variance_removed(self):
         """[P] device tensor: sum_r U_r[v]^2, what the sensors so far (``placed`` included) took
-        off the prior variance of target v.  Needs ``cross_cov``."""
-        if self.R is None:
+        off the prior variance of target v.  Needs ``cross_cov`` or ``cross_kernel``."""
+        if self.R is None and self.gen is None:
             raise ValueError("variance_removed() needs cross_cov")
         U = self.state()["U"]
         return (U * U).sum(dim=0)
@@ -245,28 +334,32 @@ class CriterionPlacement:
 
 
 def _place(cov_vv, k, criterion, candidates, placed, targets, cross_cov=None,
-           target_weights=None):
+           target_weights=None, cross_kernel=None):
     if k < 1:
         N = int(np.shape(cov_vv)[0])
         normalize_constraints(N, max(int(k), 0), candidates, placed)
         normalize_targets(N, targets)
-        check_cross_arguments(criterion, targets, cross_cov, target_weights)
+        check_cross_arguments(criterion, targets, cross_cov, target_weights, cross_kernel)
         return []
     g = CriterionPlacement(cov_vv, k, criterion, candidates=candidates, placed=placed,
-                           targets=targets, cross_cov=cross_cov, target_weights=target_weights)
+                           targets=targets, cross_cov=cross_cov, target_weights=target_weights,
+                           cross_kernel=cross_kernel)
     return g.run(k).result()[0]
 
 
 def placement_variance_reduction(cov_vv, k, candidates=None, placed=None, targets=None,
-                                 cross_cov=None, target_weights=None):
+                                 cross_cov=None, target_weights=None, cross_kernel=None):
     """k sensors by greedy variance reduction: each pick minimises the total posterior variance of
     ``targets`` (default: every location).  Returns a list of ``np.int64`` like
     ``placement_algorithm_2``; ``candidates`` / ``placed`` as there.  A singular PSD ``cov_vv``
     needs no retry: nothing is factored.
 
     ``cross_cov`` [P, N] instead of ``targets``: the posterior variance counts at P targets outside
-    V whose covariance with the N locations it holds, weighted by ``target_weights`` [P] >= 0."""
-    return _place(cov_vv, k, "variance", candidates, placed, targets, cross_cov, target_weights)
+    V whose covariance with the N locations it holds, weighted by ``target_weights`` [P] >= 0.
+    ``cross_kernel`` (a ``CrossKernel``) instead of ``cross_cov``: the same rule with that
+    covariance generated from the points in every round and never stored."""
+    return _place(cov_vv, k, "variance", candidates, placed, targets, cross_cov, target_weights,
+                  cross_kernel)
 
 
 def placement_entropy(cov_vv, k, candidates=None, placed=None):
