@@ -752,6 +752,67 @@ int vgposp_critk_buffers(void* ws, int64_t n, int64_t P, int kmax, double** nom,
                          double** delta, double** W, double** U);
 
 /* ---------------------------------------------------------------------------------------------
+ * The rules on a covariance that is never stored: Sigma = diag(a) K(X, X) diag(a) + a diagonal,
+ * generated from the points.  X [n][d] row-major fp64, 1 <= d <= 8; kind, amp, ls (device [1]) as
+ * above; site_scale a [n] (NULL: ones).  Sigma_ij = a_i a_j k(X_i, X_j) for i != j; Sigma_ii =
+ * diag[i] when diag [n] is given (noise, jitter), else a_i^2 amp^2.  The device holds n (d + 2)
+ * doubles instead of n^2.  Limit: n <= 2^21.
+ *
+ *   vgposp_kernel_symv       y = Sigma x.  Every off-diagonal entry whose row and column lie in
+ *                            different 512-tiles is evaluated once and serves y_i and y_j (the
+ *                            diagonal tiles are evaluated as full squares: n 512 entries more).  A
+ *                            workgroup owns a block of G x G tiles on or above the diagonal
+ *                            (G = 1 .. 8 by n, 8 from n = 229,377 on); one partial per (row
+ *                            group, column) and per (column group, row) goes to ws, added in
+ *                            ascending group order.  vgposp_kernel_symv_workspace_bytes(n) (0 when
+ *                            n <= 0) is at most 16 n max(ceil(n / 4096), min(ceil(n / 512), 64))
+ *                            bytes plus alignment: 0.27 GB at n = 262,144.  No float atomics, two
+ *                            launches are bit-identical, no host synchronisation.  n == 0 returns
+ *                            0 without device work.
+ *   vgposp_kernel_symv_sq    y_j = sum_i x_i Sigma_ij^2.
+ *   vgposp_critg_workspace_bytes / _init / _step / _buffers
+ *                            vgposp_crit_* with (Sigma, n, lda, diag) replaced by (kind, X, n, d,
+ *                            amp, ls, site_scale, diag): the same launch sequence, the column
+ *                            Sigma_{:,a} of a round and the pass generated by one device function.
+ *                            Under the entropy rule nothing but that column is ever evaluated.
+ *   vgposp_critgk_workspace_bytes / _init / _step / _buffers
+ *                            vgposp_critk_* with (Sigma, n, lda, diag) replaced by (n, diag): the
+ *                            off-diagonal entries of Sigma come from the kind, X, d, amp, ls and
+ *                            site_scale that generate R, so nothing of size n^2 or P n is held.
+ * Argument errors return -(position) before any device work. */
+size_t vgposp_kernel_symv_workspace_bytes(int64_t n);
+int vgposp_kernel_symv(int kind, const double* X, int64_t n, int d, const double* amp,
+                       const double* ls, const double* site_scale, const double* diag,
+                       const double* x, double* y, void* ws, size_t ws_bytes, void* stream);
+int vgposp_kernel_symv_sq(int kind, const double* X, int64_t n, int d, const double* amp,
+                          const double* ls, const double* site_scale, const double* diag,
+                          const double* x, double* y, void* ws, size_t ws_bytes, void* stream);
+size_t vgposp_critg_workspace_bytes(int64_t n, int kmax);
+int vgposp_critg_init(int kind, const double* X, int64_t n, int d, const double* amp,
+                      const double* ls, const double* site_scale, const double* diag, int kmax,
+                      int criterion, double threshold, const unsigned char* targets,
+                      const unsigned char* allowed, void* ws, size_t ws_bytes, void* stream);
+int vgposp_critg_step(int kind, const double* X, int64_t n, int d, const double* amp,
+                      const double* ls, const double* site_scale, const double* diag, int kmax,
+                      int round, const int64_t* forced, int64_t j, int64_t* selected,
+                      double* sel_delta, void* ws, size_t ws_bytes, void* stream);
+int vgposp_critg_buffers(void* ws, int64_t n, int kmax, double** nom, double** score,
+                         double** delta, double** W);
+size_t vgposp_critgk_workspace_bytes(int64_t n, int64_t P, int kmax);
+int vgposp_critgk_init(int64_t n, const double* diag, int kind, const double* Xt, int64_t P,
+                       const double* X, int d, const double* amp, const double* ls,
+                       const double* target_scale, const double* site_scale,
+                       const double* weights, int kmax, double threshold,
+                       const unsigned char* allowed, void* ws, size_t ws_bytes, void* stream);
+int vgposp_critgk_step(int64_t n, const double* diag, int kind, const double* Xt, int64_t P,
+                       const double* X, int d, const double* amp, const double* ls,
+                       const double* target_scale, const double* site_scale, int kmax, int round,
+                       const int64_t* forced, int64_t j, int64_t* selected, double* sel_delta,
+                       void* ws, size_t ws_bytes, void* stream);
+int vgposp_critgk_buffers(void* ws, int64_t n, int64_t P, int kmax, double** nom, double** score,
+                          double** delta, double** W, double** U);
+
+/* ---------------------------------------------------------------------------------------------
  * Exact algorithm 3 at grid sizes where cov_vv cannot be dense (config C4, 128^3): the beta-decay
  * tapered covariance (main_architecture_2_sampledistribution.py:355-421) is a sparse SPD stencil
  * matrix, and snippets_a3.sparse_placement_algorithm_3 (snippets_a3.py:43-364) with tf_nominator /

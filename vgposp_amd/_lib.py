@@ -57,6 +57,9 @@ _EXACT = [_i32, _c_void_p, _i64, _i64, _i64, _f64, _f64, _f64, _f64, _f64, _c_vo
 # a cross-covariance generated from the points: kind, Xt, P, X, d, amp, ls, target_scale, site_scale
 _KGEN = [_i32, _c_void_p, _i64, _c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p]
 
+# a covariance generated from the points: kind, X, n, d, amp, ls, site_scale, diag
+_SGEN = [_i32, _c_void_p, _i64, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p]
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     "vgposp_abi_version": (_i32, []),
@@ -284,6 +287,23 @@ SIGNATURES = {
                              _c_void_p]),
     "vgposp_critk_buffers": (_i32, [_c_void_p, _i64, _i64, _i32]
                              + [ctypes.POINTER(_c_void_p)] * 5),
+    "vgposp_kernel_symv_workspace_bytes": (_size, [_i64]),
+    "vgposp_kernel_symv": (_i32, _SGEN + [_c_void_p, _c_void_p, _c_void_p, _size, _c_void_p]),
+    "vgposp_kernel_symv_sq": (_i32, _SGEN + [_c_void_p, _c_void_p, _c_void_p, _size, _c_void_p]),
+    "vgposp_critg_workspace_bytes": (_size, [_i64, _i32]),
+    "vgposp_critg_init": (_i32, _SGEN + [_i32, _i32, _f64, _c_void_p, _c_void_p, _c_void_p, _size,
+                                         _c_void_p]),
+    "vgposp_critg_step": (_i32, _SGEN + [_i32, _i32, _c_void_p, _i64, _c_void_p, _c_void_p,
+                                         _c_void_p, _size, _c_void_p]),
+    "vgposp_critg_buffers": (_i32, [_c_void_p, _i64, _i32] + [ctypes.POINTER(_c_void_p)] * 4),
+    "vgposp_critgk_workspace_bytes": (_size, [_i64, _i64, _i32]),
+    "vgposp_critgk_init": (_i32, [_i64, _c_void_p] + _KGEN
+                           + [_c_void_p, _i32, _f64, _c_void_p, _c_void_p, _size, _c_void_p]),
+    "vgposp_critgk_step": (_i32, [_i64, _c_void_p] + _KGEN
+                           + [_i32, _i32, _c_void_p, _i64, _c_void_p, _c_void_p, _c_void_p, _size,
+                              _c_void_p]),
+    "vgposp_critgk_buffers": (_i32, [_c_void_p, _i64, _i64, _i32]
+                              + [ctypes.POINTER(_c_void_p)] * 5),
 }
 
 _lock = threading.Lock()
@@ -354,6 +374,8 @@ KERNEL_SOURCES = {
     "criteria_gemv_t_sq": ["criteria.hip", "common.h", "Makefile"],
     "criteria_kgemv_t": ["criteria.hip", "psd.h", "common.h", "Makefile"],
     "criteria_kgemv_t_sq": ["criteria.hip", "psd.h", "common.h", "Makefile"],
+    "criteria_ksymv": ["criteria.hip", "psd.h", "common.h", "Makefile"],
+    "criteria_ksymv_sq": ["criteria.hip", "psd.h", "common.h", "Makefile"],
     "kernel_matrix": ["kernel_matrix.hip", "psd.h", "common.h", "Makefile"],
     "exact": ["exact_greedy.hip", "psd.h", "common.h", "Makefile"],
 }

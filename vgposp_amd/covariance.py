@@ -79,6 +79,35 @@ def kernel_gemv_t(kind, Xt, X, amp, ls, x, squared=False, target_scale=None, sit
     return out
 
 
+def kernel_symv(kind, X, amp, ls, x, squared=False, site_scale=None, diag=None, out=None):
+    """out = Sigma x for Sigma = diag(site_scale) K(X, X) diag(site_scale) off the diagonal and
+    ``diag`` on it (default site_scale^2 amp^2), Sigma never formed (``squared``: of the squared
+    entries).  X [n, d], x [n].  Every off-diagonal entry is evaluated once for both of the
+    outputs it belongs to, unlike ``kernel_gemv_t(kind, X, X, ...)``."""
+    X = linalg.as_device(X)
+    X = (X[:, None] if X.dim() == 1 else X).contiguous()
+    x = linalg.as_device(x).reshape(-1).contiguous()
+    n = X.shape[0]
+    if x.numel() != n:
+        raise ValueError("kernel_symv: shapes do not match")
+
+    def vec(a):
+        if a is None:
+            return None
+        a = linalg.as_device(a).reshape(-1).contiguous()
+        if a.numel() != n:
+            raise ValueError("kernel_symv: shapes do not match")
+        return a
+    a_s, dg = vec(site_scale), vec(diag)
+    if out is None:
+        out = torch.zeros(n, dtype=F64, device=X.device)
+    ws = linalg.workspace(query("vgposp_kernel_symv_workspace_bytes", n))
+    a, l = linalg._vec(amp), linalg._vec(ls)   # held until the launch, as in kernel_matvec
+    call("vgposp_kernel_symv_sq" if squared else "vgposp_kernel_symv", kind_id(kind), _p(X), n,
+         X.shape[1], _p(a), _p(l), _p(a_s), _p(dg), _p(x), _p(out), _p(ws), ws.numel(), _stream())
+    return out
+
+
 def center_rows_(T, scale=1.0):
     """In place: T[i] <- (T[i] - mean(T[i])) * scale (device [N, S])."""
     if T.dim() != 2 or T.stride(1) != 1:
@@ -142,6 +171,6 @@ def cov_vv_from_vgp(vgp, locations, tp_samples, tr_mean=0.0, tr_stdev=1.0):
     return empirical_cov(vgp_tracer_samples(vgp, locations, tp_samples), tr_mean, tr_stdev)
 
 
-__all__ = ["kernel_matvec", "kernel_gemv_t", "center_rows_", "empirical_cov", "index_taper_",
+__all__ = ["kernel_matvec", "kernel_gemv_t", "kernel_symv", "center_rows_", "empirical_cov", "index_taper_",
            "vgp_tracer_samples",
            "cov_vv_from_vgp"]

@@ -25,7 +25,13 @@
 // The heavy step is vgposp_symv_upper: y = Sigma x from the upper triangle, every element loaded
 // once and used for y_i and for y_j.  No float atomics anywhere: partial sums go to the workspace
 // and are reduced in a fixed order, so two runs are bit-identical; nothing synchronises the host.
+//
+// Sigma need not be stored: for Sigma = diag(a) K(X, X) diag(a) + a diagonal vector the same
+// rounds run with every entry generated from the points (SGen, ksymv_kernel, the critg / critgk
+// entries); the host sequences of the rounds are written once, against where Sigma comes from.
+#include <algorithm>
 #include <cfloat>
+#include <type_traits>
 
 #include "common.h"
 #include "psd.h"
@@ -196,7 +202,9 @@ struct CritWS {
   size_t bytes;
 };
 
-static CritWS crit_layout(void* base, int64_t n, int kmax) {
+// pass_bytes: the partials of the pass over Sigma (symv_layout for a stored Sigma, ksymv_layout for
+// a generated one, 0 where the rounds never pass over it).
+static CritWS crit_layout(void* base, int64_t n, int kmax, size_t pass_bytes) {
   CritWS w{};
   const int64_t nb = ceil_div(n, CR_B), nch = ceil_div(n, CR_CH);
   char* p = static_cast<char*>(base);
@@ -220,9 +228,13 @@ static CritWS crit_layout(void* base, int64_t n, int kmax) {
   w.fval = (double*)take(nch * 8);
   w.fidx = (long long*)take(nch * 8);
   w.selmask = (unsigned char*)take(n);
-  w.symv = take(symv_layout(nullptr, n).bytes);
+  w.symv = take(pass_bytes);
   w.bytes = off;
   return w;
+}
+
+static CritWS crit_layout(void* base, int64_t n, int kmax) {
+  return crit_layout(base, n, kmax, symv_layout(nullptr, n).bytes);
 }
 
 // Block-wide (value, index) arg-max for blockDim == 1024; the result is valid in all threads.
@@ -490,10 +502,11 @@ struct CritXWS {
 };
 
 // part_bytes: the partials of the pass (gemv_t_bytes for a stored R, kgemv_t_bytes for a generated
-// one).
-static CritXWS critx_layout(void* base, int64_t n, int64_t P, int kmax, size_t part_bytes) {
+// one).  sigma_bytes: crit_layout's pass_bytes; a stored Sigma keeps the area of its in-V rule.
+static CritXWS critx_layout(void* base, int64_t n, int64_t P, int kmax, size_t part_bytes,
+                            size_t sigma_bytes) {
   CritXWS w{};
-  w.c = crit_layout(base, n, kmax);
+  w.c = crit_layout(base, n, kmax, sigma_bytes);
   char* p = static_cast<char*>(base);
   size_t off = w.c.bytes;
   auto take = [&](size_t bytes) {
@@ -508,6 +521,10 @@ static CritXWS critx_layout(void* base, int64_t n, int64_t P, int kmax, size_t p
   w.gemv = take(part_bytes);
   w.bytes = off;
   return w;
+}
+
+static CritXWS critx_layout(void* base, int64_t n, int64_t P, int kmax, size_t part_bytes) {
+  return critx_layout(base, n, P, kmax, part_bytes, symv_layout(nullptr, n).bytes);
 }
 
 // The workspace as crit_dots / crit_fold see the target side: rows U, vector omega.u, length P.
@@ -686,6 +703,493 @@ static void critk_urow_launch(const KGen& g, int64_t P, const int64_t* selected,
   }
 }
 
+// ---- Sigma generated from the points: Sigma = diag(a) K(X, X) diag(a) off the diagonal ----
+// X [n][d] row-major, kind / amp / ls as for KGen, a [n] the sites' amplitude field (NULL: ones).
+// The diagonal is a vector: diag [n] when given (noise, jitter), else a_i^2 amp^2.  Every
+// off-diagonal entry is a_i a_j kentry<>(X_i, X_j), in the pass, its squared form and the column a
+// round reads alike; Sigma is never stored.
+struct SGen {
+  int kind, d;
+  const double *X, *amp, *ls, *a, *diag;
+};
+
+__device__ __forceinline__ double sgen_diag(const SGen& g, int64_t i) {
+  if (g.diag) return g.diag[i];
+  const double a = g.a ? g.a[i] : 1.0, amp = g.amp[0];
+  return (a * a) * (amp * amp);
+}
+
+template <class F>
+static void with_kind(int kind, F&& f) {
+  switch (kind) {
+    case VGPOSP_KERNEL_EQ: f(std::integral_constant<int, VGPOSP_KERNEL_EQ>{}); break;
+    case VGPOSP_KERNEL_MATERN12: f(std::integral_constant<int, VGPOSP_KERNEL_MATERN12>{}); break;
+    case VGPOSP_KERNEL_MATERN32: f(std::integral_constant<int, VGPOSP_KERNEL_MATERN32>{}); break;
+    default: f(std::integral_constant<int, VGPOSP_KERNEL_MATERN52>{}); break;
+  }
+}
+
+// A workgroup owns a block of G x G 512-tiles on or above the diagonal, so the partials are one per
+// (row group, column) and one per (column group, row): 16 n ng bytes for ng groups.  G grows with
+// n so that there are at most KS_NG groups up to n = 512 KS_NG KS_GMAX (262,144) and enough
+// workgroups below it; beyond, G = KS_GMAX.  The allocation is the larger of the two regimes'
+// bounds, which makes it monotone in n where ng itself is not.
+constexpr int KS_CPL = 8;             // columns per lane: one wave spans a 512-column tile
+constexpr int KS_RW = SY_T / (SY_TH / 64);  // rows of a tile per wave
+constexpr int KS_RC = 8;              // row partials per transpose-reduce
+constexpr int KS_GMAX = 8, KS_NG = 64;
+static_assert(64 * KS_CPL == SY_T && KS_RW % KS_RC == 0, "a wave per 512 columns, whole chunks");
+// Waves per SIMD the registers are budgeted for: a lane holds KS_CPL columns' coordinates (16 D
+// VGPRs; 128 for the run-time dimension), 48 for xa, cs and the row partials, and the entries in
+// flight.  The bound is the largest at which nothing spills.
+constexpr int KS_WAVES(int D) { return D == 0 ? 1 : D == 3 ? 2 : 3; }
+
+struct KSymvWS {
+  double *cpart, *rpart;  // [ng][n] each: column sums per row group, row sums per column group
+  int G;
+  int64_t ng;
+  size_t bytes;
+};
+
+static KSymvWS ksymv_layout(void* base, int64_t n) {
+  KSymvWS w{};
+  const int64_t nt = ceil_div(n, SY_T);
+  w.G = (int)std::min<int64_t>(KS_GMAX, std::max<int64_t>(1, ceil_div(nt, KS_NG)));
+  w.ng = ceil_div(nt, w.G);
+  const int64_t cap = std::max(std::min<int64_t>(nt, KS_NG), ceil_div(nt, KS_GMAX));
+  const size_t slab = cr_align((size_t)cap * n * 8);
+  char* p = static_cast<char*>(base);
+  w.cpart = (double*)p;
+  w.rpart = (double*)(p ? p + slab : nullptr);
+  w.bytes = 2 * slab;
+  return w;
+}
+
+// Lanes whose bit O is clear: a summed over the lane pair (l, l ^ O); lanes whose bit O is set: b
+// summed likewise.  One v_permlane{32,16}_swap per dword and one add: the halving exchange of a
+// transpose-reduce (O = 32: the wave's halves, O = 16: the rows of 16 lanes).
+template <int O>
+__device__ __forceinline__ double fold_pair(double a, double b) {
+  static_assert(O == 32 || O == 16, "the exchanges with a swap instruction");
+  const unsigned long long ua = __builtin_bit_cast(unsigned long long, a);
+  const unsigned long long ub = __builtin_bit_cast(unsigned long long, b);
+  unsigned p0, p1, q0, q1;
+  if constexpr (O == 32) {
+    const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)ua, (unsigned)ub, false, false);
+    const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)(ua >> 32), (unsigned)(ub >> 32),
+                                                     false, false);
+    p0 = lo[0], q0 = lo[1], p1 = hi[0], q1 = hi[1];
+  } else {
+    const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)ua, (unsigned)ub, false, false);
+    const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)(ua >> 32), (unsigned)(ub >> 32),
+                                                     false, false);
+    p0 = lo[0], q0 = lo[1], p1 = hi[0], q1 = hi[1];
+  }
+  const double p = __builtin_bit_cast(double, (unsigned long long)p0 | ((unsigned long long)p1 << 32));
+  const double q = __builtin_bit_cast(double, (unsigned long long)q0 | ((unsigned long long)q1 << 32));
+  return p + q;
+}
+
+// The wave's share (KS_RW rows) of one 512 x 512 tile.  A lane owns the columns c0 + lane + 64 q,
+// q < KS_CPL: coordinates xc, x_c a_c^p in xa, column sums cs, all in registers.  The tile's rows
+// are staged in LDS as rows of DW doubles (coordinates, then x_r a_r^p last) and read back as
+// wave-uniform broadcasts.  Off the diagonal an entry serves both directions: the lane's KS_CPL
+// products of a row are one partial, KS_RC rows' partials are reduced over the wave together (two
+// halving exchanges, then four butterfly steps on the two values left, each of which ends with one
+// row's sum per 16 lanes) and added to racc, the row sums this wave owns.  DT,
+// the diagonal tile: the full square in the column direction only, the entry r == c left out (the
+// reduction adds diag); one row at a time, it is 1 / nt of the work.
+template <int KIND, int D, bool SQ, bool DT>
+__device__ __forceinline__ void ksymv_tile(const double* __restrict__ rows, int nrow, int64_t r0,
+                                           int64_t c0, const double (&xc)[KS_CPL][D > 0 ? D : 8],
+                                           const double (&xa)[KS_CPL], double (&cs)[KS_CPL],
+                                           double* __restrict__ racc, int dd, double tla,
+                                           double inv_l, double inv_l2) {
+  constexpr int DW = (D > 0 ? D : 8) + 1;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int i1 = min(nrow, (wv + 1) * KS_RW);
+  if constexpr (DT) {
+#pragma unroll 1
+    for (int i = wv * KS_RW; i < i1; ++i) {
+      const double* t = rows + i * DW;
+      const double xw = t[DW - 1];
+      const int64_t off = r0 + i - c0 - lane;
+#pragma unroll
+      for (int q = 0; q < KS_CPL; ++q) {
+        double k = kentry<KIND, D>(t, xc[q], dd, tla, inv_l, inv_l2);
+        if (SQ) k *= k;
+        if (off == 64 * q) k = 0.0;
+        cs[q] = fma(k, xw, cs[q]);
+      }
+    }
+    return;
+  }
+  const auto add = [](double a, double b) { return a + b; };
+  // one row's entries at a time: a rolled loop over row pairs keeps the basic block, and with it
+  // the registers the scheduler spends on entries in flight, small
+  const auto partial = [&](int i) {
+    const double* t = rows + i * DW;
+    const double xw = t[DW - 1];
+    double rp = 0.0;
+#pragma unroll
+    for (int q = 0; q < KS_CPL; ++q) {
+      double k = kentry<KIND, D>(t, xc[q], dd, tla, inv_l, inv_l2);
+      if (SQ) k *= k;
+      cs[q] = fma(k, xw, cs[q]);
+      rp = fma(k, xa[q], rp);
+    }
+    return rp;
+  };
+  for (int i0 = wv * KS_RW; i0 < i1; i0 += KS_RC) {  // (rows past nrow are staged as zeros)
+    double w0 = 0.0, w1 = 0.0, w2 = 0.0, w3 = 0.0;
+#pragma unroll 1
+    for (int m = 0; m < KS_RC; m += 2) {
+      const double ra = partial(i0 + m), rb = partial(i0 + m + 1);
+      w0 = w1, w1 = w2, w2 = w3;
+      w3 = fold_pair<32>(ra, rb);  // lower half: row m, upper half: row m + 1
+    }
+    double z0 = fold_pair<16>(w0, w1), z1 = fold_pair<16>(w2, w3);
+    z0 = wave_step<8>(z0, add);
+    z1 = wave_step<8>(z1, add);
+    z0 = wave_step<4>(z0, add);
+    z1 = wave_step<4>(z1, add);
+    z0 = wave_step<2>(z0, add);
+    z1 = wave_step<2>(z1, add);
+    z0 = wave_step<1>(z0, add);
+    z1 = wave_step<1>(z1, add);
+    if ((lane & 15) == 0) {  // lanes 0, 16, 32, 48 hold the rows 0, 2, 1, 3 of z0, 4 + those of z1
+      const int q = lane >> 4;
+      double* o = racc + i0 + 2 * (q & 1) + (q >> 1);
+      o[0] += z0;
+      o[4] += z1;
+    }
+  }
+}
+static_assert(KS_RC == 8, "ksymv_tile folds eight row partials");
+
+// The block (gi, gj), gj >= gi, of G x G tiles.  Column tiles outermost: the lane's column sums
+// live in registers over the block's row tiles, the four waves (same columns, a quarter of every
+// row tile each) are added in a fixed order through LDS, and cpart[gi][c] is written once.  The
+// row sums of the G row tiles stay in LDS (racc, dynamic: G x 512 doubles) over the column tiles;
+// rpart[gj][r] is written at the end.  In a diagonal block only the tiles tj >= ti exist.
+template <int KIND, int D, bool SQ>
+__global__ __launch_bounds__(SY_TH, KS_WAVES(D)) void ksymv_kernel(SGen g, int64_t n,
+                                                      const double* __restrict__ x, KSymvWS w,
+                                                      const double* __restrict__ gate) {
+  constexpr int DX = D > 0 ? D : 8, DW = DX + 1;
+  constexpr int NST = DW > SY_TH / 64 ? SY_T * DW : SY_T * (SY_TH / 64);
+  __shared__ double stage[NST];  // a row tile; between column tiles the waves' column sums
+  extern __shared__ double racc[];
+  const int64_t gi = blockIdx.y, gj = blockIdx.x;
+  if (gj < gi) return;               // below the diagonal
+  if (gate && *gate != 0.0) return;  // workgroup-uniform: no barrier is left waiting
+  const int dd = D > 0 ? D : g.d, G = w.G;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t nt = (n + SY_T - 1) / SY_T;
+  const double tla = 2.0 * log(g.amp[0]), inv_l = 1.0 / g.ls[0], inv_l2 = inv_l * inv_l;
+  for (int i = threadIdx.x; i < G * SY_T; i += SY_TH) racc[i] = 0.0;
+  for (int cj = 0; cj < G; ++cj) {
+    const int64_t tj = gj * G + cj;
+    if (tj >= nt) break;
+    const int64_t c0 = tj * SY_T;
+    double xc[KS_CPL][DX], xa[KS_CPL], cs[KS_CPL];
+#pragma unroll
+    for (int q = 0; q < KS_CPL; ++q) {
+      const int64_t c = c0 + lane + 64 * q;
+      const bool in = c < n;
+#pragma unroll
+      for (int k = 0; k < DX; ++k) xc[q][k] = (k < dd && in) ? g.X[c * dd + k] : 0.0;
+      const double a = g.a && in ? g.a[c] : 1.0;
+      xa[q] = in ? x[c] * (SQ ? a * a : a) : 0.0;
+      cs[q] = 0.0;
+    }
+    const int nri = gi == gj ? cj + 1 : G;
+    for (int ri = 0; ri < nri; ++ri) {
+      const int64_t ti = gi * G + ri;
+      if (ti >= nt) break;
+      const int64_t r0 = ti * SY_T;
+      const int nrow = (int)min((int64_t)SY_T, n - r0);
+      __syncthreads();  // the readers of the previous tile (or of the column sums) are done
+      for (int e = threadIdx.x; e < SY_T * DW; e += SY_TH) {
+        const int i = e / DW, k = e - i * DW;
+        double v = 0.0;
+        if (i < nrow) {
+          if (k < dd) {
+            v = g.X[(r0 + i) * dd + k];
+          } else if (k == DW - 1) {
+            const double a = g.a ? g.a[r0 + i] : 1.0;
+            v = x[r0 + i] * (SQ ? a * a : a);
+          }
+        }
+        stage[e] = v;
+      }
+      __syncthreads();
+      if (ti == tj)
+        ksymv_tile<KIND, D, SQ, true>(stage, nrow, r0, c0, xc, xa, cs, racc + ri * SY_T, dd, tla,
+                                      inv_l, inv_l2);
+      else
+        ksymv_tile<KIND, D, SQ, false>(stage, nrow, r0, c0, xc, xa, cs, racc + ri * SY_T, dd, tla,
+                                       inv_l, inv_l2);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < KS_CPL; ++q) stage[wv * SY_T + lane + 64 * q] = cs[q];
+    __syncthreads();
+    for (int i = threadIdx.x; i < SY_T; i += SY_TH)
+      if (c0 + i < n)
+        w.cpart[gi * n + c0 + i] = (stage[i] + stage[SY_T + i]) +
+                                   (stage[2 * SY_T + i] + stage[3 * SY_T + i]);
+  }
+  __syncthreads();
+  const int64_t rb = gi * G * SY_T;
+  for (int i = threadIdx.x; i < G * SY_T; i += SY_TH)
+    if (rb + i < n) w.rpart[gj * n + rb + i] = racc[i];
+}
+static_assert(SY_TH == 256, "ksymv_kernel adds four waves");
+
+// y_i = a_i^p ((the column sums of the row groups 0 .. gi, ascending) + (the row sums of the
+//       column groups gi .. ng - 1, ascending)) + Sigma_ii^p x_i,   gi the group of i, p = 1 + sq
+__global__ __launch_bounds__(CR_B) void ksymv_reduce_kernel(SGen g, int64_t n,
+                                                            const double* __restrict__ x,
+                                                            KSymvWS w, double* __restrict__ y,
+                                                            int sq,
+                                                            const double* __restrict__ gate) {
+  if (gate && *gate != 0.0) return;
+  const int64_t i = (int64_t)blockIdx.x * CR_B + threadIdx.x;
+  if (i >= n) return;
+  const int64_t gi = i / ((int64_t)w.G * SY_T);
+  double cs = 0.0, rs = 0.0;
+  for (int64_t b = 0; b <= gi; ++b) cs += w.cpart[b * n + i];
+  for (int64_t b = gi; b < w.ng; ++b) rs += w.rpart[b * n + i];
+  const double a = g.a ? g.a[i] : 1.0, dg = sgen_diag(g, i);
+  const double s = (cs + rs) * (sq ? a * a : a);
+  y[i] = fma(sq ? dg * dg : dg, x[i], s);
+}
+
+// y = Sigma x (SQ: of the squared entries) for the generated Sigma.  gate as in gemv_t_launch.
+template <bool SQ>
+static void ksymv_launch(const SGen& g, int64_t n, const double* x, double* y, const KSymvWS& w,
+                         const double* gate, hipStream_t s) {
+  {
+    const double tri = 0.5 * (double)n * (double)n;
+    ProfScope ps(SQ ? "criteria_ksymv_sq" : "criteria_ksymv", s, (3.0 * g.d + 34.0) * tri,
+                 8.0 * (double)n * (g.d + 2) * (double)w.ng);
+    const dim3 grid((unsigned)w.ng, (unsigned)w.ng);
+    const size_t lds = (size_t)w.G * SY_T * 8;
+    with_kind(g.kind, [&](auto kind) {
+      constexpr int KIND = decltype(kind)::value;
+#define KS_CASE(DD)                                                                             \
+  hipLaunchKernelGGL((ksymv_kernel<KIND, DD, SQ>), grid, dim3(SY_TH), lds, s, g, n, x, w, gate); \
+  break;
+      switch (g.d) {
+        case 1: KS_CASE(1)
+        case 2: KS_CASE(2)
+        case 3: KS_CASE(3)
+        default: KS_CASE(0)
+      }
+#undef KS_CASE
+    });
+  }
+  hipLaunchKernelGGL(ksymv_reduce_kernel, dim3((unsigned)ceil_div(n, CR_B)), dim3(CR_B), 0, s, g, n,
+                     x, w, y, SQ ? 1 : 0, gate);
+}
+
+// crit_init_kernel with nom = the generated diagonal.
+__global__ void critg_init_kernel(SGen g, int64_t n, int criterion, double thr,
+                                  const unsigned char* targets, const unsigned char* allowed,
+                                  CritWS w) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {
+    w.nom[i] = sgen_diag(g, i);
+    w.tvec[i] = (!targets || targets[i]) ? 1.0 : 0.0;
+    w.selmask[i] = (allowed && !allowed[i]) ? 1 : 0;
+    w.delta[i] = 0.0;
+    if (criterion != VGPOSP_CRIT_VARIANCE) w.s[i] = 0.0;
+  }
+  if (i == 0) {
+    w.prm[0] = thr;
+    w.prm[1] = criterion == VGPOSP_CRIT_VARIANCE ? 0.0 : 1.0;
+  }
+}
+
+// crit_row_kernel with Sigma_ay generated: a_a a_y k(X_y, X_a), the entry the pass sums, and the
+// diagonal vector at y = a.
+template <int KIND>
+__global__ __launch_bounds__(CR_B) void critg_row_kernel(SGen g, int64_t n,
+                                                         const int64_t* selected, int round,
+                                                         CritWS w) {
+  const int64_t i = (int64_t)blockIdx.x * CR_B + threadIdx.x;
+  const int64_t a = selected[round];
+  if (i >= n || a < 0) return;
+  double s;
+  if (i == a) {
+    s = sgen_diag(g, a);
+  } else {
+    double xi[8], xa[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      xi[k] = k < g.d ? g.X[i * g.d + k] : 0.0;
+      xa[k] = k < g.d ? g.X[a * g.d + k] : 0.0;
+    }
+    const double tla = 2.0 * log(g.amp[0]), inv_l = 1.0 / g.ls[0], inv_l2 = inv_l * inv_l;
+    s = kentry<KIND, 0>(xi, xa, g.d, tla, inv_l, inv_l2);
+    if (g.a) s *= g.a[i] * g.a[a];
+  }
+  for (int t = 0; t < round; ++t) s -= w.piv[1 + t] * w.W[(int64_t)t * n + i];
+  const double noma = w.piv[0];
+  const double wy = noma >= w.prm[0] && noma > 0.0 ? s / sqrt(noma) : 0.0;
+  w.W[(int64_t)round * n + i] = wy;
+  w.wt[i] = wy * w.tvec[i];
+  w.nom[i] -= wy * wy;
+}
+
+// ---- where Sigma comes from: what the host sequences of the rounds are written against ----
+struct SigmaStored {
+  const double* S;
+  int64_t lda;
+  const double* diag;
+};
+
+static void sigma_init(const SigmaStored& sg, int64_t n, int criterion, double thr,
+                       const unsigned char* targets, const unsigned char* allowed, const CritWS& w,
+                       hipStream_t s) {
+  hipLaunchKernelGGL(crit_init_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, sg.S, n,
+                     sg.lda, sg.diag, criterion, thr, targets, allowed, w);
+}
+static void sigma_init(const SGen& sg, int64_t n, int criterion, double thr,
+                       const unsigned char* targets, const unsigned char* allowed, const CritWS& w,
+                       hipStream_t s) {
+  hipLaunchKernelGGL(critg_init_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, sg, n,
+                     criterion, thr, targets, allowed, w);
+}
+
+static void sigma_row(const SigmaStored& sg, int64_t n, const int64_t* selected, int round,
+                      const CritWS& w, hipStream_t s) {
+  hipLaunchKernelGGL(crit_row_kernel, dim3((unsigned)ceil_div(n, CR_B)), dim3(CR_B), 0, s, sg.S, n,
+                     sg.lda, sg.diag, selected, round, w);
+}
+static void sigma_row(const SGen& sg, int64_t n, const int64_t* selected, int round,
+                      const CritWS& w, hipStream_t s) {
+  with_kind(sg.kind, [&](auto kind) {
+    hipLaunchKernelGGL(critg_row_kernel<decltype(kind)::value>, dim3((unsigned)ceil_div(n, CR_B)),
+                       dim3(CR_B), 0, s, sg, n, selected, round, w);
+  });
+}
+
+// The pass over Sigma on the partials area of the workspace.
+template <bool SQ>
+static void sigma_pass(const SigmaStored& sg, int64_t n, const double* x, double* y, void* area,
+                       const double* gate, hipStream_t s) {
+  symv_launch<SQ>(sg.S, n, sg.lda, sg.diag, x, y, symv_layout(area, n), gate, s);
+}
+template <bool SQ>
+static void sigma_pass(const SGen& sg, int64_t n, const double* x, double* y, void* area,
+                       const double* gate, hipStream_t s) {
+  ksymv_launch<SQ>(sg, n, x, y, ksymv_layout(area, n), gate, s);
+}
+
+// The in-V rule, after the entry has checked its arguments and laid out w.
+template <class Sigma>
+static int crit_init_run(const Sigma& sg, int64_t n, int criterion, double threshold,
+                         const unsigned char* targets, const unsigned char* allowed,
+                         const CritWS& w, hipStream_t s) {
+  sigma_init(sg, n, criterion, threshold, targets, allowed, w, s);
+  VG_LAUNCH_CHECK();
+  if (criterion == VGPOSP_CRIT_VARIANCE) {  // s_y = sum_v t_v Sigma_vy^2
+    sigma_pass<true>(sg, n, w.tvec, w.s, w.symv, nullptr, s);
+    VG_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+template <class Sigma>
+static int crit_step_run(const Sigma& sg, int64_t n, int round, const int64_t* forced, int64_t j,
+                         int64_t* selected, double* sel_delta, const CritWS& w, hipStream_t s) {
+  const unsigned nb = (unsigned)ceil_div(n, CR_B);
+  {
+    ProfScope ps("criteria_select", s, 0.0, 8.0 * 3.0 * n);
+    hipLaunchKernelGGL(crit_score_kernel, dim3((unsigned)ceil_div(n, CR_CH)), dim3(CR_CH), 0, s, n,
+                       w);
+    hipLaunchKernelGGL(crit_select_kernel, dim3(1), dim3(CR_CH), 0, s, n, round, forced, j,
+                       selected, sel_delta, w);
+    VG_LAUNCH_CHECK();
+  }
+  {
+    ProfScope ps("criteria_row", s, 0.0, 8.0 * (double)n * (5 + round));
+    sigma_row(sg, n, selected, round, w, s);
+    VG_LAUNCH_CHECK();
+  }
+  // the variance rule's part: every kernel below returns at once under the entropy rule (the
+  // criterion lives in the workspace, so the launch sequence does not depend on it)
+  const double* gate = w.prm + 1;
+  hipLaunchKernelGGL(crit_dots_kernel, dim3(nb, (unsigned)round + 1), dim3(CR_B), 0, s, n,
+                     selected, round, w);
+  hipLaunchKernelGGL(crit_fold_kernel, dim3((unsigned)round + 1), dim3(CR_B), 0, s, (int64_t)nb,
+                     selected, round, w);
+  VG_LAUNCH_CHECK();
+  sigma_pass<false>(sg, n, w.wt, w.g, w.symv, gate, s);
+  VG_LAUNCH_CHECK();
+  {
+    ProfScope ps("criteria_update", s, 0.0, 8.0 * (double)n * (4 + round));
+    hipLaunchKernelGGL(crit_update_kernel, dim3(nb), dim3(CR_B), 0, s, n, selected, round, w);
+    VG_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+// The rule on a generated R, after the entry has checked its arguments and laid out w.
+template <class Sigma>
+static int critk_init_run(const Sigma& sg, const KGen& g, int64_t n, int64_t P,
+                          const double* weights, double threshold, const unsigned char* allowed,
+                          const CritXWS& w, hipStream_t s) {
+  sigma_init(sg, n, VGPOSP_CRIT_VARIANCE, threshold, nullptr, allowed, w.c, s);
+  hipLaunchKernelGGL(critx_init_kernel, dim3((unsigned)ceil_div(P, 256)), dim3(256), 0, s, P,
+                     weights, w);
+  VG_LAUNCH_CHECK();
+  // s_y = sum_v omega_v R_vy^2
+  kgemv_t_launch<true>(g, P, n, w.omega, w.c.s, w.gemv, nullptr, s);
+  VG_LAUNCH_CHECK();
+  return 0;
+}
+
+template <class Sigma>
+static int critk_step_run(const Sigma& sg, const KGen& g, int64_t n, int64_t P, int round,
+                          const int64_t* forced, int64_t j, int64_t* selected, double* sel_delta,
+                          const CritXWS& w, hipStream_t s) {
+  const CritWS tv = critx_target_view(w);
+  const int d = g.d;
+  const unsigned nb = (unsigned)ceil_div(n, CR_B), nbp = (unsigned)ceil_div(P, CR_B);
+  {
+    ProfScope ps("criteria_select", s, 0.0, 8.0 * 3.0 * n);
+    hipLaunchKernelGGL(crit_score_kernel, dim3((unsigned)ceil_div(n, CR_CH)), dim3(CR_CH), 0, s, n,
+                       w.c);
+    hipLaunchKernelGGL(crit_select_kernel, dim3(1), dim3(CR_CH), 0, s, n, round, forced, j,
+                       selected, sel_delta, w.c);
+    VG_LAUNCH_CHECK();
+  }
+  {
+    ProfScope ps("criteria_row", s, 0.0,
+                 8.0 * ((double)n * (5 + round) + (double)P * (4 + d + round)));
+    sigma_row(sg, n, selected, round, w.c, s);
+    critk_urow_launch(g, P, selected, round, w, s);
+    VG_LAUNCH_CHECK();
+  }
+  // dot[t] = U_t . (omega.u) for t <= round (t = round: sum_v omega_v u_v^2), over P
+  hipLaunchKernelGGL(crit_dots_kernel, dim3(nbp, (unsigned)round + 1), dim3(CR_B), 0, s, P,
+                     selected, round, tv);
+  hipLaunchKernelGGL(crit_fold_kernel, dim3((unsigned)round + 1), dim3(CR_B), 0, s, (int64_t)nbp,
+                     selected, round, tv);
+  VG_LAUNCH_CHECK();
+  kgemv_t_launch<false>(g, P, n, w.wu, w.c.g, w.gemv, w.c.prm + 1, s);
+  VG_LAUNCH_CHECK();
+  {
+    ProfScope ps("criteria_update", s, 0.0, 8.0 * (double)n * (4 + round));
+    hipLaunchKernelGGL(crit_update_kernel, dim3(nb), dim3(CR_B), 0, s, n, selected, round, w.c);
+    VG_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
 }  // namespace vgposp
 
 using namespace vgposp;
@@ -747,15 +1251,8 @@ extern "C" int vgposp_crit_init(const double* Sigma, int64_t n, int64_t lda, con
   VG_CHECK_ARG(ws != nullptr, 10);
   const CritWS w = crit_layout(ws, n, kmax);
   VG_CHECK_WS(ws_bytes, w.bytes);
-  hipStream_t s = as_stream(stream);
-  hipLaunchKernelGGL(crit_init_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, Sigma, n,
-                     lda, diag, criterion, threshold, targets, allowed, w);
-  VG_LAUNCH_CHECK();
-  if (criterion == VGPOSP_CRIT_VARIANCE) {  // s_y = sum_v t_v Sigma_vy^2
-    symv_launch<true>(Sigma, n, lda, diag, w.tvec, w.s, symv_layout(w.symv, n), nullptr, s);
-    VG_LAUNCH_CHECK();
-  }
-  return 0;
+  return crit_init_run(SigmaStored{Sigma, lda, diag}, n, criterion, threshold, targets, allowed, w,
+                       as_stream(stream));
 }
 
 extern "C" int vgposp_crit_step(const double* Sigma, int64_t n, int64_t lda, const double* diag,
@@ -773,38 +1270,8 @@ extern "C" int vgposp_crit_step(const double* Sigma, int64_t n, int64_t lda, con
   VG_CHECK_ARG(ws != nullptr, 11);
   const CritWS w = crit_layout(ws, n, kmax);
   VG_CHECK_WS(ws_bytes, w.bytes);
-  hipStream_t s = as_stream(stream);
-  const unsigned nb = (unsigned)ceil_div(n, CR_B);
-  {
-    ProfScope ps("criteria_select", s, 0.0, 8.0 * 3.0 * n);
-    hipLaunchKernelGGL(crit_score_kernel, dim3((unsigned)ceil_div(n, CR_CH)), dim3(CR_CH), 0, s, n,
-                       w);
-    hipLaunchKernelGGL(crit_select_kernel, dim3(1), dim3(CR_CH), 0, s, n, round, forced, j,
-                       selected, sel_delta, w);
-    VG_LAUNCH_CHECK();
-  }
-  {
-    ProfScope ps("criteria_row", s, 0.0, 8.0 * (double)n * (5 + round));
-    hipLaunchKernelGGL(crit_row_kernel, dim3(nb), dim3(CR_B), 0, s, Sigma, n, lda, diag, selected,
-                       round, w);
-    VG_LAUNCH_CHECK();
-  }
-  // the variance rule's part: every kernel below returns at once under the entropy rule (the
-  // criterion lives in the workspace, so the launch sequence does not depend on it)
-  const double* gate = w.prm + 1;
-  hipLaunchKernelGGL(crit_dots_kernel, dim3(nb, (unsigned)round + 1), dim3(CR_B), 0, s, n,
-                     selected, round, w);
-  hipLaunchKernelGGL(crit_fold_kernel, dim3((unsigned)round + 1), dim3(CR_B), 0, s, (int64_t)nb,
-                     selected, round, w);
-  VG_LAUNCH_CHECK();
-  symv_launch<false>(Sigma, n, lda, diag, w.wt, w.g, symv_layout(w.symv, n), gate, s);
-  VG_LAUNCH_CHECK();
-  {
-    ProfScope ps("criteria_update", s, 0.0, 8.0 * (double)n * (4 + round));
-    hipLaunchKernelGGL(crit_update_kernel, dim3(nb), dim3(CR_B), 0, s, n, selected, round, w);
-    VG_LAUNCH_CHECK();
-  }
-  return 0;
+  return crit_step_run(SigmaStored{Sigma, lda, diag}, n, round, forced, j, selected, sel_delta, w,
+                       as_stream(stream));
 }
 
 extern "C" int vgposp_crit_buffers(void* ws, int64_t n, int kmax, double** nom, double** score,
@@ -1048,17 +1515,9 @@ extern "C" int vgposp_critk_init(const double* Sigma, int64_t n, int64_t lda, co
   VG_CHECK_ARG(ws != nullptr, 18);
   const CritXWS w = critx_layout(ws, n, P, kmax, kgemv_t_bytes(P, n));
   VG_CHECK_WS(ws_bytes, w.bytes);
-  hipStream_t s = as_stream(stream);
-  hipLaunchKernelGGL(crit_init_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, Sigma, n,
-                     lda, diag, VGPOSP_CRIT_VARIANCE, threshold, nullptr, allowed, w.c);
-  hipLaunchKernelGGL(critx_init_kernel, dim3((unsigned)ceil_div(P, 256)), dim3(256), 0, s, P,
-                     weights, w);
-  VG_LAUNCH_CHECK();
-  // s_y = sum_v omega_v R_vy^2
   const KGen g{kind, d, Xt, X, amp, ls, target_scale, site_scale};
-  kgemv_t_launch<true>(g, P, n, w.omega, w.c.s, w.gemv, nullptr, s);
-  VG_LAUNCH_CHECK();
-  return 0;
+  return critk_init_run(SigmaStored{Sigma, lda, diag}, g, n, P, weights, threshold, allowed, w,
+                        as_stream(stream));
 }
 
 extern "C" int vgposp_critk_step(const double* Sigma, int64_t n, int64_t lda, const double* diag,
@@ -1085,40 +1544,9 @@ extern "C" int vgposp_critk_step(const double* Sigma, int64_t n, int64_t lda, co
   VG_CHECK_ARG(ws != nullptr, 20);
   const CritXWS w = critx_layout(ws, n, P, kmax, kgemv_t_bytes(P, n));
   VG_CHECK_WS(ws_bytes, w.bytes);
-  const CritWS tv = critx_target_view(w);
   const KGen g{kind, d, Xt, X, amp, ls, target_scale, site_scale};
-  hipStream_t s = as_stream(stream);
-  const unsigned nb = (unsigned)ceil_div(n, CR_B), nbp = (unsigned)ceil_div(P, CR_B);
-  {
-    ProfScope ps("criteria_select", s, 0.0, 8.0 * 3.0 * n);
-    hipLaunchKernelGGL(crit_score_kernel, dim3((unsigned)ceil_div(n, CR_CH)), dim3(CR_CH), 0, s, n,
-                       w.c);
-    hipLaunchKernelGGL(crit_select_kernel, dim3(1), dim3(CR_CH), 0, s, n, round, forced, j,
-                       selected, sel_delta, w.c);
-    VG_LAUNCH_CHECK();
-  }
-  {
-    ProfScope ps("criteria_row", s, 0.0,
-                 8.0 * ((double)n * (5 + round) + (double)P * (4 + d + round)));
-    hipLaunchKernelGGL(crit_row_kernel, dim3(nb), dim3(CR_B), 0, s, Sigma, n, lda, diag, selected,
-                       round, w.c);
-    critk_urow_launch(g, P, selected, round, w, s);
-    VG_LAUNCH_CHECK();
-  }
-  // dot[t] = U_t . (omega.u) for t <= round (t = round: sum_v omega_v u_v^2), over P
-  hipLaunchKernelGGL(crit_dots_kernel, dim3(nbp, (unsigned)round + 1), dim3(CR_B), 0, s, P,
-                     selected, round, tv);
-  hipLaunchKernelGGL(crit_fold_kernel, dim3((unsigned)round + 1), dim3(CR_B), 0, s, (int64_t)nbp,
-                     selected, round, tv);
-  VG_LAUNCH_CHECK();
-  kgemv_t_launch<false>(g, P, n, w.wu, w.c.g, w.gemv, w.c.prm + 1, s);
-  VG_LAUNCH_CHECK();
-  {
-    ProfScope ps("criteria_update", s, 0.0, 8.0 * (double)n * (4 + round));
-    hipLaunchKernelGGL(crit_update_kernel, dim3(nb), dim3(CR_B), 0, s, n, selected, round, w.c);
-    VG_LAUNCH_CHECK();
-  }
-  return 0;
+  return critk_step_run(SigmaStored{Sigma, lda, diag}, g, n, P, round, forced, j, selected,
+                        sel_delta, w, as_stream(stream));
 }
 
 extern "C" int vgposp_critk_buffers(void* ws, int64_t n, int64_t P, int kmax, double** nom,
@@ -1129,6 +1557,207 @@ extern "C" int vgposp_critk_buffers(void* ws, int64_t n, int64_t P, int kmax, do
   VG_CHECK_ARG(P >= 1, 3);
   VG_CHECK_ARG(kmax >= 1, 4);
   const CritXWS w = critx_layout(ws, n, P, kmax, kgemv_t_bytes(P, n));
+  if (nom) *nom = w.c.nom;
+  if (score) *score = w.c.s;
+  if (delta) *delta = w.c.delta;
+  if (W) *W = w.c.W;
+  if (U) *U = w.U;
+  return 0;
+}
+
+// ---- Sigma generated from the points: the pass and the rounds ----
+extern "C" size_t vgposp_kernel_symv_workspace_bytes(int64_t n) {
+  if (n <= 0) return 0;
+  return ksymv_layout(nullptr, n).bytes;
+}
+
+template <bool SQ>
+static int ksymv_entry(const char* fn, int kind, const double* X, int64_t n, int d,
+                       const double* amp, const double* ls, const double* site_scale,
+                       const double* diag, const double* x, double* y, void* ws, size_t ws_bytes,
+                       void* stream) {
+  clear_error();
+  if (n == 0) return 0;
+#define KS_ARG(cond, idx)                                \
+  if (!(cond)) {                                         \
+    set_error("%s: bad argument %d (%s)", fn, idx, #cond); \
+    return -(idx);                                       \
+  }
+  KS_ARG(kind >= VGPOSP_KERNEL_EQ && kind <= VGPOSP_KERNEL_MATERN52, 1)
+  KS_ARG(X != nullptr, 2)
+  KS_ARG(n >= 1 && n <= CR_NMAX, 3)
+  KS_ARG(d >= 1 && d <= 8, 4)
+  KS_ARG(amp != nullptr, 5)
+  KS_ARG(ls != nullptr, 6)
+  KS_ARG(x != nullptr, 9)
+  KS_ARG(y != nullptr, 10)
+#undef KS_ARG
+  if (ws == nullptr) { set_error("%s: workspace is null", fn); return VGPOSP_E_WS; }
+  const KSymvWS w = ksymv_layout(ws, n);
+  if (ws_bytes < w.bytes) {
+    set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, w.bytes);
+    return VGPOSP_E_WS;
+  }
+  const SGen g{kind, d, X, amp, ls, site_scale, diag};
+  ksymv_launch<SQ>(g, n, x, y, w, nullptr, as_stream(stream));
+  VG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int vgposp_kernel_symv(int kind, const double* X, int64_t n, int d, const double* amp,
+                                  const double* ls, const double* site_scale, const double* diag,
+                                  const double* x, double* y, void* ws, size_t ws_bytes,
+                                  void* stream) {
+  return ksymv_entry<false>(__func__, kind, X, n, d, amp, ls, site_scale, diag, x, y, ws, ws_bytes,
+                            stream);
+}
+
+extern "C" int vgposp_kernel_symv_sq(int kind, const double* X, int64_t n, int d,
+                                     const double* amp, const double* ls,
+                                     const double* site_scale, const double* diag, const double* x,
+                                     double* y, void* ws, size_t ws_bytes, void* stream) {
+  return ksymv_entry<true>(__func__, kind, X, n, d, amp, ls, site_scale, diag, x, y, ws, ws_bytes,
+                           stream);
+}
+
+static CritWS critg_layout(void* base, int64_t n, int kmax) {
+  return crit_layout(base, n, kmax, ksymv_layout(nullptr, n).bytes);
+}
+
+extern "C" size_t vgposp_critg_workspace_bytes(int64_t n, int kmax) {
+  if (n <= 0 || kmax <= 0) return 0;
+  return critg_layout(nullptr, n, kmax).bytes;
+}
+
+extern "C" int vgposp_critg_init(int kind, const double* X, int64_t n, int d, const double* amp,
+                                 const double* ls, const double* site_scale, const double* diag,
+                                 int kmax, int criterion, double threshold,
+                                 const unsigned char* targets, const unsigned char* allowed,
+                                 void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  VG_CHECK_ARG(kind >= VGPOSP_KERNEL_EQ && kind <= VGPOSP_KERNEL_MATERN52, 1);
+  VG_CHECK_ARG(X != nullptr, 2);
+  VG_CHECK_ARG(n >= 1 && n <= CR_NMAX, 3);
+  VG_CHECK_ARG(d >= 1 && d <= 8, 4);
+  VG_CHECK_ARG(amp != nullptr, 5);
+  VG_CHECK_ARG(ls != nullptr, 6);
+  VG_CHECK_ARG(kmax >= 1 && kmax <= n, 9);
+  VG_CHECK_ARG(criterion == VGPOSP_CRIT_VARIANCE || criterion == VGPOSP_CRIT_ENTROPY, 10);
+  VG_CHECK_ARG(threshold >= 0.0, 11);
+  VG_CHECK_ARG(ws != nullptr, 14);
+  const CritWS w = critg_layout(ws, n, kmax);
+  VG_CHECK_WS(ws_bytes, w.bytes);
+  return crit_init_run(SGen{kind, d, X, amp, ls, site_scale, diag}, n, criterion, threshold,
+                       targets, allowed, w, as_stream(stream));
+}
+
+extern "C" int vgposp_critg_step(int kind, const double* X, int64_t n, int d, const double* amp,
+                                 const double* ls, const double* site_scale, const double* diag,
+                                 int kmax, int round, const int64_t* forced, int64_t j,
+                                 int64_t* selected, double* sel_delta, void* ws, size_t ws_bytes,
+                                 void* stream) {
+  clear_error();
+  VG_CHECK_ARG(kind >= VGPOSP_KERNEL_EQ && kind <= VGPOSP_KERNEL_MATERN52, 1);
+  VG_CHECK_ARG(X != nullptr, 2);
+  VG_CHECK_ARG(n >= 1 && n <= CR_NMAX, 3);
+  VG_CHECK_ARG(d >= 1 && d <= 8, 4);
+  VG_CHECK_ARG(amp != nullptr, 5);
+  VG_CHECK_ARG(ls != nullptr, 6);
+  VG_CHECK_ARG(kmax >= 1 && kmax <= n, 9);
+  VG_CHECK_ARG(round >= 0 && round < kmax, 10);
+  VG_CHECK_ARG(forced == nullptr || j >= 0, 12);
+  VG_CHECK_ARG(selected != nullptr, 13);
+  VG_CHECK_ARG(ws != nullptr, 15);
+  const CritWS w = critg_layout(ws, n, kmax);
+  VG_CHECK_WS(ws_bytes, w.bytes);
+  return crit_step_run(SGen{kind, d, X, amp, ls, site_scale, diag}, n, round, forced, j, selected,
+                       sel_delta, w, as_stream(stream));
+}
+
+extern "C" int vgposp_critg_buffers(void* ws, int64_t n, int kmax, double** nom, double** score,
+                                    double** delta, double** W) {
+  clear_error();
+  VG_CHECK_ARG(ws != nullptr, 1);
+  VG_CHECK_ARG(n >= 1, 2);
+  VG_CHECK_ARG(kmax >= 1, 3);
+  const CritWS w = critg_layout(ws, n, kmax);
+  if (nom) *nom = w.nom;
+  if (score) *score = w.s;
+  if (delta) *delta = w.delta;
+  if (W) *W = w.W;
+  return 0;
+}
+
+// Both sides generated: the rounds never pass over Sigma, so the location side has no partials.
+static CritXWS critgk_layout(void* base, int64_t n, int64_t P, int kmax) {
+  return critx_layout(base, n, P, kmax, kgemv_t_bytes(P, n), 0);
+}
+
+extern "C" size_t vgposp_critgk_workspace_bytes(int64_t n, int64_t P, int kmax) {
+  if (n <= 0 || P <= 0 || kmax <= 0) return 0;
+  return critgk_layout(nullptr, n, P, kmax).bytes;
+}
+
+extern "C" int vgposp_critgk_init(int64_t n, const double* diag, int kind, const double* Xt,
+                                  int64_t P, const double* X, int d, const double* amp,
+                                  const double* ls, const double* target_scale,
+                                  const double* site_scale, const double* weights, int kmax,
+                                  double threshold, const unsigned char* allowed, void* ws,
+                                  size_t ws_bytes, void* stream) {
+  clear_error();
+  VG_CHECK_ARG(n >= 1 && n <= CR_NMAX, 1);
+  VG_CHECK_ARG(kind >= VGPOSP_KERNEL_EQ && kind <= VGPOSP_KERNEL_MATERN52, 3);
+  VG_CHECK_ARG(Xt != nullptr, 4);
+  VG_CHECK_ARG(P >= 1 && P <= CRX_PMAX, 5);
+  VG_CHECK_ARG(X != nullptr, 6);
+  VG_CHECK_ARG(d >= 1 && d <= 8, 7);
+  VG_CHECK_ARG(amp != nullptr, 8);
+  VG_CHECK_ARG(ls != nullptr, 9);
+  VG_CHECK_ARG(kmax >= 1 && kmax <= n, 13);
+  VG_CHECK_ARG(threshold >= 0.0, 14);
+  VG_CHECK_ARG(ws != nullptr, 16);
+  const CritXWS w = critgk_layout(ws, n, P, kmax);
+  VG_CHECK_WS(ws_bytes, w.bytes);
+  const KGen g{kind, d, Xt, X, amp, ls, target_scale, site_scale};
+  return critk_init_run(SGen{kind, d, X, amp, ls, site_scale, diag}, g, n, P, weights, threshold,
+                        allowed, w, as_stream(stream));
+}
+
+extern "C" int vgposp_critgk_step(int64_t n, const double* diag, int kind, const double* Xt,
+                                  int64_t P, const double* X, int d, const double* amp,
+                                  const double* ls, const double* target_scale,
+                                  const double* site_scale, int kmax, int round,
+                                  const int64_t* forced, int64_t j, int64_t* selected,
+                                  double* sel_delta, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  VG_CHECK_ARG(n >= 1 && n <= CR_NMAX, 1);
+  VG_CHECK_ARG(kind >= VGPOSP_KERNEL_EQ && kind <= VGPOSP_KERNEL_MATERN52, 3);
+  VG_CHECK_ARG(Xt != nullptr, 4);
+  VG_CHECK_ARG(P >= 1 && P <= CRX_PMAX, 5);
+  VG_CHECK_ARG(X != nullptr, 6);
+  VG_CHECK_ARG(d >= 1 && d <= 8, 7);
+  VG_CHECK_ARG(amp != nullptr, 8);
+  VG_CHECK_ARG(ls != nullptr, 9);
+  VG_CHECK_ARG(kmax >= 1 && kmax <= n, 12);
+  VG_CHECK_ARG(round >= 0 && round < kmax, 13);
+  VG_CHECK_ARG(forced == nullptr || j >= 0, 15);
+  VG_CHECK_ARG(selected != nullptr, 16);
+  VG_CHECK_ARG(ws != nullptr, 18);
+  const CritXWS w = critgk_layout(ws, n, P, kmax);
+  VG_CHECK_WS(ws_bytes, w.bytes);
+  const KGen g{kind, d, Xt, X, amp, ls, target_scale, site_scale};
+  return critk_step_run(SGen{kind, d, X, amp, ls, site_scale, diag}, g, n, P, round, forced, j,
+                        selected, sel_delta, w, as_stream(stream));
+}
+
+extern "C" int vgposp_critgk_buffers(void* ws, int64_t n, int64_t P, int kmax, double** nom,
+                                     double** score, double** delta, double** W, double** U) {
+  clear_error();
+  VG_CHECK_ARG(ws != nullptr, 1);
+  VG_CHECK_ARG(n >= 1, 2);
+  VG_CHECK_ARG(P >= 1, 3);
+  VG_CHECK_ARG(kmax >= 1, 4);
+  const CritXWS w = critgk_layout(ws, n, P, kmax);
   if (nom) *nom = w.c.nom;
   if (score) *score = w.c.s;
   if (delta) *delta = w.c.delta;

@@ -301,7 +301,7 @@ def dg_create_random_cov(n, rng=None):
 
 def placement_from_points(X, k, kind="eq", amp=1.0, ls=1.0, noise=1e-2, jitter=1e-6, lazy=True,
                           candidates=None, placed=None, criterion="mi", targets=None,
-                          target_points=None, target_weights=None, cross=None):
+                          target_points=None, target_weights=None, cross=None, cov="dense"):
     """Assemble Sigma = K(X, X) + (noise + jitter) I on device and place k sensors.
 
     ``criterion``: ``"mi"`` (mutual information, the default), or ``"variance"`` / ``"entropy"``
@@ -313,7 +313,24 @@ def placement_from_points(X, k, kind="eq", amp=1.0, ls=1.0, noise=1e-2, jitter=1
     covariance K(Xt, X) is assembled without noise.  ``target_weights`` [P] >= 0 weigh them.
     ``cross``: ``"dense"`` (the default) assembles K(Xt, X) [P, N] once; ``"matrix_free"`` never
     does and generates its entries from the points in every round (placement_criteria.CrossKernel),
-    for a mesh whose cross-covariance does not fit the device."""
+    for a mesh whose cross-covariance does not fit the device.
+
+    ``cov``: ``"dense"`` (the default) assembles Sigma [N, N]; ``"matrix_free"`` never does and
+    generates it from the points in every round (placement_criteria.SiteKernel with the diagonal
+    amp^2 + noise + jitter the assembly has), for site sets whose covariance does not fit the
+    device.  It is for ``"variance"`` and ``"entropy"`` (the mutual-information placement factors
+    Sigma) and, with ``target_points``, implies ``cross="matrix_free"``."""
+    if cov not in ("dense", "matrix_free"):
+        raise ValueError(f"unknown cov {cov!r}; expected 'dense' or 'matrix_free'")
+    if cov == "matrix_free":
+        if criterion == "mi":
+            raise ValueError("cov='matrix_free' applies to criterion='variance' and 'entropy': "
+                             "the mutual-information placement factors Sigma")
+        if cross == "dense":
+            raise ValueError("cov='matrix_free' and cross='dense' exclude each other: a stored "
+                             "cross-covariance with a generated Sigma is not supported")
+        if target_points is not None and cross is None:
+            cross = "matrix_free"
     if cross is not None:
         if target_points is None:
             raise ValueError("cross needs target_points")
@@ -341,6 +358,14 @@ def placement_from_points(X, k, kind="eq", amp=1.0, ls=1.0, noise=1e-2, jitter=1
         if criterion not in CRITERIA:
             raise ValueError(f"unknown criterion {criterion!r}; expected 'mi' or one of "
                              f"{list(CRITERIA)}")
+    if cov == "matrix_free":
+        from .placement_criteria import CriterionPlacement, CrossKernel, SiteKernel
+        site = SiteKernel(kind, X, amp, ls, noise=noise + jitter)
+        gen = CrossKernel.from_site(site, Xt) if target_points is not None else None
+        g = CriterionPlacement(site, k, criterion, candidates=candidates, placed=placed,
+                               targets=targets, target_weights=target_weights,
+                               cross_kernel=gen).run(k)
+        return g.result()[0]
     K = linalg.kernel_matrix(kind, X, None, amp, ls, diag_shift=noise + jitter)[0]
     if criterion != "mi":
         from .placement_criteria import CriterionPlacement, CrossKernel

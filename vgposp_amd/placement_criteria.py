@@ -29,6 +29,12 @@ A mesh too fine to store R: ``cross_kernel`` = ``CrossKernel(kind, points, targe
 ls, ...)`` instead of ``cross_cov`` runs the same rounds with every entry of R generated from the
 2 d coordinates of its target and its location (``vgposp_kernel_gemv_t``), so the device holds
 (P + N) d doubles instead of P N.
+
+Sites too many to store Sigma: a ``SiteKernel(kind, points, amp, ls, scale=None, noise=0.0)`` in
+the place of ``cov_vv`` is Sigma = diag(a) K(X, X) diag(a) + diag(noise), generated from the points
+in every pass (``vgposp_kernel_symv``) and in the one column a round reads, so the device holds
+N (d + 2) doubles instead of N^2.  With ``CrossKernel.from_site`` beside it nothing of size N^2 or
+P N is held at all.
 """
 from __future__ import annotations
 
@@ -68,6 +74,69 @@ def _criterion_id(criterion):
         raise ValueError(f"unknown criterion {criterion!r}; expected one of {list(CRITERIA)}")
 
 
+def _points(name, X):
+    X = linalg.as_device(X)
+    X = X[:, None] if X.dim() == 1 else X
+    if X.dim() != 2 or X.shape[0] < 1:
+        raise ValueError(f"{name} must be [count, d] with count >= 1, got {tuple(X.shape)}")
+    return X.contiguous()
+
+
+def _positive_scalars(amp, ls):
+    for name, v in (("amp", amp), ("ls", ls)):
+        if not (np.ndim(v) == 0 and np.isfinite(float(v)) and float(v) > 0.0):
+            raise ValueError(f"{name} must be a finite, positive scalar, got {v!r}")
+    return float(amp), float(ls)
+
+
+def _host_vector(name, a, count):
+    a = (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a))
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.shape != (count,):
+        raise ValueError(f"{name} must have length {count}, got shape {a.shape}")
+    return a
+
+
+def _scale(name, a, count):
+    if a is None:
+        return None
+    a = _host_vector(name, a, count)
+    if not np.isfinite(a).all() or (a <= 0.0).any():
+        raise ValueError(f"{name} must be finite and positive")
+    return linalg.as_device(a)
+
+
+class SiteKernel:
+    """A covariance of the candidate sites that is never stored: Sigma = diag(scale) K(points,
+    points) diag(scale) + diag(noise) for one stationary kernel ``kind`` (``amp``, ``ls`` scalars)
+    under a per-point amplitude field.  ``points`` [N, d], d <= 8; ``scale`` [N] (default ones) is
+    finite and positive; ``noise`` (a scalar or [N]) is finite and not negative.  It goes where
+    ``cov_vv`` goes in ``CriterionPlacement`` and the placement functions.  The device holds the
+    points, the scale and the diagonal scale^2 amp^2 + noise: N (d + 2) doubles instead of N^2."""
+
+    def __init__(self, kind, points, amp, ls, scale=None, noise=0.0):
+        self.kind = linalg.kind_id(kind)
+        self.X = _points("points", points)
+        self.N, self.d = int(self.X.shape[0]), int(self.X.shape[1])
+        if not 1 <= self.d <= 8:
+            raise ValueError(f"points must have 1 <= d <= 8 coordinates, got {self.d}")
+        self.amp_value, self.ls_value = _positive_scalars(amp, ls)
+        self.amp, self.ls = linalg._vec(self.amp_value), linalg._vec(self.ls_value)
+        self.scale = _scale("scale", scale, self.N)
+        if np.ndim(noise) == 0:
+            noise = np.full(self.N, float(noise))
+        noise = _host_vector("noise", noise, self.N)
+        if not np.isfinite(noise).all() or (noise < 0.0).any():
+            raise ValueError("noise must be finite and not negative")
+        a = np.ones(self.N) if self.scale is None else self.scale.cpu().numpy()
+        self.diag = linalg.as_device(a * a * (self.amp_value * self.amp_value) + noise)
+
+    def args(self):
+        """(kind, X, N, d, amp, ls, site_scale, diag) as the vgposp_critg_* entries take them."""
+        return (self.kind, _p(self.X), self.N, self.d, _p(self.amp), _p(self.ls), _p(self.scale),
+                _p(self.diag))
+
+
 class CrossKernel:
     """A cross-covariance that is never stored: R = diag(target_scale) K(target_points, points)
     diag(site_scale) for one stationary kernel ``kind`` (``amp``, ``ls`` scalars) under a per-point
@@ -77,38 +146,45 @@ class CrossKernel:
 
     def __init__(self, kind, points, target_points, amp, ls, site_scale=None, target_scale=None):
         self.kind = linalg.kind_id(kind)
-
-        def pts(name, X):
-            X = linalg.as_device(X)
-            X = X[:, None] if X.dim() == 1 else X
-            if X.dim() != 2 or X.shape[0] < 1:
-                raise ValueError(f"{name} must be [count, d] with count >= 1, got "
-                                 f"{tuple(X.shape)}")
-            return X.contiguous()
-        self.X, self.Xt = pts("points", points), pts("target_points", target_points)
+        self.X, self.Xt = _points("points", points), _points("target_points", target_points)
         self.N, self.d = int(self.X.shape[0]), int(self.X.shape[1])
         self.P = int(self.Xt.shape[0])
         if not 1 <= self.d <= 8:
             raise ValueError(f"points must have 1 <= d <= 8 coordinates, got {self.d}")
         if self.Xt.shape[1] != self.d:
             raise ValueError(f"target_points must be [P, {self.d}], got {tuple(self.Xt.shape)}")
-        for name, v in (("amp", amp), ("ls", ls)):
-            if not (np.ndim(v) == 0 and np.isfinite(float(v)) and float(v) > 0.0):
-                raise ValueError(f"{name} must be a finite, positive scalar, got {v!r}")
-        self.amp, self.ls = linalg._vec(float(amp)), linalg._vec(float(ls))
+        self.amp_value, self.ls_value = _positive_scalars(amp, ls)
+        self.amp, self.ls = linalg._vec(self.amp_value), linalg._vec(self.ls_value)
+        self.site_scale = _scale("site_scale", site_scale, self.N)
+        self.target_scale = _scale("target_scale", target_scale, self.P)
 
-        def scale(name, a, count):
-            if a is None:
-                return None
-            a = (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a))
-            a = np.ascontiguousarray(a, dtype=np.float64)
-            if a.shape != (count,):
-                raise ValueError(f"{name} must have length {count}, got shape {a.shape}")
-            if not np.isfinite(a).all() or (a <= 0.0).any():
-                raise ValueError(f"{name} must be finite and positive")
-            return linalg.as_device(a)
-        self.site_scale = scale("site_scale", site_scale, self.N)
-        self.target_scale = scale("target_scale", target_scale, self.P)
+    @classmethod
+    def from_site(cls, site, target_points, target_scale=None):
+        """The cross-covariance between ``target_points`` and the sites of a ``SiteKernel``: its
+        kind, amp, ls, points and scale (the sensor noise is no part of it)."""
+        if not isinstance(site, SiteKernel):
+            raise ValueError("from_site needs a placement_criteria.SiteKernel")
+        gen = cls.__new__(cls)
+        gen.kind, gen.X, gen.N, gen.d = site.kind, site.X, site.N, site.d
+        gen.Xt = _points("target_points", target_points)
+        gen.P = int(gen.Xt.shape[0])
+        if gen.Xt.shape[1] != gen.d:
+            raise ValueError(f"target_points must be [P, {gen.d}], got {tuple(gen.Xt.shape)}")
+        gen.amp_value, gen.ls_value, gen.amp, gen.ls = (site.amp_value, site.ls_value, site.amp,
+                                                        site.ls)
+        gen.site_scale = site.scale
+        gen.target_scale = _scale("target_scale", target_scale, gen.P)
+        return gen
+
+    def agrees_with(self, site):
+        """Whether this cross-covariance and the ``SiteKernel`` describe one field: the same kind,
+        amp, ls, points and site scale."""
+        def same(a, b):
+            return (a is None and b is None) or (a is not None and b is not None
+                                                 and a.shape == b.shape and bool(torch.equal(a, b)))
+        return (self.kind == site.kind and self.amp_value == site.amp_value
+                and self.ls_value == site.ls_value and same(self.X, site.X)
+                and same(self.site_scale, site.scale))
 
     def args(self):
         """(kind, Xt, P, X, d, amp, ls, target_scale, site_scale) as the vgposp_critk_* entries
@@ -182,6 +258,10 @@ class CriterionPlacement:
 
     ``cross_kernel`` (a ``CrossKernel``, instead of ``cross_cov``) runs the same rounds on a
     cross-covariance generated from the points in every pass and never stored.
+
+    ``Sigma`` may be a ``SiteKernel`` instead of a matrix: the same rounds on a covariance
+    generated from the points.  ``diag`` and ``cross_cov`` do not combine with it, and a
+    ``cross_kernel`` must describe the same field (``CrossKernel.from_site``).
     """
 
     def __init__(self, Sigma, kmax, criterion="variance", candidates=None, placed=None,
@@ -189,11 +269,24 @@ class CriterionPlacement:
                  cross_kernel=None):
         self.criterion = criterion
         self.crit = _criterion_id(criterion)
-        S = _device_matrix(Sigma)
-        if S.dim() != 2 or S.shape[0] != S.shape[1]:
-            raise ValueError("cov_vv must be a square matrix")
+        self.site = Sigma if isinstance(Sigma, SiteKernel) else None
+        if self.site is not None:
+            if diag is not None:
+                raise ValueError("diag and a SiteKernel exclude each other: the SiteKernel holds "
+                                 "the diagonal")
+            if cross_cov is not None:
+                raise ValueError("cross_cov and a SiteKernel exclude each other: use "
+                                 "CrossKernel.from_site")
+            S = None
+            self.N = self.n = self.site.N
+            dev = self.site.X.device
+        else:
+            S = _device_matrix(Sigma)
+            if S.dim() != 2 or S.shape[0] != S.shape[1]:
+                raise ValueError("cov_vv must be a square matrix")
+            self.N = self.n = int(S.shape[0])
+            dev = S.device
         self.S = S
-        self.N = self.n = int(S.shape[0])
         if not (1 <= kmax <= self.N):
             raise ValueError(f"k must be in [1, {self.N}], got {kmax}")
         self.allowed, self.placed = normalize_constraints(self.N, kmax, candidates, placed)
@@ -207,6 +300,10 @@ class CriterionPlacement:
         if self.gen is not None:
             if self.gen.N != self.N:
                 raise ValueError(f"cross_kernel has {self.gen.N} points, cov_vv {self.N} locations")
+            if self.site is not None and not self.gen.agrees_with(self.site):
+                raise ValueError("cross_kernel and the SiteKernel must agree in kind, amp, ls, "
+                                 "points and site scale (CrossKernel.from_site builds one that "
+                                 "does)")
             self.P = self.gen.P
             self.omega = normalize_weights(self.P, target_weights)
         if cross_cov is not None:
@@ -222,7 +319,6 @@ class CriterionPlacement:
         self.m = len(self.placed)
         self.k = int(kmax)
         self.kmax = self.k + self.m
-        dev = S.device
         self.diag = None
         if diag is not None:
             self.diag = linalg.as_device(diag).reshape(-1)
@@ -234,13 +330,15 @@ class CriterionPlacement:
         self._allowed_dev, self._targets_dev = mask(self.allowed), mask(self.targets)
         self._placed_dev = (torch.as_tensor(self.placed, dtype=torch.int64, device=dev)
                             if self.m else None)
-        if self.gen is not None:
-            nbytes = query("vgposp_critk_workspace_bytes", self.n, self.P, self.kmax)
-        elif self.R is None:
-            nbytes = query("vgposp_crit_workspace_bytes", self.n, self.kmax)
+        # the entry family: crit / critx / critk on a stored Sigma, critg / critgk on a SiteKernel
+        if self.site is not None:
+            self._family = "vgposp_critg" if self.gen is None else "vgposp_critgk"
+        elif self.gen is not None:
+            self._family = "vgposp_critk"
         else:
-            nbytes = query("vgposp_critx_workspace_bytes", self.n, self.P, self.kmax)
-        self.ws = linalg.workspace(nbytes)
+            self._family = "vgposp_crit" if self.R is None else "vgposp_critx"
+        sizes = (self.n, self.kmax) if self.P == 0 else (self.n, self.P, self.kmax)
+        self.ws = linalg.workspace(query(self._family + "_workspace_bytes", *sizes))
         self.selected = torch.full((self.kmax,), -1, dtype=torch.int64, device=dev)
         self.sel_delta = torch.zeros(self.kmax, dtype=torch.float64, device=dev)
         self.rounds = 0
@@ -254,7 +352,12 @@ class CriterionPlacement:
     def _step(self, r, forced=None, j=0):
         tail = (r, _p(forced), j, _p(self.selected), _p(self.sel_delta), _p(self.ws),
                 self.ws.numel(), _stream())
-        if self.gen is not None:
+        if self.site is not None and self.gen is None:
+            call("vgposp_critg_step", *self.site.args(), self.kmax, *tail)
+        elif self.site is not None:
+            call("vgposp_critgk_step", self.n, _p(self.site.diag), *self.gen.args(), self.kmax,
+                 *tail)
+        elif self.gen is not None:
             call("vgposp_critk_step", *self._sigma_args(), *self.gen.args(), self.kmax, *tail)
         elif self.R is None:
             call("vgposp_crit_step", *self._sigma_args(), self.kmax, *tail)
@@ -262,7 +365,15 @@ class CriterionPlacement:
             call("vgposp_critx_step", *self._sigma_args(), *self._cross_args(), self.kmax, *tail)
 
     def init(self):
-        if self.gen is not None:
+        if self.site is not None and self.gen is None:
+            call("vgposp_critg_init", *self.site.args(), self.kmax, self.crit, self.threshold,
+                 _p(self._targets_dev), _p(self._allowed_dev), _p(self.ws), self.ws.numel(),
+                 _stream())
+        elif self.site is not None:
+            call("vgposp_critgk_init", self.n, _p(self.site.diag), *self.gen.args(),
+                 _p(self.omega), self.kmax, self.threshold, _p(self._allowed_dev), _p(self.ws),
+                 self.ws.numel(), _stream())
+        elif self.gen is not None:
             call("vgposp_critk_init", *self._sigma_args(), *self.gen.args(), _p(self.omega),
                  self.kmax, self.threshold, _p(self._allowed_dev), _p(self.ws), self.ws.numel(),
                  _stream())
@@ -300,10 +411,11 @@ class CriterionPlacement:
         cross = self.R is not None or self.gen is not None
         ptr = [ctypes.c_void_p() for _ in range(5 if cross else 4)]
         if not cross:
-            call("vgposp_crit_buffers", _p(self.ws), self.n, self.kmax, *map(ctypes.byref, ptr))
+            call(self._family + "_buffers", _p(self.ws), self.n, self.kmax,
+                 *map(ctypes.byref, ptr))
         else:
-            call("vgposp_critk_buffers" if self.R is None else "vgposp_critx_buffers",
-                 _p(self.ws), self.n, self.P, self.kmax, *map(ctypes.byref, ptr))
+            call(self._family + "_buffers", _p(self.ws), self.n, self.P, self.kmax,
+                 *map(ctypes.byref, ptr))
 
         def view(p, count):
             off = p.value - self.ws.data_ptr()
@@ -336,7 +448,7 @@ class CriterionPlacement:
 def _place(cov_vv, k, criterion, candidates, placed, targets, cross_cov=None,
            target_weights=None, cross_kernel=None):
     if k < 1:
-        N = int(np.shape(cov_vv)[0])
+        N = cov_vv.N if isinstance(cov_vv, SiteKernel) else int(np.shape(cov_vv)[0])
         normalize_constraints(N, max(int(k), 0), candidates, placed)
         normalize_targets(N, targets)
         check_cross_arguments(criterion, targets, cross_cov, target_weights, cross_kernel)
