@@ -813,6 +813,53 @@ int vgposp_critgk_buffers(void* ws, int64_t n, int64_t P, int kmax, double** nom
                           double** delta, double** W, double** U);
 
 /* ---------------------------------------------------------------------------------------------
+ * The rules on a covariance given by a factor: Sigma = F F^T + diag(noise).  This is the
+ * reference's own placement covariance, the empirical covariance of S tracer samples per location
+ * (tfp.stats.covariance(t_i, t_j, sample_axis=0) for every pair, main.py:190-199; the VGP-predicted
+ * variant, main_architecture_2_sampledistribution.py:470-479), with F = the centred samples over
+ * tr_stdev sqrt(S) (vgposp_center_rows); any low-rank-plus-diagonal covariance has the same form.
+ * F [n][s] row-major fp64, row pitch ldf >= s, only read; noise [n] >= 0 or NULL (zeros).
+ *   Sigma_ij = f_i . f_j (i != j),    Sigma_ii = dg_i = f_i . f_i + noise_i
+ * dg is computed once (the kernel of vgposp_row_sumsq) and kept in the workspace.  The device holds
+ * n s doubles instead of n^2.  Limits: 1 <= s <= 4,096; n <= 2^22 for the passes and n <= 2^21 for
+ * the rounds, whose scoring and selection kernels are those of vgposp_crit_step.
+ *
+ *   vgposp_factor_symv     y = Sigma x as z = F^T x, y_i = f_i . z + noise_i x_i: two streams over
+ *                          F, 16 n s bytes.  A workgroup of the first owns a block of rows, read
+ *                          with 16-byte loads when ldf is even and F is 16-byte aligned (8-byte
+ *                          loads otherwise), and writes one partial z to ws; the partials are added
+ *                          in ascending block order.  In the second a wave takes whole rows, z is
+ *                          broadcast through LDS and the order over s is fixed.  No float atomics,
+ *                          two launches are bit-identical, no host synchronisation.  n == 0 returns
+ *                          0 without device work.
+ *   vgposp_factor_symv_sq  y_j = sum_i x_i Sigma_ij^2 through the s x s moment matrix
+ *                          M = F^T diag(x) F:  y_j = f_j^T M f_j - x_j (f_j . f_j)^2 + x_j dg_j^2.
+ *                          M and F M run in row chunks through vgposp_gemm's kernels: O(n s^2).
+ *   vgposp_factor_symv_workspace_bytes(n, s): at most 8 (s^2 + 16,384 s) + 8 n bytes plus
+ *                          alignment; 0 when n <= 0 or s <= 0.
+ *   vgposp_critf_workspace_bytes / _init / _step / _buffers
+ *                          vgposp_crit_* with (Sigma, n, lda, diag) replaced by (F, n, s, ldf,
+ *                          noise): the same launch sequence; the column Sigma_{:,a} of a round is
+ *                          f_y . f_a, with dg_a at y = a.  Threshold, candidate mask, forced rounds,
+ *                          ties and "no candidate left -> -1" are those of vgposp_crit_step.  The
+ *                          workspace query returns 0 when n <= 0, s <= 0 or kmax <= 0.
+ * Argument errors return -(position) before any device work. */
+size_t vgposp_factor_symv_workspace_bytes(int64_t n, int64_t s);
+int vgposp_factor_symv(const double* F, int64_t n, int64_t s, int64_t ldf, const double* noise,
+                       const double* x, double* y, void* ws, size_t ws_bytes, void* stream);
+int vgposp_factor_symv_sq(const double* F, int64_t n, int64_t s, int64_t ldf, const double* noise,
+                          const double* x, double* y, void* ws, size_t ws_bytes, void* stream);
+size_t vgposp_critf_workspace_bytes(int64_t n, int64_t s, int kmax);
+int vgposp_critf_init(const double* F, int64_t n, int64_t s, int64_t ldf, const double* noise,
+                      int kmax, int criterion, double threshold, const unsigned char* targets,
+                      const unsigned char* allowed, void* ws, size_t ws_bytes, void* stream);
+int vgposp_critf_step(const double* F, int64_t n, int64_t s, int64_t ldf, const double* noise,
+                      int kmax, int round, const int64_t* forced, int64_t j, int64_t* selected,
+                      double* sel_delta, void* ws, size_t ws_bytes, void* stream);
+int vgposp_critf_buffers(void* ws, int64_t n, int64_t s, int kmax, double** nom, double** score,
+                         double** delta, double** W);
+
+/* ---------------------------------------------------------------------------------------------
  * Exact algorithm 3 at grid sizes where cov_vv cannot be dense (config C4, 128^3): the beta-decay
  * tapered covariance (main_architecture_2_sampledistribution.py:355-421) is a sparse SPD stencil
  * matrix, and snippets_a3.sparse_placement_algorithm_3 (snippets_a3.py:43-364) with tf_nominator /

@@ -60,6 +60,9 @@ _KGEN = [_i32, _c_void_p, _i64, _c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p
 # a covariance generated from the points: kind, X, n, d, amp, ls, site_scale, diag
 _SGEN = [_i32, _c_void_p, _i64, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p]
 
+# a covariance given by a factor: F, n, s, ldf, noise
+_SFAC = [_c_void_p, _i64, _i64, _i64, _c_void_p]
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     "vgposp_abi_version": (_i32, []),
@@ -304,6 +307,16 @@ SIGNATURES = {
                               _c_void_p]),
     "vgposp_critgk_buffers": (_i32, [_c_void_p, _i64, _i64, _i32]
                               + [ctypes.POINTER(_c_void_p)] * 5),
+    "vgposp_factor_symv_workspace_bytes": (_size, [_i64, _i64]),
+    "vgposp_factor_symv": (_i32, _SFAC + [_c_void_p, _c_void_p, _c_void_p, _size, _c_void_p]),
+    "vgposp_factor_symv_sq": (_i32, _SFAC + [_c_void_p, _c_void_p, _c_void_p, _size, _c_void_p]),
+    "vgposp_critf_workspace_bytes": (_size, [_i64, _i64, _i32]),
+    "vgposp_critf_init": (_i32, _SFAC + [_i32, _i32, _f64, _c_void_p, _c_void_p, _c_void_p, _size,
+                                         _c_void_p]),
+    "vgposp_critf_step": (_i32, _SFAC + [_i32, _i32, _c_void_p, _i64, _c_void_p, _c_void_p,
+                                         _c_void_p, _size, _c_void_p]),
+    "vgposp_critf_buffers": (_i32, [_c_void_p, _i64, _i64, _i32]
+                             + [ctypes.POINTER(_c_void_p)] * 4),
 }
 
 _lock = threading.Lock()
@@ -370,6 +383,8 @@ KERNEL_SOURCES = {
     "greedy_trmv": ["greedy.hip", "common.h", "Makefile"],
     "greedy_colsq": ["greedy.hip", "common.h", "Makefile"],
     "criteria_symv": ["criteria.hip", "common.h", "Makefile"],
+    "criteria_fsymv": ["criteria.hip", "common.h", "Makefile"],
+    "criteria_fsymv_sq": ["criteria.hip", "common.h", "Makefile"],
     "criteria_gemv_t": ["criteria.hip", "common.h", "Makefile"],
     "criteria_gemv_t_sq": ["criteria.hip", "common.h", "Makefile"],
     "criteria_kgemv_t": ["criteria.hip", "psd.h", "common.h", "Makefile"],

@@ -108,6 +108,31 @@ def kernel_symv(kind, X, amp, ls, x, squared=False, site_scale=None, diag=None, 
     return out
 
 
+def factor_symv(F, x, noise=None, squared=False, out=None):
+    """out = Sigma x for Sigma = F F^T + diag(noise), Sigma never formed (``squared``: of the
+    squared entries, through the S x S moment matrix F^T diag(x) F).  F [n, S] (a device float64
+    view with unit column stride is used where it lies), x [n], noise [n] or None."""
+    if not (isinstance(F, torch.Tensor) and F.device.type == "cuda" and F.dim() == 2
+            and F.dtype == F64 and F.stride(1) == 1 and F.stride(0) >= F.shape[1]):
+        F = linalg.as_device(F)
+    if F.dim() != 2:
+        raise ValueError("factor_symv: F must be [n, S]")
+    n, S = F.shape
+    x = linalg.as_device(x).reshape(-1).contiguous()
+    if x.numel() != n:
+        raise ValueError("factor_symv: shapes do not match")
+    if noise is not None:
+        noise = linalg.as_device(noise).reshape(-1).contiguous()
+        if noise.numel() != n:
+            raise ValueError("factor_symv: shapes do not match")
+    if out is None:
+        out = torch.zeros(n, dtype=F64, device=F.device)
+    ws = linalg.workspace(query("vgposp_factor_symv_workspace_bytes", n, S))
+    call("vgposp_factor_symv_sq" if squared else "vgposp_factor_symv", _p(F), n, S, F.stride(0),
+         _p(noise), _p(x), _p(out), _p(ws), ws.numel(), _stream())
+    return out
+
+
 def center_rows_(T, scale=1.0):
     """In place: T[i] <- (T[i] - mean(T[i])) * scale (device [N, S])."""
     if T.dim() != 2 or T.stride(1) != 1:
@@ -171,6 +196,6 @@ def cov_vv_from_vgp(vgp, locations, tp_samples, tr_mean=0.0, tr_stdev=1.0):
     return empirical_cov(vgp_tracer_samples(vgp, locations, tp_samples), tr_mean, tr_stdev)
 
 
-__all__ = ["kernel_matvec", "kernel_gemv_t", "kernel_symv", "center_rows_", "empirical_cov", "index_taper_",
+__all__ = ["kernel_matvec", "kernel_gemv_t", "kernel_symv", "factor_symv", "center_rows_", "empirical_cov", "index_taper_",
            "vgp_tracer_samples",
            "cov_vv_from_vgp"]

@@ -29,11 +29,14 @@
 // Sigma need not be stored: for Sigma = diag(a) K(X, X) diag(a) + a diagonal vector the same
 // rounds run with every entry generated from the points (SGen, ksymv_kernel, the critg / critgk
 // entries); the host sequences of the rounds are written once, against where Sigma comes from.
+// The third source is a factor: Sigma = F F^T + diag(noise) with F [n][S] the centred samples of an
+// empirical covariance (SFactor, the critf entries): a pass is two tall-skinny streams over F.
 #include <algorithm>
 #include <cfloat>
 #include <type_traits>
 
 #include "common.h"
+#include "dense.h"
 #include "psd.h"
 
 namespace vgposp {
@@ -1043,6 +1046,367 @@ __global__ __launch_bounds__(CR_B) void critg_row_kernel(SGen g, int64_t n,
   w.nom[i] -= wy * wy;
 }
 
+// ---- Sigma generated from a factor: Sigma = F F^T off the diagonal ----
+// F [n][S] row-major, pitch ldf >= S, only read (the centred samples of an empirical covariance
+// over sqrt(S), a PCA-truncated field, a Nystroem factor); noise [n] >= 0 or NULL.
+//   Sigma_ij = f_i . f_j  (i != j),   Sigma_ii = dg_i = f_i . f_i + noise_i
+// dg is computed once (row_sumsq of gp.hip, then the noise) and kept in the workspace.  The three
+// things the rounds need have closed forms on F:
+//   column a:   f_y . f_a                                       (factor_row with z = f_a)
+//   y = Sigma x:   z = F^T x, y_i = f_i . z + noise_i x_i       (factor_tv, then factor_row)
+//   y_j = sum_i x_i Sigma_ij^2:   M = F^T diag(x) F (S x S),
+//                  y_j = f_j^T M f_j - x_j (f_j . f_j)^2 + x_j dg_j^2
+// the last in row chunks through the fp64 MFMA GEMM: O(n S^2), never n^2.
+struct SFactor {
+  const double* F;
+  int64_t S, ldf;
+  const double* noise;
+};
+
+constexpr int64_t FC_NMAX = (int64_t)1 << 22;  // the passes; the rounds keep CR_NMAX
+constexpr int64_t FC_SMAX = 4096;
+constexpr int FC_TH = 256;        // four waves; a wave of factor_row owns 64 rows
+constexpr int FC_NBLK = 1024;     // at most this many row blocks (partials of z)
+constexpr int64_t FC_ROWS = 16384;  // rows of a chunk of the squared pass, split partials included
+static_assert(FC_TH == CR_B, "factor_row's column form does crit_row_kernel's 256 rows");
+
+// dg [n], z [S], M [S][S], and one area that is the partials of z ([nblk][S]) in the plain pass
+// and, in the squared pass, the chunk temporary ([rc][S]) followed by the GEMM's split-K partials.
+struct FacWS {
+  double *dg, *z, *M, *zpart, *tmp, *part;
+  int64_t rb, nblk, rc;  // rows per block of factor_tv, blocks, rows per chunk
+  int nsplit;
+  size_t bytes;
+};
+
+static FacWS fac_layout(void* base, int64_t n, int64_t S) {
+  FacWS w{};
+  w.rb = std::max<int64_t>(64, ceil_div(ceil_div(n, FC_NBLK), 64) * 64);
+  w.nblk = ceil_div(n, w.rb);
+  // an S x S result is a few output tiles: enough K ranges to fill the device with them
+  w.nsplit = (int)std::min<int64_t>(64, std::max<int64_t>(1, 8192 / S));
+  // what is set aside for the split partials bounds nsplit S^2 and grows with S
+  const int64_t pcap = std::min<int64_t>(64 * S * S, 8192 * S);
+  w.rc = std::min<int64_t>(FC_ROWS - pcap / S, n + (n & 1));  // even: chunks start 16-byte aligned
+  const int64_t area = std::max(std::min<int64_t>(FC_NBLK, ceil_div(n, 64)) * S, w.rc * S + pcap);
+  char* p = static_cast<char*>(base);
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char* r = p ? p + off : nullptr;
+    off += cr_align(bytes);
+    return (double*)r;
+  };
+  w.dg = take((size_t)n * 8);
+  w.z = take((size_t)S * 8);
+  w.M = take((size_t)S * S * 8);
+  w.zpart = w.tmp = take((size_t)area * 8);
+  w.part = w.tmp ? w.tmp + w.rc * S : nullptr;
+  w.bytes = off;
+  return w;
+}
+
+typedef double fc_d2 __attribute__((ext_vector_type(2)));
+
+// The column pair (c, c + 1) of the row at p (p already points at column c), zero past S.  One
+// 16-byte load where the pair is whole and VEC (even pitch, 16-byte aligned base), else 8-byte
+// loads; the last odd column is never read as a pair (it may be the buffer's last element).
+template <bool VEC>
+__device__ __forceinline__ fc_d2 fc_pair(const double* __restrict__ p, int64_t c, int64_t S) {
+  fc_d2 m = {0.0, 0.0};
+  if (c >= S) return m;
+  if (c + 1 < S) {
+    if (VEC) return *reinterpret_cast<const fc_d2*>(p);
+    m.x = p[0];
+    m.y = p[1];
+    return m;
+  }
+  m.x = p[0];
+  return m;
+}
+
+// factor_tv: zpart[blockIdx.x][c] = sum over the block's rows r of F[r][c] x[r].  A workgroup owns
+// rb rows; wave wv takes the rows r0 + wv, r0 + wv + 4, ... in ascending order, a lane the column
+// pairs 2 lane + 128 q (q < NQ) of a chunk of 128 NQ columns, with 8 / NQ rows in flight so that a
+// short row still keeps eight loads per lane in the air.  The four waves' sums are added through
+// LDS in a fixed order.
+template <bool VEC, int NQ>
+__global__ __launch_bounds__(FC_TH) void factor_tv_kernel(const double* __restrict__ F, int64_t n,
+                                                         int64_t S, int64_t ldf,
+                                                         const double* __restrict__ x, int64_t rb,
+                                                         double* __restrict__ zpart,
+                                                         const double* __restrict__ gate) {
+  constexpr int RU = 8 / NQ, CW = 128 * NQ;
+  __shared__ double acc[FC_TH / 64][CW];
+  if (gate && *gate != 0.0) return;  // workgroup-uniform: no barrier is left waiting
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t r0 = (int64_t)blockIdx.x * rb, r1 = min(r0 + rb, n);
+  for (int64_t cc = 0; cc < S; cc += CW) {
+    fc_d2 a[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) a[q] = fc_d2{0.0, 0.0};
+    const int64_t c0 = cc + 2 * lane;
+    int64_t r = r0 + wv;
+    for (; r + 4 * (RU - 1) < r1; r += 4 * RU) {
+      fc_d2 m[RU][NQ];
+#pragma unroll
+      for (int u = 0; u < RU; ++u)
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+          m[u][q] = fc_pair<VEC>(F + (r + 4 * u) * ldf + c0 + 128 * q, c0 + 128 * q, S);
+#pragma unroll
+      for (int u = 0; u < RU; ++u) {
+        const double xr = x[r + 4 * u];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+          a[q].x = fma(m[u][q].x, xr, a[q].x);
+          a[q].y = fma(m[u][q].y, xr, a[q].y);
+        }
+      }
+    }
+    for (; r < r1; r += 4) {
+      const double xr = x[r];
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        const fc_d2 m = fc_pair<VEC>(F + r * ldf + c0 + 128 * q, c0 + 128 * q, S);
+        a[q].x = fma(m.x, xr, a[q].x);
+        a[q].y = fma(m.y, xr, a[q].y);
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      acc[wv][2 * lane + 128 * q] = a[q].x;
+      acc[wv][2 * lane + 128 * q + 1] = a[q].y;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < CW; i += FC_TH)
+      if (cc + i < S)
+        zpart[(int64_t)blockIdx.x * S + cc + i] = (acc[0][i] + acc[1][i]) + (acc[2][i] + acc[3][i]);
+    __syncthreads();
+  }
+}
+static_assert(FC_TH == 256, "factor_tv_kernel adds four waves");
+
+// z[c] = the partials of the blocks in ascending order: sixteen waves take sixteen consecutive
+// ranges of blocks, each in ascending order, and the ranges are added in ascending order.
+__global__ __launch_bounds__(1024) void factor_tv_reduce_kernel(int64_t S, int64_t nblk,
+                                                                const double* __restrict__ zpart,
+                                                                double* __restrict__ z,
+                                                                const double* __restrict__ gate) {
+  __shared__ double sw[16][64];
+  if (gate && *gate != 0.0) return;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t c = (int64_t)blockIdx.x * 64 + lane;
+  const int64_t per = (nblk + 15) / 16, b0 = wv * per, b1 = min(b0 + per, nblk);
+  double s = 0.0;
+  if (c < S) {
+#pragma unroll 8
+    for (int64_t b = b0; b < b1; ++b) s += zpart[b * S + c];
+  }
+  sw[wv][lane] = s;
+  __syncthreads();
+  if (wv == 0 && c < S) {
+    double t = sw[0][lane];
+    for (int k = 1; k < 16; ++k) t += sw[k][lane];
+    z[c] = t;
+  }
+}
+
+// factor_row: one dot product of length S per row, a wave per row so that any S is coalesced: lane
+// l holds the column pairs 2 l + 128 q in ascending q (the fixed order over S), then the wave's
+// butterfly.  A wave owns 64 consecutive rows, four in flight; the sum of row base + l is kept by
+// lane l, so that what follows the dot runs one lane per row on coalesced vectors.
+//   FR_PLAIN  y_i = f_i . z + noise_i x_i                z [S] broadcast through LDS
+//   FR_COL    the column of a round: z = f_a, the entry dg_a at i = a, then crit_row_kernel's
+//             arithmetic (the W row, w.t, the nom downdate)
+//   FR_SQ     y_i = f_i . h_i - x_i (f_i . f_i)^2 + x_i dg_i^2,  h_i = row i of H = F M ([n][S])
+enum { FR_PLAIN = 0, FR_COL = 1, FR_SQ = 2 };
+
+template <bool VEC, int MODE>
+__global__ __launch_bounds__(FC_TH) void factor_row_kernel(
+    const double* __restrict__ F, int64_t n, int64_t S, int64_t ldf, const double* __restrict__ z,
+    const double* __restrict__ noise, const double* __restrict__ dg, const double* __restrict__ x,
+    double* __restrict__ y, const int64_t* __restrict__ selected, int round, CritWS w,
+    const double* __restrict__ gate) {
+  extern __shared__ double zs[];  // S doubles (FR_PLAIN, FR_COL)
+  if (gate && *gate != 0.0) return;  // workgroup-uniform, as the next one
+  int64_t a = -1;
+  if (MODE == FR_COL) {
+    a = selected[round];
+    if (a < 0) return;
+    z = F + a * ldf;
+  }
+  if (MODE != FR_SQ) {
+    for (int64_t i = threadIdx.x; i < S; i += FC_TH) zs[i] = z[i];
+    __syncthreads();
+  }
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t base = (int64_t)blockIdx.x * FC_TH + 64 * wv;
+  if (base >= n) return;
+  const bool hvec = (S & 1) == 0;  // H has pitch S and a 256-byte aligned base
+  double mine = 0.0, mff = 0.0;
+  for (int k = 0; k < 64 && base + k < n; k += 4) {
+    double s[4] = {0.0, 0.0, 0.0, 0.0}, ff[4] = {0.0, 0.0, 0.0, 0.0};
+    int64_t row[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) row[u] = min(base + k + u, n - 1);  // clamped: loaded, not kept
+    for (int64_t cq = 0; cq < S; cq += 128) {
+      const int64_t c = cq + 2 * lane;
+      fc_d2 m[4], h[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) m[u] = fc_pair<VEC>(F + row[u] * ldf + c, c, S);
+      if (MODE == FR_SQ) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+          h[u] = hvec ? fc_pair<true>(z + row[u] * S + c, c, S)
+                      : fc_pair<false>(z + row[u] * S + c, c, S);
+      } else {
+        const fc_d2 zz = {c < S ? zs[c] : 0.0, c + 1 < S ? zs[c + 1] : 0.0};
+#pragma unroll
+        for (int u = 0; u < 4; ++u) h[u] = zz;
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        s[u] = fma(m[u].x, h[u].x, s[u]);
+        s[u] = fma(m[u].y, h[u].y, s[u]);
+        if (MODE == FR_SQ) {
+          ff[u] = fma(m[u].x, m[u].x, ff[u]);
+          ff[u] = fma(m[u].y, m[u].y, ff[u]);
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const double v = wave_sum(s[u]);
+      if (lane == k + u) mine = v;
+      if (MODE == FR_SQ) {
+        const double f2 = wave_sum(ff[u]);
+        if (lane == k + u) mff = f2;
+      }
+    }
+  }
+  const int64_t i = base + lane;
+  if (i >= n) return;
+  if (MODE == FR_PLAIN) y[i] = noise ? fma(noise[i], x[i], mine) : mine;
+  if (MODE == FR_SQ) {
+    const double xi = x[i], d = dg[i];
+    y[i] = (mine - xi * (mff * mff)) + xi * (d * d);
+  }
+  if (MODE == FR_COL) {
+    double s = i == a ? dg[a] : mine;
+    for (int t = 0; t < round; ++t) s -= w.piv[1 + t] * w.W[(int64_t)t * n + i];
+    const double noma = w.piv[0];
+    const double wy = noma >= w.prm[0] && noma > 0.0 ? s / sqrt(noma) : 0.0;
+    w.W[(int64_t)round * n + i] = wy;
+    w.wt[i] = wy * w.tvec[i];
+    w.nom[i] -= wy * wy;
+  }
+}
+
+template <int MODE>
+static void factor_row_launch(const SFactor& f, int64_t n, const double* z, const double* dg,
+                              const double* x, double* y, const int64_t* selected, int round,
+                              const CritWS& w, const double* gate, hipStream_t s) {
+  const dim3 grid((unsigned)ceil_div(n, FC_TH));
+  const size_t lds = MODE == FR_SQ ? 0 : (size_t)f.S * 8;
+  if (symv_vec(f.F, f.ldf))
+    hipLaunchKernelGGL((factor_row_kernel<true, MODE>), grid, dim3(FC_TH), lds, s, f.F, n, f.S,
+                       f.ldf, z, f.noise, dg, x, y, selected, round, w, gate);
+  else
+    hipLaunchKernelGGL((factor_row_kernel<false, MODE>), grid, dim3(FC_TH), lds, s, f.F, n, f.S,
+                       f.ldf, z, f.noise, dg, x, y, selected, round, w, gate);
+}
+
+// dg_i = f_i . f_i (+ noise_i)
+__global__ void factor_noise_kernel(int64_t n, const double* __restrict__ noise,
+                                    double* __restrict__ dg) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dg[i] += noise[i];
+}
+
+static int factor_diag_launch(const SFactor& f, int64_t n, double* dg, hipStream_t s) {
+  if (int rc = vgposp_row_sumsq(f.F, n, f.S, f.ldf, 1.0, 0.0, dg, s)) return rc;
+  if (f.noise) {
+    hipLaunchKernelGGL(factor_noise_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, n,
+                       f.noise, dg);
+    VG_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+// y = Sigma x: factor_tv, its reduction, factor_row.  F is read twice.
+static int factor_symv_launch(const SFactor& f, int64_t n, const double* x, double* y,
+                              const FacWS& w, const double* gate, hipStream_t s) {
+  const double ns = (double)n * (double)f.S;
+  ProfScope ps("criteria_fsymv", s, 4.0 * ns, 16.0 * ns);
+  const dim3 grid((unsigned)w.nblk);
+  const bool vec = symv_vec(f.F, f.ldf);
+#define FC_TV(NQ)                                                                                 \
+  if (vec)                                                                                        \
+    hipLaunchKernelGGL((factor_tv_kernel<true, NQ>), grid, dim3(FC_TH), 0, s, f.F, n, f.S, f.ldf, \
+                       x, w.rb, w.zpart, gate);                                                   \
+  else                                                                                            \
+    hipLaunchKernelGGL((factor_tv_kernel<false, NQ>), grid, dim3(FC_TH), 0, s, f.F, n, f.S,       \
+                       f.ldf, x, w.rb, w.zpart, gate);
+  if (f.S <= 128) {
+    FC_TV(1)
+  } else if (f.S <= 256) {
+    FC_TV(2)
+  } else {
+    FC_TV(4)
+  }
+#undef FC_TV
+  hipLaunchKernelGGL(factor_tv_reduce_kernel, dim3((unsigned)ceil_div(f.S, 64)), dim3(1024), 0, s,
+                     f.S, w.nblk, w.zpart, w.z, gate);
+  factor_row_launch<FR_PLAIN>(f, n, w.z, nullptr, x, y, nullptr, 0, CritWS{}, gate, s);
+  VG_LAUNCH_CHECK();
+  return 0;
+}
+
+// tmp[i][j] = x[i] F[i][j] for the rows of a chunk (pitch S)
+__global__ __launch_bounds__(256) void factor_scale_kernel(const double* __restrict__ F,
+                                                           int64_t rows, int64_t S, int64_t ldf,
+                                                           const double* __restrict__ x,
+                                                           double* __restrict__ tmp) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= rows * S) return;
+  const int64_t i = e / S, j = e - i * S;
+  tmp[e] = x[i] * F[i * ldf + j];
+}
+
+// y_j = sum_i x_i Sigma_ij^2 through the moment matrix M = F^T diag(x) F, both products in row
+// chunks of w.rc rows through the fp64 MFMA GEMM (split-K for the S x S result of a long chunk).
+// dg must hold the diagonal.
+static int factor_symv_sq_launch(const SFactor& f, int64_t n, const double* x, double* y,
+                                 const FacWS& w, hipStream_t s) {
+  const int64_t S = f.S;
+  const double ns = (double)n * (double)S;
+  ProfScope ps("criteria_fsymv_sq", s, 4.0 * ns * (double)S, 8.0 * 5.0 * ns);
+  for (int64_t c0 = 0; c0 < n; c0 += w.rc) {
+    const int64_t rc = std::min(w.rc, n - c0);
+    const double* Fc = f.F + c0 * f.ldf;
+    hipLaunchKernelGGL(factor_scale_kernel, dim3((unsigned)ceil_div(rc * S, 256)), dim3(256), 0, s,
+                       Fc, rc, S, f.ldf, x + c0, w.tmp);
+    VG_LAUNCH_CHECK();
+    if (int rc2 = gemm_launch_split(1, 0, S, S, rc, 1.0, Fc, f.ldf, w.tmp, S, c0 ? 1.0 : 0.0, w.M,
+                                    S, VGPOSP_FULL, 0, 0, w.nsplit, w.nsplit > 1 ? w.part : nullptr,
+                                    s))
+      return rc2;
+  }
+  for (int64_t c0 = 0; c0 < n; c0 += w.rc) {
+    const int64_t rc = std::min(w.rc, n - c0);
+    const SFactor fc{f.F + c0 * f.ldf, S, f.ldf, nullptr};
+    if (int rc2 = gemm_launch(0, 0, rc, S, S, 1.0, fc.F, f.ldf, w.M, S, 0.0, w.tmp, S, VGPOSP_FULL,
+                              0, 0, s))
+      return rc2;
+    factor_row_launch<FR_SQ>(fc, rc, w.tmp, w.dg + c0, x + c0, y + c0, nullptr, 0, CritWS{},
+                             nullptr, s);
+    VG_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
 // ---- where Sigma comes from: what the host sequences of the rounds are written against ----
 struct SigmaStored {
   const double* S;
@@ -1062,6 +1426,15 @@ static void sigma_init(const SGen& sg, int64_t n, int criterion, double thr,
   hipLaunchKernelGGL(critg_init_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, sg, n,
                      criterion, thr, targets, allowed, w);
 }
+// the diagonal into the pass area, where every later use reads it; then crit_init_kernel on it
+static void sigma_init(const SFactor& sg, int64_t n, int criterion, double thr,
+                       const unsigned char* targets, const unsigned char* allowed, const CritWS& w,
+                       hipStream_t s) {
+  const FacWS fw = fac_layout(w.symv, n, sg.S);
+  if (factor_diag_launch(sg, n, fw.dg, s)) return;  // the launch check that follows reports it
+  hipLaunchKernelGGL(crit_init_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, nullptr,
+                     n, (int64_t)0, fw.dg, criterion, thr, targets, allowed, w);
+}
 
 static void sigma_row(const SigmaStored& sg, int64_t n, const int64_t* selected, int round,
                       const CritWS& w, hipStream_t s) {
@@ -1075,17 +1448,32 @@ static void sigma_row(const SGen& sg, int64_t n, const int64_t* selected, int ro
                        dim3(CR_B), 0, s, sg, n, selected, round, w);
   });
 }
+static void sigma_row(const SFactor& sg, int64_t n, const int64_t* selected, int round,
+                      const CritWS& w, hipStream_t s) {
+  factor_row_launch<FR_COL>(sg, n, nullptr, fac_layout(w.symv, n, sg.S).dg, nullptr, nullptr,
+                            selected, round, w, nullptr, s);
+}
 
 // The pass over Sigma on the partials area of the workspace.
 template <bool SQ>
-static void sigma_pass(const SigmaStored& sg, int64_t n, const double* x, double* y, void* area,
-                       const double* gate, hipStream_t s) {
+static int sigma_pass(const SigmaStored& sg, int64_t n, const double* x, double* y, void* area,
+                      const double* gate, hipStream_t s) {
   symv_launch<SQ>(sg.S, n, sg.lda, sg.diag, x, y, symv_layout(area, n), gate, s);
+  return 0;
 }
 template <bool SQ>
-static void sigma_pass(const SGen& sg, int64_t n, const double* x, double* y, void* area,
-                       const double* gate, hipStream_t s) {
+static int sigma_pass(const SGen& sg, int64_t n, const double* x, double* y, void* area,
+                      const double* gate, hipStream_t s) {
   ksymv_launch<SQ>(sg, n, x, y, ksymv_layout(area, n), gate, s);
+  return 0;
+}
+// (the squared pass runs at init alone and is never gated)
+template <bool SQ>
+static int sigma_pass(const SFactor& sg, int64_t n, const double* x, double* y, void* area,
+                      const double* gate, hipStream_t s) {
+  const FacWS fw = fac_layout(area, n, sg.S);
+  if (SQ) return factor_symv_sq_launch(sg, n, x, y, fw, s);
+  return factor_symv_launch(sg, n, x, y, fw, gate, s);
 }
 
 // The in-V rule, after the entry has checked its arguments and laid out w.
@@ -1096,7 +1484,7 @@ static int crit_init_run(const Sigma& sg, int64_t n, int criterion, double thres
   sigma_init(sg, n, criterion, threshold, targets, allowed, w, s);
   VG_LAUNCH_CHECK();
   if (criterion == VGPOSP_CRIT_VARIANCE) {  // s_y = sum_v t_v Sigma_vy^2
-    sigma_pass<true>(sg, n, w.tvec, w.s, w.symv, nullptr, s);
+    if (int rc = sigma_pass<true>(sg, n, w.tvec, w.s, w.symv, nullptr, s)) return rc;
     VG_LAUNCH_CHECK();
   }
   return 0;
@@ -1127,7 +1515,7 @@ static int crit_step_run(const Sigma& sg, int64_t n, int round, const int64_t* f
   hipLaunchKernelGGL(crit_fold_kernel, dim3((unsigned)round + 1), dim3(CR_B), 0, s, (int64_t)nb,
                      selected, round, w);
   VG_LAUNCH_CHECK();
-  sigma_pass<false>(sg, n, w.wt, w.g, w.symv, gate, s);
+  if (int rc = sigma_pass<false>(sg, n, w.wt, w.g, w.symv, gate, s)) return rc;
   VG_LAUNCH_CHECK();
   {
     ProfScope ps("criteria_update", s, 0.0, 8.0 * (double)n * (4 + round));
@@ -1763,5 +2151,119 @@ extern "C" int vgposp_critgk_buffers(void* ws, int64_t n, int64_t P, int kmax, d
   if (delta) *delta = w.c.delta;
   if (W) *W = w.c.W;
   if (U) *U = w.U;
+  return 0;
+}
+
+// ---- Sigma generated from a factor: the passes and the rounds ----
+extern "C" size_t vgposp_factor_symv_workspace_bytes(int64_t n, int64_t s) {
+  if (n <= 0 || s <= 0) return 0;
+  return fac_layout(nullptr, n, s).bytes;
+}
+
+template <bool SQ>
+static int fsymv_entry(const char* fn, const double* F, int64_t n, int64_t S, int64_t ldf,
+                       const double* noise, const double* x, double* y, void* ws, size_t ws_bytes,
+                       void* stream) {
+  clear_error();
+  if (n == 0) return 0;
+#define FS_ARG(cond, idx)                                \
+  if (!(cond)) {                                         \
+    set_error("%s: bad argument %d (%s)", fn, idx, #cond); \
+    return -(idx);                                       \
+  }
+  FS_ARG(F != nullptr, 1)
+  FS_ARG(n >= 1 && n <= FC_NMAX, 2)
+  FS_ARG(S >= 1 && S <= FC_SMAX, 3)
+  FS_ARG(ldf >= S, 4)
+  FS_ARG(x != nullptr, 6)
+  FS_ARG(y != nullptr, 7)
+#undef FS_ARG
+  if (ws == nullptr) { set_error("%s: workspace is null", fn); return VGPOSP_E_WS; }
+  const FacWS w = fac_layout(ws, n, S);
+  if (ws_bytes < w.bytes) {
+    set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, w.bytes);
+    return VGPOSP_E_WS;
+  }
+  const SFactor f{F, S, ldf, noise};
+  hipStream_t s = as_stream(stream);
+  if (SQ) {
+    if (int rc = factor_diag_launch(f, n, w.dg, s)) return rc;
+    return factor_symv_sq_launch(f, n, x, y, w, s);
+  }
+  return factor_symv_launch(f, n, x, y, w, nullptr, s);
+}
+
+extern "C" int vgposp_factor_symv(const double* F, int64_t n, int64_t s, int64_t ldf,
+                                  const double* noise, const double* x, double* y, void* ws,
+                                  size_t ws_bytes, void* stream) {
+  return fsymv_entry<false>(__func__, F, n, s, ldf, noise, x, y, ws, ws_bytes, stream);
+}
+
+extern "C" int vgposp_factor_symv_sq(const double* F, int64_t n, int64_t s, int64_t ldf,
+                                     const double* noise, const double* x, double* y, void* ws,
+                                     size_t ws_bytes, void* stream) {
+  return fsymv_entry<true>(__func__, F, n, s, ldf, noise, x, y, ws, ws_bytes, stream);
+}
+
+static CritWS critf_layout(void* base, int64_t n, int64_t S, int kmax) {
+  return crit_layout(base, n, kmax, fac_layout(nullptr, n, S).bytes);
+}
+
+extern "C" size_t vgposp_critf_workspace_bytes(int64_t n, int64_t s, int kmax) {
+  if (n <= 0 || s <= 0 || kmax <= 0) return 0;
+  return critf_layout(nullptr, n, s, kmax).bytes;
+}
+
+extern "C" int vgposp_critf_init(const double* F, int64_t n, int64_t s, int64_t ldf,
+                                 const double* noise, int kmax, int criterion, double threshold,
+                                 const unsigned char* targets, const unsigned char* allowed,
+                                 void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  VG_CHECK_ARG(F != nullptr, 1);
+  VG_CHECK_ARG(n >= 1 && n <= CR_NMAX, 2);
+  VG_CHECK_ARG(s >= 1 && s <= FC_SMAX, 3);
+  VG_CHECK_ARG(ldf >= s, 4);
+  VG_CHECK_ARG(kmax >= 1 && kmax <= n, 6);
+  VG_CHECK_ARG(criterion == VGPOSP_CRIT_VARIANCE || criterion == VGPOSP_CRIT_ENTROPY, 7);
+  VG_CHECK_ARG(threshold >= 0.0, 8);
+  VG_CHECK_ARG(ws != nullptr, 11);
+  const CritWS w = critf_layout(ws, n, s, kmax);
+  VG_CHECK_WS(ws_bytes, w.bytes);
+  return crit_init_run(SFactor{F, s, ldf, noise}, n, criterion, threshold, targets, allowed, w,
+                       as_stream(stream));
+}
+
+extern "C" int vgposp_critf_step(const double* F, int64_t n, int64_t s, int64_t ldf,
+                                 const double* noise, int kmax, int round, const int64_t* forced,
+                                 int64_t j, int64_t* selected, double* sel_delta, void* ws,
+                                 size_t ws_bytes, void* stream) {
+  clear_error();
+  VG_CHECK_ARG(F != nullptr, 1);
+  VG_CHECK_ARG(n >= 1 && n <= CR_NMAX, 2);
+  VG_CHECK_ARG(s >= 1 && s <= FC_SMAX, 3);
+  VG_CHECK_ARG(ldf >= s, 4);
+  VG_CHECK_ARG(kmax >= 1 && kmax <= n, 6);
+  VG_CHECK_ARG(round >= 0 && round < kmax, 7);
+  VG_CHECK_ARG(forced == nullptr || j >= 0, 9);
+  VG_CHECK_ARG(selected != nullptr, 10);
+  VG_CHECK_ARG(ws != nullptr, 12);
+  const CritWS w = critf_layout(ws, n, s, kmax);
+  VG_CHECK_WS(ws_bytes, w.bytes);
+  return crit_step_run(SFactor{F, s, ldf, noise}, n, round, forced, j, selected, sel_delta, w,
+                       as_stream(stream));
+}
+
+extern "C" int vgposp_critf_buffers(void* ws, int64_t n, int64_t s, int kmax, double** nom,
+                                    double** score, double** delta, double** W) {
+  clear_error();
+  VG_CHECK_ARG(ws != nullptr, 1);
+  VG_CHECK_ARG(n >= 1, 2);
+  VG_CHECK_ARG(s >= 1, 3);
+  VG_CHECK_ARG(kmax >= 1, 4);
+  const CritWS w = critf_layout(ws, n, s, kmax);
+  if (nom) *nom = w.nom;
+  if (score) *score = w.s;
+  if (delta) *delta = w.delta;
+  if (W) *W = w.W;
   return 0;
 }

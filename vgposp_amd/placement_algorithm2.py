@@ -380,3 +380,54 @@ def placement_from_points(X, k, kind="eq", amp=1.0, ls=1.0, noise=1e-2, jitter=1
         return g.result()[0]
     g = GreedyPlacement(K, k, candidates=candidates, placed=placed).run(k, lazy=lazy)
     return g.result()[0]
+
+
+def placement_from_samples(samples, k, criterion="variance", noise=0.0, tr_stdev=1.0,
+                           candidates=None, placed=None, targets=None, cov="factored"):
+    """Place k sensors on the empirical covariance of ``samples`` [N locations, S samples] plus
+    diag(``noise``): the reference's placement covariance (tfp.stats.covariance of the tracer
+    samples for every pair of locations, main.py:190-199).
+
+    ``cov``: ``"factored"`` (the default) never forms the N x N matrix and runs the rounds on the
+    centred samples themselves (placement_criteria.FactoredCovariance.from_samples): N S doubles
+    on the device instead of N^2.  It is for ``"variance"`` and ``"entropy"``.  ``"dense"``
+    assembles ``covariance.empirical_cov(samples) + diag(noise)`` and runs the existing paths,
+    ``"mi"`` included.  ``noise`` is a scalar or [N], ``targets`` belongs to ``"variance"``."""
+    if cov not in ("dense", "factored"):
+        raise ValueError(f"unknown cov {cov!r}; expected 'dense' or 'factored'")
+    if criterion == "mi":
+        if cov == "factored":
+            raise ValueError("cov='factored' applies to criterion='variance' and 'entropy': the "
+                             "mutual-information placement factors the stored Sigma (on a factor "
+                             "it needs a Woodbury form that is not built); use cov='dense'")
+        if targets is not None:
+            raise ValueError("targets apply to criterion='variance'; the mutual-information "
+                             "placement has no target set")
+    else:
+        from .placement_criteria import CRITERIA
+        if criterion not in CRITERIA:
+            raise ValueError(f"unknown criterion {criterion!r}; expected 'mi' or one of "
+                             f"{list(CRITERIA)}")
+    from .placement_criteria import CriterionPlacement, FactoredCovariance
+    if cov == "factored":
+        fac = FactoredCovariance.from_samples(samples, noise=noise, tr_stdev=tr_stdev)
+        if k < 1:
+            normalize_constraints(fac.N, max(int(k), 0), candidates, placed)
+            return []
+        g = CriterionPlacement(fac, k, criterion, candidates=candidates, placed=placed,
+                               targets=targets).run(k)
+        return g.result()[0]
+    from .covariance import empirical_cov
+    N = int(np.shape(samples)[0])
+    nv = FactoredCovariance._noise_vector(noise, N)
+    Sigma = empirical_cov(samples, tr_stdev=tr_stdev)
+    if nv is not None:
+        torch.diagonal(Sigma).add_(linalg.as_device(nv))
+    if criterion == "mi":
+        return _place(Sigma, k, True, False, None, candidates, placed)
+    if k < 1:
+        normalize_constraints(N, max(int(k), 0), candidates, placed)
+        return []
+    g = CriterionPlacement(Sigma, k, criterion, candidates=candidates, placed=placed,
+                           targets=targets).run(k)
+    return g.result()[0]

@@ -35,6 +35,12 @@ the place of ``cov_vv`` is Sigma = diag(a) K(X, X) diag(a) + diag(noise), genera
 in every pass (``vgposp_kernel_symv``) and in the one column a round reads, so the device holds
 N (d + 2) doubles instead of N^2.  With ``CrossKernel.from_site`` beside it nothing of size N^2 or
 P N is held at all.
+
+A covariance estimated from samples: a ``FactoredCovariance(F, noise=0.0)`` in the place of
+``cov_vv`` is Sigma = F F^T + diag(noise); ``FactoredCovariance.from_samples(samples)`` is the
+reference's empirical covariance of S samples per location (``covariance.empirical_cov``) without
+the N x N matrix.  A pass is two streams over F (``vgposp_factor_symv``), the column of a round one,
+so the device holds N S doubles instead of N^2.
 """
 from __future__ import annotations
 
@@ -135,6 +141,81 @@ class SiteKernel:
         """(kind, X, N, d, amp, ls, site_scale, diag) as the vgposp_critg_* entries take them."""
         return (self.kind, _p(self.X), self.N, self.d, _p(self.amp), _p(self.ls), _p(self.scale),
                 _p(self.diag))
+
+
+class FactoredCovariance:
+    """A covariance given by a factor and never stored: Sigma = F F^T + diag(noise), F [N, S] with
+    1 <= S <= 4096.  A device float64 ``F`` with unit column stride (a view with a row pitch
+    included) is used where it lies and only read; anything else is copied to the device.
+    ``noise`` (a scalar or [N]) is finite and not negative.  It goes where ``cov_vv`` goes in
+    ``CriterionPlacement`` and the placement functions.  The device holds N S doubles instead of
+    N^2."""
+
+    S_MAX = 4096
+
+    def __init__(self, F, noise=0.0):
+        on_device = isinstance(F, torch.Tensor) and F.device.type == "cuda"
+        self._F = F if on_device else np.asarray(
+            F.detach().cpu().numpy() if isinstance(F, torch.Tensor) else F, dtype=np.float64)
+        shape = tuple(self._F.shape)
+        if len(shape) != 2 or shape[0] < 1:
+            raise ValueError(f"F must be [N, S] with N >= 1, got {shape}")
+        self.N, self.S = int(shape[0]), int(shape[1])
+        if not 1 <= self.S <= self.S_MAX:
+            raise ValueError(f"F must have 1 <= S <= {self.S_MAX} columns, got {self.S}")
+        self._noise = self._noise_vector(noise, self.N)
+        self._uploaded = False
+
+    @staticmethod
+    def _noise_vector(noise, N):
+        """-> host float64 [N], or None when it is zero everywhere."""
+        if np.ndim(noise) == 0:
+            noise = np.full(N, float(noise))
+        noise = _host_vector("noise", noise, N)
+        if not np.isfinite(noise).all() or (noise < 0.0).any():
+            raise ValueError("noise must be finite and not negative")
+        return noise if noise.any() else None
+
+    def _upload(self):
+        # on first use, so that the arguments are validated without a device
+        if not self._uploaded:
+            self._F = _device_matrix(self._F)
+            self._noise = None if self._noise is None else linalg.as_device(self._noise)
+            self._uploaded = True
+
+    @property
+    def F(self):
+        """The factor on the device, [N, S] float64 with unit column stride."""
+        self._upload()
+        return self._F
+
+    @property
+    def noise(self):
+        """The noise on the device, [N] float64, or None when it is zero everywhere."""
+        self._upload()
+        return self._noise
+
+    @classmethod
+    def from_samples(cls, samples, noise=0.0, tr_stdev=1.0):
+        """The empirical covariance of ``samples`` [N locations, S samples] (+ diag(noise)):
+        F = (samples - their mean per location) / (tr_stdev sqrt(S)), so that F F^T equals
+        ``covariance.empirical_cov(samples, tr_stdev=tr_stdev)`` (biased, centred on the sample
+        mean).  The samples are copied, then centred in place."""
+        from .covariance import center_rows_
+        shape = tuple(np.shape(samples))
+        if len(shape) != 2 or shape[0] < 1 or not 1 <= shape[1] <= cls.S_MAX:
+            raise ValueError(f"samples must be [N, S] with N >= 1 and 1 <= S <= {cls.S_MAX}, got "
+                             f"{shape}")
+        if not (np.ndim(tr_stdev) == 0 and np.isfinite(float(tr_stdev)) and float(tr_stdev) > 0.0):
+            raise ValueError(f"tr_stdev must be a finite, positive scalar, got {tr_stdev!r}")
+        cls._noise_vector(noise, shape[0])
+        T = linalg.as_device(samples).clone()
+        center_rows_(T, 1.0 / (float(tr_stdev) * float(np.sqrt(shape[1]))))
+        return cls(T, noise)
+
+    def args(self):
+        """(F, N, S, ldf, noise) as the vgposp_critf_* entries take them."""
+        return _p(self.F), self.N, self.S, self.F.stride(0), _p(self.noise)
 
 
 class CrossKernel:
@@ -262,6 +343,9 @@ class CriterionPlacement:
     ``Sigma`` may be a ``SiteKernel`` instead of a matrix: the same rounds on a covariance
     generated from the points.  ``diag`` and ``cross_cov`` do not combine with it, and a
     ``cross_kernel`` must describe the same field (``CrossKernel.from_site``).
+
+    ``Sigma`` may be a ``FactoredCovariance``: the same rounds on Sigma = F F^T + diag(noise).
+    ``diag``, ``cross_cov`` and ``cross_kernel`` do not combine with it.
     """
 
     def __init__(self, Sigma, kmax, criterion="variance", candidates=None, placed=None,
@@ -270,7 +354,18 @@ class CriterionPlacement:
         self.criterion = criterion
         self.crit = _criterion_id(criterion)
         self.site = Sigma if isinstance(Sigma, SiteKernel) else None
-        if self.site is not None:
+        self.fac = Sigma if isinstance(Sigma, FactoredCovariance) else None
+        if self.fac is not None:
+            for name, arg in (("diag", diag), ("cross_cov", cross_cov),
+                              ("cross_kernel", cross_kernel)):
+                if arg is not None:
+                    raise ValueError(f"{name} and a FactoredCovariance exclude each other: the "
+                                     "factor is the whole covariance, and targets outside V "
+                                     "from samples are not supported")
+            S = None
+            self.N = self.n = self.fac.N
+            dev = self.fac.F.device
+        elif self.site is not None:
             if diag is not None:
                 raise ValueError("diag and a SiteKernel exclude each other: the SiteKernel holds "
                                  "the diagonal")
@@ -330,14 +425,19 @@ class CriterionPlacement:
         self._allowed_dev, self._targets_dev = mask(self.allowed), mask(self.targets)
         self._placed_dev = (torch.as_tensor(self.placed, dtype=torch.int64, device=dev)
                             if self.m else None)
-        # the entry family: crit / critx / critk on a stored Sigma, critg / critgk on a SiteKernel
-        if self.site is not None:
+        # the entry family: crit / critx / critk on a stored Sigma, critg / critgk on a SiteKernel,
+        # critf on a FactoredCovariance
+        if self.fac is not None:
+            self._family = "vgposp_critf"
+        elif self.site is not None:
             self._family = "vgposp_critg" if self.gen is None else "vgposp_critgk"
         elif self.gen is not None:
             self._family = "vgposp_critk"
         else:
             self._family = "vgposp_crit" if self.R is None else "vgposp_critx"
         sizes = (self.n, self.kmax) if self.P == 0 else (self.n, self.P, self.kmax)
+        if self.fac is not None:
+            sizes = (self.n, self.fac.S, self.kmax)
         self.ws = linalg.workspace(query(self._family + "_workspace_bytes", *sizes))
         self.selected = torch.full((self.kmax,), -1, dtype=torch.int64, device=dev)
         self.sel_delta = torch.zeros(self.kmax, dtype=torch.float64, device=dev)
@@ -352,7 +452,9 @@ class CriterionPlacement:
     def _step(self, r, forced=None, j=0):
         tail = (r, _p(forced), j, _p(self.selected), _p(self.sel_delta), _p(self.ws),
                 self.ws.numel(), _stream())
-        if self.site is not None and self.gen is None:
+        if self.fac is not None:
+            call("vgposp_critf_step", *self.fac.args(), self.kmax, *tail)
+        elif self.site is not None and self.gen is None:
             call("vgposp_critg_step", *self.site.args(), self.kmax, *tail)
         elif self.site is not None:
             call("vgposp_critgk_step", self.n, _p(self.site.diag), *self.gen.args(), self.kmax,
@@ -365,7 +467,11 @@ class CriterionPlacement:
             call("vgposp_critx_step", *self._sigma_args(), *self._cross_args(), self.kmax, *tail)
 
     def init(self):
-        if self.site is not None and self.gen is None:
+        if self.fac is not None:
+            call("vgposp_critf_init", *self.fac.args(), self.kmax, self.crit, self.threshold,
+                 _p(self._targets_dev), _p(self._allowed_dev), _p(self.ws), self.ws.numel(),
+                 _stream())
+        elif self.site is not None and self.gen is None:
             call("vgposp_critg_init", *self.site.args(), self.kmax, self.crit, self.threshold,
                  _p(self._targets_dev), _p(self._allowed_dev), _p(self.ws), self.ws.numel(),
                  _stream())
@@ -410,7 +516,10 @@ class CriterionPlacement:
         [placed + rounds, P]."""
         cross = self.R is not None or self.gen is not None
         ptr = [ctypes.c_void_p() for _ in range(5 if cross else 4)]
-        if not cross:
+        if self.fac is not None:
+            call(self._family + "_buffers", _p(self.ws), self.n, self.fac.S, self.kmax,
+                 *map(ctypes.byref, ptr))
+        elif not cross:
             call(self._family + "_buffers", _p(self.ws), self.n, self.kmax,
                  *map(ctypes.byref, ptr))
         else:
@@ -448,7 +557,12 @@ class CriterionPlacement:
 def _place(cov_vv, k, criterion, candidates, placed, targets, cross_cov=None,
            target_weights=None, cross_kernel=None):
     if k < 1:
-        N = cov_vv.N if isinstance(cov_vv, SiteKernel) else int(np.shape(cov_vv)[0])
+        N = (cov_vv.N if isinstance(cov_vv, (SiteKernel, FactoredCovariance))
+             else int(np.shape(cov_vv)[0]))
+        if isinstance(cov_vv, FactoredCovariance) and (cross_cov is not None
+                                                       or cross_kernel is not None):
+            raise ValueError("cross_cov / cross_kernel and a FactoredCovariance exclude each "
+                             "other: targets outside V from samples are not supported")
         normalize_constraints(N, max(int(k), 0), candidates, placed)
         normalize_targets(N, targets)
         check_cross_arguments(criterion, targets, cross_cov, target_weights, cross_kernel)
