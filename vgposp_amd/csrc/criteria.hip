@@ -28,9 +28,16 @@
 //
 // Sigma need not be stored: for Sigma = diag(a) K(X, X) diag(a) + a diagonal vector the same
 // rounds run with every entry generated from the points (SGen, ksymv_kernel, the critg / critgk
-// entries); the host sequences of the rounds are written once, against where Sigma comes from.
-// The third source is a factor: Sigma = F F^T + diag(noise) with F [n][S] the centred samples of an
-// empirical covariance (SFactor, the critf entries): a pass is two tall-skinny streams over F.
+// entries).  The third source is a factor: Sigma = F F^T + diag(noise) with F [n][S] the centred
+// samples of an empirical covariance (SFactor, the critf entries): a pass is two tall-skinny
+// streams over F.  The targets may lie outside V, with their cross-covariance R stored
+// (CrossStored) or generated (KGen).
+//
+// The host side is written once: one start (crit_init_run) and one round (crit_step_run), both
+// templates on where Sigma comes from (SigmaStored, SGen, SFactor) and on where the targets are
+// (InV, CrossStored, KGen); every _init and _step entry of the six families checks its argument
+// groups (check_sigma, check_cross, check_rule, check_round), lays out its workspace and calls
+// them.
 #include <algorithm>
 #include <cfloat>
 #include <type_traits>
@@ -637,17 +644,26 @@ __global__ __launch_bounds__(SY_TH) void kgemv_t_kernel(KGen g, int64_t P, int64
   if (in1) out[c + 1] = u0 + u1;
 }
 
-template <int KIND, bool SQ>
-static void kgemv_t_launch_kind(const KGen& g, int64_t P, int64_t n, const double* x, double* part,
-                                const double* gate, hipStream_t s) {
-  const dim3 grid((unsigned)ceil_div(n, SY_T), (unsigned)ceil_div(P, KG_ROWS));
-#define KG_CASE(DD, DT)                                                                          \
-  case DD:                                                                                       \
-    hipLaunchKernelGGL((kgemv_t_kernel<KIND, DT, SQ>), grid, dim3(SY_TH), 0, s, g, P, n, x, part, \
-                       gate);                                                                    \
-    break;
-  switch (g.d) { KG_CASE(1, 1) KG_CASE(2, 2) KG_CASE(3, 3) default: KG_CASE(0, 0) }
-#undef KG_CASE
+// f(kind) with the kernel kind as a compile-time constant: every generated entry is a kentry<KIND>.
+template <class F>
+static void with_kind(int kind, F&& f) {
+  switch (kind) {
+    case VGPOSP_KERNEL_EQ: f(std::integral_constant<int, VGPOSP_KERNEL_EQ>{}); break;
+    case VGPOSP_KERNEL_MATERN12: f(std::integral_constant<int, VGPOSP_KERNEL_MATERN12>{}); break;
+    case VGPOSP_KERNEL_MATERN32: f(std::integral_constant<int, VGPOSP_KERNEL_MATERN32>{}); break;
+    default: f(std::integral_constant<int, VGPOSP_KERNEL_MATERN52>{}); break;
+  }
+}
+
+// f(D) for the passes' dimension: 1, 2, 3 unrolled, 0 for the run-time loop over 4 .. 8.
+template <class F>
+static void with_dim(int d, F&& f) {
+  switch (d) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 0>{}); break;
+  }
 }
 
 // y_j = a_s[j]^p sum_v x_v a_t[v]^p k(Xt_v, X_j)^p: the pass, then gemv_t's reduction of the
@@ -659,12 +675,13 @@ static void kgemv_t_launch(const KGen& g, int64_t P, int64_t n, const double* x,
     const double pn = (double)P * (double)n;
     ProfScope ps(SQ ? "criteria_kgemv_t_sq" : "criteria_kgemv_t", s, (3.0 * g.d + 32.0) * pn,
                  8.0 * (double)(P + n) * (g.d + 1));
-    switch (g.kind) {
-      case VGPOSP_KERNEL_EQ: kgemv_t_launch_kind<VGPOSP_KERNEL_EQ, SQ>(g, P, n, x, part, gate, s); break;
-      case VGPOSP_KERNEL_MATERN12: kgemv_t_launch_kind<VGPOSP_KERNEL_MATERN12, SQ>(g, P, n, x, part, gate, s); break;
-      case VGPOSP_KERNEL_MATERN32: kgemv_t_launch_kind<VGPOSP_KERNEL_MATERN32, SQ>(g, P, n, x, part, gate, s); break;
-      default: kgemv_t_launch_kind<VGPOSP_KERNEL_MATERN52, SQ>(g, P, n, x, part, gate, s); break;
-    }
+    const dim3 grid((unsigned)ceil_div(n, SY_T), (unsigned)ceil_div(P, KG_ROWS));
+    with_kind(g.kind, [&](auto kind) {
+      with_dim(g.d, [&](auto dim) {
+        hipLaunchKernelGGL((kgemv_t_kernel<decltype(kind)::value, decltype(dim)::value, SQ>), grid,
+                           dim3(SY_TH), 0, s, g, P, n, x, part, gate);
+      });
+    });
   }
   hipLaunchKernelGGL(gemv_t_reduce_kernel, dim3((unsigned)ceil_div(n, CR_B)), dim3(CR_B), 0, s,
                      ceil_div(P, KG_ROWS), n, part, y, gate, g.as, SQ ? 1 : 0);
@@ -697,13 +714,10 @@ __global__ __launch_bounds__(CR_B) void critk_urow_kernel(KGen g, int64_t P,
 
 static void critk_urow_launch(const KGen& g, int64_t P, const int64_t* selected, int round,
                               const CritXWS& w, hipStream_t s) {
-  const dim3 grid((unsigned)ceil_div(P, CR_B));
-  switch (g.kind) {
-    case VGPOSP_KERNEL_EQ: hipLaunchKernelGGL(critk_urow_kernel<VGPOSP_KERNEL_EQ>, grid, dim3(CR_B), 0, s, g, P, selected, round, w); break;
-    case VGPOSP_KERNEL_MATERN12: hipLaunchKernelGGL(critk_urow_kernel<VGPOSP_KERNEL_MATERN12>, grid, dim3(CR_B), 0, s, g, P, selected, round, w); break;
-    case VGPOSP_KERNEL_MATERN32: hipLaunchKernelGGL(critk_urow_kernel<VGPOSP_KERNEL_MATERN32>, grid, dim3(CR_B), 0, s, g, P, selected, round, w); break;
-    default: hipLaunchKernelGGL(critk_urow_kernel<VGPOSP_KERNEL_MATERN52>, grid, dim3(CR_B), 0, s, g, P, selected, round, w); break;
-  }
+  with_kind(g.kind, [&](auto kind) {
+    hipLaunchKernelGGL(critk_urow_kernel<decltype(kind)::value>, dim3((unsigned)ceil_div(P, CR_B)),
+                       dim3(CR_B), 0, s, g, P, selected, round, w);
+  });
 }
 
 // ---- Sigma generated from the points: Sigma = diag(a) K(X, X) diag(a) off the diagonal ----
@@ -720,16 +734,6 @@ __device__ __forceinline__ double sgen_diag(const SGen& g, int64_t i) {
   if (g.diag) return g.diag[i];
   const double a = g.a ? g.a[i] : 1.0, amp = g.amp[0];
   return (a * a) * (amp * amp);
-}
-
-template <class F>
-static void with_kind(int kind, F&& f) {
-  switch (kind) {
-    case VGPOSP_KERNEL_EQ: f(std::integral_constant<int, VGPOSP_KERNEL_EQ>{}); break;
-    case VGPOSP_KERNEL_MATERN12: f(std::integral_constant<int, VGPOSP_KERNEL_MATERN12>{}); break;
-    case VGPOSP_KERNEL_MATERN32: f(std::integral_constant<int, VGPOSP_KERNEL_MATERN32>{}); break;
-    default: f(std::integral_constant<int, VGPOSP_KERNEL_MATERN52>{}); break;
-  }
 }
 
 // A workgroup owns a block of G x G 512-tiles on or above the diagonal, so the partials are one per
@@ -980,17 +984,10 @@ static void ksymv_launch(const SGen& g, int64_t n, const double* x, double* y, c
     const dim3 grid((unsigned)w.ng, (unsigned)w.ng);
     const size_t lds = (size_t)w.G * SY_T * 8;
     with_kind(g.kind, [&](auto kind) {
-      constexpr int KIND = decltype(kind)::value;
-#define KS_CASE(DD)                                                                             \
-  hipLaunchKernelGGL((ksymv_kernel<KIND, DD, SQ>), grid, dim3(SY_TH), lds, s, g, n, x, w, gate); \
-  break;
-      switch (g.d) {
-        case 1: KS_CASE(1)
-        case 2: KS_CASE(2)
-        case 3: KS_CASE(3)
-        default: KS_CASE(0)
-      }
-#undef KS_CASE
+      with_dim(g.d, [&](auto dim) {
+        hipLaunchKernelGGL((ksymv_kernel<decltype(kind)::value, decltype(dim)::value, SQ>), grid,
+                           dim3(SY_TH), lds, s, g, n, x, w, gate);
+      });
     });
   }
   hipLaunchKernelGGL(ksymv_reduce_kernel, dim3((unsigned)ceil_div(n, CR_B)), dim3(CR_B), 0, s, g, n,
@@ -1408,6 +1405,8 @@ static int factor_symv_sq_launch(const SFactor& f, int64_t n, const double* x, d
 }
 
 // ---- where Sigma comes from: what the host sequences of the rounds are written against ----
+// A source of Sigma is SigmaStored, SGen or SFactor with the overloads sigma_init (nom, the masks
+// and prm), sigma_row (step 1) and sigma_pass<SQ> (y = Sigma x on the workspace's pass area).
 struct SigmaStored {
   const double* S;
   int64_t lda;
@@ -1476,106 +1475,259 @@ static int sigma_pass(const SFactor& sg, int64_t n, const double* x, double* y, 
   return factor_symv_launch(sg, n, x, y, fw, gate, s);
 }
 
-// The in-V rule, after the entry has checked its arguments and laid out w.
-template <class Sigma>
-static int crit_init_run(const Sigma& sg, int64_t n, int criterion, double threshold,
-                         const unsigned char* targets, const unsigned char* allowed,
-                         const CritWS& w, hipStream_t s) {
-  sigma_init(sg, n, criterion, threshold, targets, allowed, w, s);
-  VG_LAUNCH_CHECK();
-  if (criterion == VGPOSP_CRIT_VARIANCE) {  // s_y = sum_v t_v Sigma_vy^2
-    if (int rc = sigma_pass<true>(sg, n, w.tvec, w.s, w.symv, nullptr, s)) return rc;
+// ---- where the targets are: the other thing the sequences are written against ----
+// InV: the targets are locations (the 0/1 mask t), the workspace is a CritWS, the dots run over n
+// on it and the pass of a round is sigma_pass.  Otherwise the targets lie outside V, the workspace
+// is a CritXWS, and a source of R, CrossStored or KGen, has the overloads cross_pass<SQ>
+// (y = R^T x on w.gemv), cross_urow (step 2) and cross_row_doubles (what the u-row reads and
+// writes per target beside the rows of U, for criteria_row's byte model).
+struct InV {};
+struct CrossStored {
+  const double* R;
+  int64_t ldr;
+};
+
+template <bool SQ>
+static void cross_pass(const CrossStored& c, int64_t P, int64_t n, const double* x, double* y,
+                       const CritXWS& w, const double* gate, hipStream_t s) {
+  gemv_t_launch<SQ>(c.R, P, n, c.ldr, x, y, w.gemv, gate, s);
+}
+template <bool SQ>
+static void cross_pass(const KGen& g, int64_t P, int64_t n, const double* x, double* y,
+                       const CritXWS& w, const double* gate, hipStream_t s) {
+  kgemv_t_launch<SQ>(g, P, n, x, y, w.gemv, gate, s);
+}
+
+static void cross_urow(const CrossStored& c, int64_t P, const int64_t* selected, int round,
+                       const CritXWS& w, hipStream_t s) {
+  hipLaunchKernelGGL(critx_urow_kernel, dim3((unsigned)ceil_div(P, CR_B)), dim3(CR_B), 0, s, c.R,
+                     P, c.ldr, selected, round, w);
+}
+static void cross_urow(const KGen& g, int64_t P, const int64_t* selected, int round,
+                       const CritXWS& w, hipStream_t s) {
+  critk_urow_launch(g, P, selected, round, w, s);
+}
+
+static int cross_row_doubles(const CrossStored&) { return 4; }
+static int cross_row_doubles(const KGen& g) { return 4 + g.d; }
+
+static const CritWS& location_side(const CritWS& w) { return w; }
+static const CritWS& location_side(const CritXWS& w) { return w.c; }
+
+// The rule's start, after the entry has checked its arguments and laid out w (a CritWS for InV, a
+// CritXWS otherwise; P, weights: the target side's, unused for InV; the cross families run the
+// variance rule without a mask).
+template <class Sigma, class Cross, class WS>
+static int crit_init_run(const Sigma& sg, const Cross& cr, int64_t n, int64_t P, int criterion,
+                         double threshold, const unsigned char* targets, const double* weights,
+                         const unsigned char* allowed, const WS& w, hipStream_t s) {
+  const CritWS& c = location_side(w);
+  sigma_init(sg, n, criterion, threshold, targets, allowed, c, s);
+  if constexpr (std::is_same<Cross, InV>::value) {
+    VG_LAUNCH_CHECK();
+    if (criterion == VGPOSP_CRIT_VARIANCE) {  // s_y = sum_v t_v Sigma_vy^2
+      if (int rc = sigma_pass<true>(sg, n, c.tvec, c.s, c.symv, nullptr, s)) return rc;
+      VG_LAUNCH_CHECK();
+    }
+  } else {
+    hipLaunchKernelGGL(critx_init_kernel, dim3((unsigned)ceil_div(P, 256)), dim3(256), 0, s, P,
+                       weights, w);
+    VG_LAUNCH_CHECK();
+    // s_y = sum_v omega_v R_vy^2
+    cross_pass<true>(cr, P, n, w.omega, c.s, w, nullptr, s);
     VG_LAUNCH_CHECK();
   }
   return 0;
 }
 
-template <class Sigma>
-static int crit_step_run(const Sigma& sg, int64_t n, int round, const int64_t* forced, int64_t j,
-                         int64_t* selected, double* sel_delta, const CritWS& w, hipStream_t s) {
+// One round.  The three places where the families differ: where the column of R comes from
+// (cross_urow; none for InV, whose w-row is its u-row), over which side the dots run, and which
+// pass fills g.
+template <class Sigma, class Cross, class WS>
+static int crit_step_run(const Sigma& sg, const Cross& cr, int64_t n, int64_t P, int round,
+                         const int64_t* forced, int64_t j, int64_t* selected, double* sel_delta,
+                         const WS& w, hipStream_t s) {
+  constexpr bool in_v = std::is_same<Cross, InV>::value;
+  const CritWS& c = location_side(w);
   const unsigned nb = (unsigned)ceil_div(n, CR_B);
   {
     ProfScope ps("criteria_select", s, 0.0, 8.0 * 3.0 * n);
     hipLaunchKernelGGL(crit_score_kernel, dim3((unsigned)ceil_div(n, CR_CH)), dim3(CR_CH), 0, s, n,
-                       w);
+                       c);
     hipLaunchKernelGGL(crit_select_kernel, dim3(1), dim3(CR_CH), 0, s, n, round, forced, j,
-                       selected, sel_delta, w);
+                       selected, sel_delta, c);
     VG_LAUNCH_CHECK();
   }
+  double row_doubles = (double)n * (5 + round);
+  if constexpr (!in_v) row_doubles += (double)P * (cross_row_doubles(cr) + round);
   {
-    ProfScope ps("criteria_row", s, 0.0, 8.0 * (double)n * (5 + round));
-    sigma_row(sg, n, selected, round, w, s);
+    ProfScope ps("criteria_row", s, 0.0, 8.0 * row_doubles);
+    sigma_row(sg, n, selected, round, c, s);
+    if constexpr (!in_v) cross_urow(cr, P, selected, round, w, s);
     VG_LAUNCH_CHECK();
   }
-  // the variance rule's part: every kernel below returns at once under the entropy rule (the
-  // criterion lives in the workspace, so the launch sequence does not depend on it)
-  const double* gate = w.prm + 1;
-  hipLaunchKernelGGL(crit_dots_kernel, dim3(nb, (unsigned)round + 1), dim3(CR_B), 0, s, n,
-                     selected, round, w);
-  hipLaunchKernelGGL(crit_fold_kernel, dim3((unsigned)round + 1), dim3(CR_B), 0, s, (int64_t)nb,
-                     selected, round, w);
+  // The variance rule's part: every kernel below returns at once under the entropy rule (the
+  // criterion lives in the workspace, so the launch sequence does not depend on it).
+  // dot[t] = W_t . (w.t) over n, or U_t . (omega.u) over P on the target side's view, for
+  // t <= round (t = round: |w.t|^2, or sum_v omega_v u_v^2)
+  const double* gate = c.prm + 1;
+  CritWS tv = c;
+  int64_t nt = n;
+  if constexpr (!in_v) {
+    tv = critx_target_view(w);
+    nt = P;
+  }
+  const unsigned nbt = (unsigned)ceil_div(nt, CR_B);
+  hipLaunchKernelGGL(crit_dots_kernel, dim3(nbt, (unsigned)round + 1), dim3(CR_B), 0, s, nt,
+                     selected, round, tv);
+  hipLaunchKernelGGL(crit_fold_kernel, dim3((unsigned)round + 1), dim3(CR_B), 0, s, (int64_t)nbt,
+                     selected, round, tv);
   VG_LAUNCH_CHECK();
-  if (int rc = sigma_pass<false>(sg, n, w.wt, w.g, w.symv, gate, s)) return rc;
+  if constexpr (in_v) {
+    if (int rc = sigma_pass<false>(sg, n, c.wt, c.g, c.symv, gate, s)) return rc;
+  } else {
+    cross_pass<false>(cr, P, n, w.wu, c.g, w, gate, s);
+  }
   VG_LAUNCH_CHECK();
   {
     ProfScope ps("criteria_update", s, 0.0, 8.0 * (double)n * (4 + round));
-    hipLaunchKernelGGL(crit_update_kernel, dim3(nb), dim3(CR_B), 0, s, n, selected, round, w);
+    hipLaunchKernelGGL(crit_update_kernel, dim3(nb), dim3(CR_B), 0, s, n, selected, round, c);
     VG_LAUNCH_CHECK();
   }
   return 0;
 }
 
-// The rule on a generated R, after the entry has checked its arguments and laid out w.
-template <class Sigma>
-static int critk_init_run(const Sigma& sg, const KGen& g, int64_t n, int64_t P,
-                          const double* weights, double threshold, const unsigned char* allowed,
-                          const CritXWS& w, hipStream_t s) {
-  sigma_init(sg, n, VGPOSP_CRIT_VARIANCE, threshold, nullptr, allowed, w.c, s);
-  hipLaunchKernelGGL(critx_init_kernel, dim3((unsigned)ceil_div(P, 256)), dim3(256), 0, s, P,
-                     weights, w);
-  VG_LAUNCH_CHECK();
-  // s_y = sum_v omega_v R_vy^2
-  kgemv_t_launch<true>(g, P, n, w.omega, w.c.s, w.gemv, nullptr, s);
-  VG_LAUNCH_CHECK();
+// ---- the entries' argument checks, one per group of arguments ----
+// VG_CHECK_ARG for a check that entries share: `fn` is the entry's name (a helper's __func__ is
+// not), `at` the position of the group's first argument in that entry.
+#define CR_ARG(cond, idx)                                    \
+  do {                                                       \
+    if (!(cond)) {                                           \
+      set_error("%s: bad argument %d (%s)", fn, (idx), #cond); \
+      return -(idx);                                         \
+    }                                                        \
+  } while (0)
+#define CR_TRY(expr)                     \
+  do {                                   \
+    if (int rc_ = (expr)) return rc_;    \
+  } while (0)
+
+// (Sigma, n, lda, diag)
+static int check_sigma(const char* fn, int at, const SigmaStored& sg, int64_t n) {
+  CR_ARG(sg.S != nullptr, at);
+  CR_ARG(n >= 1 && n <= CR_NMAX, at + 1);
+  CR_ARG(sg.lda >= n, at + 2);
+  return 0;
+}
+// (kind, X, n, d, amp, ls, site_scale, diag)
+static int check_sigma(const char* fn, int at, const SGen& g, int64_t n) {
+  CR_ARG(g.kind >= VGPOSP_KERNEL_EQ && g.kind <= VGPOSP_KERNEL_MATERN52, at);
+  CR_ARG(g.X != nullptr, at + 1);
+  CR_ARG(n >= 1 && n <= CR_NMAX, at + 2);
+  CR_ARG(g.d >= 1 && g.d <= 8, at + 3);
+  CR_ARG(g.amp != nullptr, at + 4);
+  CR_ARG(g.ls != nullptr, at + 5);
+  return 0;
+}
+// (F, n, s, ldf, noise); nmax: the passes alone go beyond the rounds' CR_NMAX
+static int check_sigma(const char* fn, int at, const SFactor& f, int64_t n,
+                       int64_t nmax = CR_NMAX) {
+  CR_ARG(f.F != nullptr, at);
+  CR_ARG(n >= 1 && n <= nmax, at + 1);
+  CR_ARG(f.S >= 1 && f.S <= FC_SMAX, at + 2);
+  CR_ARG(f.ldf >= f.S, at + 3);
   return 0;
 }
 
-template <class Sigma>
-static int critk_step_run(const Sigma& sg, const KGen& g, int64_t n, int64_t P, int round,
-                          const int64_t* forced, int64_t j, int64_t* selected, double* sel_delta,
-                          const CritXWS& w, hipStream_t s) {
-  const CritWS tv = critx_target_view(w);
-  const int d = g.d;
-  const unsigned nb = (unsigned)ceil_div(n, CR_B), nbp = (unsigned)ceil_div(P, CR_B);
-  {
-    ProfScope ps("criteria_select", s, 0.0, 8.0 * 3.0 * n);
-    hipLaunchKernelGGL(crit_score_kernel, dim3((unsigned)ceil_div(n, CR_CH)), dim3(CR_CH), 0, s, n,
-                       w.c);
-    hipLaunchKernelGGL(crit_select_kernel, dim3(1), dim3(CR_CH), 0, s, n, round, forced, j,
-                       selected, sel_delta, w.c);
-    VG_LAUNCH_CHECK();
+// (R, P, ldr), and (kind, Xt, P, X, d, amp, ls, target_scale, site_scale).  with_n: the pass
+// entries have no Sigma group and carry n inside this one, after P (stored) or after X (generated).
+static int check_cross(const char* fn, int at, const CrossStored& c, int64_t P, int64_t n,
+                       bool with_n = false) {
+  CR_ARG(c.R != nullptr, at);
+  CR_ARG(P >= 1 && P <= CRX_PMAX, at + 1);
+  if (with_n) {
+    CR_ARG(n >= 1 && n <= CR_NMAX, at + 2);
+    ++at;
   }
-  {
-    ProfScope ps("criteria_row", s, 0.0,
-                 8.0 * ((double)n * (5 + round) + (double)P * (4 + d + round)));
-    sigma_row(sg, n, selected, round, w.c, s);
-    critk_urow_launch(g, P, selected, round, w, s);
-    VG_LAUNCH_CHECK();
+  CR_ARG(c.ldr >= n, at + 2);
+  return 0;
+}
+static int check_cross(const char* fn, int at, const KGen& g, int64_t P, int64_t n,
+                       bool with_n = false) {
+  CR_ARG(g.kind >= VGPOSP_KERNEL_EQ && g.kind <= VGPOSP_KERNEL_MATERN52, at);
+  CR_ARG(g.Xt != nullptr, at + 1);
+  CR_ARG(P >= 1 && P <= CRX_PMAX, at + 2);
+  CR_ARG(g.X != nullptr, at + 3);
+  if (with_n) {
+    CR_ARG(n >= 1 && n <= CR_NMAX, at + 4);
+    ++at;
   }
-  // dot[t] = U_t . (omega.u) for t <= round (t = round: sum_v omega_v u_v^2), over P
-  hipLaunchKernelGGL(crit_dots_kernel, dim3(nbp, (unsigned)round + 1), dim3(CR_B), 0, s, P,
-                     selected, round, tv);
-  hipLaunchKernelGGL(crit_fold_kernel, dim3((unsigned)round + 1), dim3(CR_B), 0, s, (int64_t)nbp,
-                     selected, round, tv);
-  VG_LAUNCH_CHECK();
-  kgemv_t_launch<false>(g, P, n, w.wu, w.c.g, w.gemv, w.c.prm + 1, s);
-  VG_LAUNCH_CHECK();
-  {
-    ProfScope ps("criteria_update", s, 0.0, 8.0 * (double)n * (4 + round));
-    hipLaunchKernelGGL(crit_update_kernel, dim3(nb), dim3(CR_B), 0, s, n, selected, round, w.c);
-    VG_LAUNCH_CHECK();
+  CR_ARG(g.d >= 1 && g.d <= 8, at + 4);
+  CR_ARG(g.amp != nullptr, at + 5);
+  CR_ARG(g.ls != nullptr, at + 6);
+  return 0;
+}
+
+// (kmax, criterion, threshold) of an in-V init; the cross inits have (kmax, threshold):
+// criterion == nullptr
+static int check_rule(const char* fn, int at, int kmax, int64_t n, const int* criterion,
+                      double threshold) {
+  CR_ARG(kmax >= 1 && kmax <= n, at);
+  if (criterion) {
+    CR_ARG(*criterion == VGPOSP_CRIT_VARIANCE || *criterion == VGPOSP_CRIT_ENTROPY, at + 1);
+    ++at;
+  }
+  CR_ARG(threshold >= 0.0, at + 1);
+  return 0;
+}
+
+// (kmax, round, forced, j, selected, sel_delta) of a step
+static int check_round(const char* fn, int at, int kmax, int64_t n, int round,
+                       const int64_t* forced, int64_t j, const int64_t* selected) {
+  CR_ARG(kmax >= 1 && kmax <= n, at);
+  CR_ARG(round >= 0 && round < kmax, at + 1);
+  CR_ARG(forced == nullptr || j >= 0, at + 3);
+  CR_ARG(selected != nullptr, at + 4);
+  return 0;
+}
+
+// (ws, n[, mid], kmax) of a _buffers entry; mid: P or s where the entry has one
+static int check_buffers(const char* fn, const void* ws, int64_t n, const int64_t* mid, int kmax) {
+  CR_ARG(ws != nullptr, 1);
+  CR_ARG(n >= 1, 2);
+  if (mid) CR_ARG(*mid >= 1, 3);
+  CR_ARG(kmax >= 1, mid ? 4 : 3);
+  return 0;
+}
+
+// (x, y, ws, ws_bytes) of a pass entry, x at `at`: a missing workspace is VGPOSP_E_WS there
+static int check_pass(const char* fn, int at, const double* x, const double* y, const void* ws,
+                      size_t ws_bytes, size_t need) {
+  CR_ARG(x != nullptr, at);
+  CR_ARG(y != nullptr, at + 1);
+  if (ws == nullptr) {
+    set_error("%s: workspace is null", fn);
+    return VGPOSP_E_WS;
+  }
+  if (ws_bytes < need) {
+    set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, need);
+    return VGPOSP_E_WS;
   }
   return 0;
+}
+
+// The outputs of a _buffers entry, each optional.
+static void crit_outputs(const CritWS& w, double** nom, double** score, double** delta,
+                         double** W) {
+  if (nom) *nom = w.nom;
+  if (score) *score = w.s;
+  if (delta) *delta = w.delta;
+  if (W) *W = w.W;
+}
+static void critx_outputs(const CritXWS& w, double** nom, double** score, double** delta,
+                          double** W, double** U) {
+  crit_outputs(w.c, nom, score, delta, W);
+  if (U) *U = w.U;
 }
 
 }  // namespace vgposp
@@ -1592,17 +1744,9 @@ static int symv_entry(const char* fn, const double* A, int64_t n, int64_t lda, c
                       const double* x, double* y, void* ws, size_t ws_bytes, void* stream) {
   clear_error();
   if (n == 0) return 0;
-  if (A == nullptr) { set_error("%s: bad argument 1", fn); return -1; }
-  if (!(n >= 1 && n <= CR_NMAX)) { set_error("%s: bad argument 2", fn); return -2; }
-  if (lda < n) { set_error("%s: bad argument 3", fn); return -3; }
-  if (x == nullptr) { set_error("%s: bad argument 5", fn); return -5; }
-  if (y == nullptr) { set_error("%s: bad argument 6", fn); return -6; }
-  if (ws == nullptr) { set_error("%s: workspace is null", fn); return VGPOSP_E_WS; }
+  CR_TRY(check_sigma(fn, 1, SigmaStored{A, lda, diag}, n));
   const SymvWS w = symv_layout(ws, n);
-  if (ws_bytes < w.bytes) {
-    set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, w.bytes);
-    return VGPOSP_E_WS;
-  }
+  CR_TRY(check_pass(fn, 5, x, y, ws, ws_bytes, w.bytes));
   symv_launch<SQ>(A, n, lda, diag, x, y, w, nullptr, as_stream(stream));
   VG_LAUNCH_CHECK();
   return 0;
@@ -1630,16 +1774,13 @@ extern "C" int vgposp_crit_init(const double* Sigma, int64_t n, int64_t lda, con
                                 const unsigned char* targets, const unsigned char* allowed,
                                 void* ws, size_t ws_bytes, void* stream) {
   clear_error();
-  VG_CHECK_ARG(Sigma != nullptr, 1);
-  VG_CHECK_ARG(n >= 1 && n <= CR_NMAX, 2);
-  VG_CHECK_ARG(lda >= n, 3);
-  VG_CHECK_ARG(kmax >= 1 && kmax <= n, 5);
-  VG_CHECK_ARG(criterion == VGPOSP_CRIT_VARIANCE || criterion == VGPOSP_CRIT_ENTROPY, 6);
-  VG_CHECK_ARG(threshold >= 0.0, 7);
+  const SigmaStored sg{Sigma, lda, diag};
+  CR_TRY(check_sigma(__func__, 1, sg, n));
+  CR_TRY(check_rule(__func__, 5, kmax, n, &criterion, threshold));
   VG_CHECK_ARG(ws != nullptr, 10);
   const CritWS w = crit_layout(ws, n, kmax);
   VG_CHECK_WS(ws_bytes, w.bytes);
-  return crit_init_run(SigmaStored{Sigma, lda, diag}, n, criterion, threshold, targets, allowed, w,
+  return crit_init_run(sg, InV{}, n, 0, criterion, threshold, targets, nullptr, allowed, w,
                        as_stream(stream));
 }
 
@@ -1648,31 +1789,21 @@ extern "C" int vgposp_crit_step(const double* Sigma, int64_t n, int64_t lda, con
                                 int64_t* selected, double* sel_delta, void* ws, size_t ws_bytes,
                                 void* stream) {
   clear_error();
-  VG_CHECK_ARG(Sigma != nullptr, 1);
-  VG_CHECK_ARG(n >= 1 && n <= CR_NMAX, 2);
-  VG_CHECK_ARG(lda >= n, 3);
-  VG_CHECK_ARG(kmax >= 1 && kmax <= n, 5);
-  VG_CHECK_ARG(round >= 0 && round < kmax, 6);
-  VG_CHECK_ARG(forced == nullptr || j >= 0, 8);
-  VG_CHECK_ARG(selected != nullptr, 9);
+  const SigmaStored sg{Sigma, lda, diag};
+  CR_TRY(check_sigma(__func__, 1, sg, n));
+  CR_TRY(check_round(__func__, 5, kmax, n, round, forced, j, selected));
   VG_CHECK_ARG(ws != nullptr, 11);
   const CritWS w = crit_layout(ws, n, kmax);
   VG_CHECK_WS(ws_bytes, w.bytes);
-  return crit_step_run(SigmaStored{Sigma, lda, diag}, n, round, forced, j, selected, sel_delta, w,
+  return crit_step_run(sg, InV{}, n, 0, round, forced, j, selected, sel_delta, w,
                        as_stream(stream));
 }
 
 extern "C" int vgposp_crit_buffers(void* ws, int64_t n, int kmax, double** nom, double** score,
                                    double** delta, double** W) {
   clear_error();
-  VG_CHECK_ARG(ws != nullptr, 1);
-  VG_CHECK_ARG(n >= 1, 2);
-  VG_CHECK_ARG(kmax >= 1, 3);
-  const CritWS w = crit_layout(ws, n, kmax);
-  if (nom) *nom = w.nom;
-  if (score) *score = w.s;
-  if (delta) *delta = w.delta;
-  if (W) *W = w.W;
+  CR_TRY(check_buffers(__func__, ws, n, nullptr, kmax));
+  crit_outputs(crit_layout(ws, n, kmax), nom, score, delta, W);
   return 0;
 }
 
@@ -1686,18 +1817,8 @@ static int gemv_t_entry(const char* fn, const double* R, int64_t P, int64_t n, i
                         const double* x, double* y, void* ws, size_t ws_bytes, void* stream) {
   clear_error();
   if (P == 0 || n == 0) return 0;
-  if (R == nullptr) { set_error("%s: bad argument 1", fn); return -1; }
-  if (!(P >= 1 && P <= CRX_PMAX)) { set_error("%s: bad argument 2", fn); return -2; }
-  if (!(n >= 1 && n <= CR_NMAX)) { set_error("%s: bad argument 3", fn); return -3; }
-  if (ldr < n) { set_error("%s: bad argument 4", fn); return -4; }
-  if (x == nullptr) { set_error("%s: bad argument 5", fn); return -5; }
-  if (y == nullptr) { set_error("%s: bad argument 6", fn); return -6; }
-  if (ws == nullptr) { set_error("%s: workspace is null", fn); return VGPOSP_E_WS; }
-  const size_t need = gemv_t_bytes(P, n);
-  if (ws_bytes < need) {
-    set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, need);
-    return VGPOSP_E_WS;
-  }
+  CR_TRY(check_cross(fn, 1, CrossStored{R, ldr}, P, n, true));
+  CR_TRY(check_pass(fn, 5, x, y, ws, ws_bytes, gemv_t_bytes(P, n)));
   gemv_t_launch<SQ>(R, P, n, ldr, x, y, static_cast<double*>(ws), nullptr, as_stream(stream));
   VG_LAUNCH_CHECK();
   return 0;
@@ -1724,27 +1845,16 @@ extern "C" int vgposp_critx_init(const double* Sigma, int64_t n, int64_t lda, co
                                  int kmax, double threshold, const unsigned char* allowed,
                                  void* ws, size_t ws_bytes, void* stream) {
   clear_error();
-  VG_CHECK_ARG(Sigma != nullptr, 1);
-  VG_CHECK_ARG(n >= 1 && n <= CR_NMAX, 2);
-  VG_CHECK_ARG(lda >= n, 3);
-  VG_CHECK_ARG(R != nullptr, 5);
-  VG_CHECK_ARG(P >= 1 && P <= CRX_PMAX, 6);
-  VG_CHECK_ARG(ldr >= n, 7);
-  VG_CHECK_ARG(kmax >= 1 && kmax <= n, 9);
-  VG_CHECK_ARG(threshold >= 0.0, 10);
+  const SigmaStored sg{Sigma, lda, diag};
+  const CrossStored cr{R, ldr};
+  CR_TRY(check_sigma(__func__, 1, sg, n));
+  CR_TRY(check_cross(__func__, 5, cr, P, n));
+  CR_TRY(check_rule(__func__, 9, kmax, n, nullptr, threshold));
   VG_CHECK_ARG(ws != nullptr, 12);
   const CritXWS w = critx_layout(ws, n, P, kmax, gemv_t_bytes(P, n));
   VG_CHECK_WS(ws_bytes, w.bytes);
-  hipStream_t s = as_stream(stream);
-  hipLaunchKernelGGL(crit_init_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, Sigma, n,
-                     lda, diag, VGPOSP_CRIT_VARIANCE, threshold, nullptr, allowed, w.c);
-  hipLaunchKernelGGL(critx_init_kernel, dim3((unsigned)ceil_div(P, 256)), dim3(256), 0, s, P,
-                     weights, w);
-  VG_LAUNCH_CHECK();
-  // s_y = sum_v omega_v R_vy^2
-  gemv_t_launch<true>(R, P, n, ldr, w.omega, w.c.s, w.gemv, nullptr, s);
-  VG_LAUNCH_CHECK();
-  return 0;
+  return crit_init_run(sg, cr, n, P, VGPOSP_CRIT_VARIANCE, threshold, nullptr, weights, allowed, w,
+                       as_stream(stream));
 }
 
 extern "C" int vgposp_critx_step(const double* Sigma, int64_t n, int64_t lda, const double* diag,
@@ -1752,68 +1862,22 @@ extern "C" int vgposp_critx_step(const double* Sigma, int64_t n, int64_t lda, co
                                  const int64_t* forced, int64_t j, int64_t* selected,
                                  double* sel_delta, void* ws, size_t ws_bytes, void* stream) {
   clear_error();
-  VG_CHECK_ARG(Sigma != nullptr, 1);
-  VG_CHECK_ARG(n >= 1 && n <= CR_NMAX, 2);
-  VG_CHECK_ARG(lda >= n, 3);
-  VG_CHECK_ARG(R != nullptr, 5);
-  VG_CHECK_ARG(P >= 1 && P <= CRX_PMAX, 6);
-  VG_CHECK_ARG(ldr >= n, 7);
-  VG_CHECK_ARG(kmax >= 1 && kmax <= n, 8);
-  VG_CHECK_ARG(round >= 0 && round < kmax, 9);
-  VG_CHECK_ARG(forced == nullptr || j >= 0, 11);
-  VG_CHECK_ARG(selected != nullptr, 12);
+  const SigmaStored sg{Sigma, lda, diag};
+  const CrossStored cr{R, ldr};
+  CR_TRY(check_sigma(__func__, 1, sg, n));
+  CR_TRY(check_cross(__func__, 5, cr, P, n));
+  CR_TRY(check_round(__func__, 8, kmax, n, round, forced, j, selected));
   VG_CHECK_ARG(ws != nullptr, 14);
   const CritXWS w = critx_layout(ws, n, P, kmax, gemv_t_bytes(P, n));
   VG_CHECK_WS(ws_bytes, w.bytes);
-  const CritWS tv = critx_target_view(w);
-  hipStream_t s = as_stream(stream);
-  const unsigned nb = (unsigned)ceil_div(n, CR_B), nbp = (unsigned)ceil_div(P, CR_B);
-  {
-    ProfScope ps("criteria_select", s, 0.0, 8.0 * 3.0 * n);
-    hipLaunchKernelGGL(crit_score_kernel, dim3((unsigned)ceil_div(n, CR_CH)), dim3(CR_CH), 0, s, n,
-                       w.c);
-    hipLaunchKernelGGL(crit_select_kernel, dim3(1), dim3(CR_CH), 0, s, n, round, forced, j,
-                       selected, sel_delta, w.c);
-    VG_LAUNCH_CHECK();
-  }
-  {
-    ProfScope ps("criteria_row", s, 0.0,
-                 8.0 * ((double)n * (5 + round) + (double)P * (4 + round)));
-    hipLaunchKernelGGL(crit_row_kernel, dim3(nb), dim3(CR_B), 0, s, Sigma, n, lda, diag, selected,
-                       round, w.c);
-    hipLaunchKernelGGL(critx_urow_kernel, dim3(nbp), dim3(CR_B), 0, s, R, P, ldr, selected, round,
-                       w);
-    VG_LAUNCH_CHECK();
-  }
-  // dot[t] = U_t . (omega.u) for t <= round (t = round: sum_v omega_v u_v^2), over P
-  hipLaunchKernelGGL(crit_dots_kernel, dim3(nbp, (unsigned)round + 1), dim3(CR_B), 0, s, P,
-                     selected, round, tv);
-  hipLaunchKernelGGL(crit_fold_kernel, dim3((unsigned)round + 1), dim3(CR_B), 0, s, (int64_t)nbp,
-                     selected, round, tv);
-  VG_LAUNCH_CHECK();
-  gemv_t_launch<false>(R, P, n, ldr, w.wu, w.c.g, w.gemv, w.c.prm + 1, s);
-  VG_LAUNCH_CHECK();
-  {
-    ProfScope ps("criteria_update", s, 0.0, 8.0 * (double)n * (4 + round));
-    hipLaunchKernelGGL(crit_update_kernel, dim3(nb), dim3(CR_B), 0, s, n, selected, round, w.c);
-    VG_LAUNCH_CHECK();
-  }
-  return 0;
+  return crit_step_run(sg, cr, n, P, round, forced, j, selected, sel_delta, w, as_stream(stream));
 }
 
 extern "C" int vgposp_critx_buffers(void* ws, int64_t n, int64_t P, int kmax, double** nom,
                                     double** score, double** delta, double** W, double** U) {
   clear_error();
-  VG_CHECK_ARG(ws != nullptr, 1);
-  VG_CHECK_ARG(n >= 1, 2);
-  VG_CHECK_ARG(P >= 1, 3);
-  VG_CHECK_ARG(kmax >= 1, 4);
-  const CritXWS w = critx_layout(ws, n, P, kmax, gemv_t_bytes(P, n));
-  if (nom) *nom = w.c.nom;
-  if (score) *score = w.c.s;
-  if (delta) *delta = w.c.delta;
-  if (W) *W = w.c.W;
-  if (U) *U = w.U;
+  CR_TRY(check_buffers(__func__, ws, n, &P, kmax));
+  critx_outputs(critx_layout(ws, n, P, kmax, gemv_t_bytes(P, n)), nom, score, delta, W, U);
   return 0;
 }
 
@@ -1824,35 +1888,12 @@ extern "C" size_t vgposp_kernel_gemv_t_workspace_bytes(int64_t P, int64_t n) {
 }
 
 template <bool SQ>
-static int kgemv_t_entry(const char* fn, int kind, const double* Xt, int64_t P, const double* X,
-                         int64_t n, int d, const double* amp, const double* ls,
-                         const double* target_scale, const double* site_scale, const double* x,
+static int kgemv_t_entry(const char* fn, const KGen& g, int64_t P, int64_t n, const double* x,
                          double* y, void* ws, size_t ws_bytes, void* stream) {
   clear_error();
   if (P == 0 || n == 0) return 0;
-#define KG_ARG(cond, idx)                                \
-  if (!(cond)) {                                         \
-    set_error("%s: bad argument %d (%s)", fn, idx, #cond); \
-    return -(idx);                                       \
-  }
-  KG_ARG(kind >= VGPOSP_KERNEL_EQ && kind <= VGPOSP_KERNEL_MATERN52, 1)
-  KG_ARG(Xt != nullptr, 2)
-  KG_ARG(P >= 1 && P <= CRX_PMAX, 3)
-  KG_ARG(X != nullptr, 4)
-  KG_ARG(n >= 1 && n <= CR_NMAX, 5)
-  KG_ARG(d >= 1 && d <= 8, 6)
-  KG_ARG(amp != nullptr, 7)
-  KG_ARG(ls != nullptr, 8)
-  KG_ARG(x != nullptr, 11)
-  KG_ARG(y != nullptr, 12)
-#undef KG_ARG
-  if (ws == nullptr) { set_error("%s: workspace is null", fn); return VGPOSP_E_WS; }
-  const size_t need = kgemv_t_bytes(P, n);
-  if (ws_bytes < need) {
-    set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, need);
-    return VGPOSP_E_WS;
-  }
-  const KGen g{kind, d, Xt, X, amp, ls, target_scale, site_scale};
+  CR_TRY(check_cross(fn, 1, g, P, n, true));
+  CR_TRY(check_pass(fn, 11, x, y, ws, ws_bytes, kgemv_t_bytes(P, n)));
   kgemv_t_launch<SQ>(g, P, n, x, y, static_cast<double*>(ws), nullptr, as_stream(stream));
   VG_LAUNCH_CHECK();
   return 0;
@@ -1863,8 +1904,8 @@ extern "C" int vgposp_kernel_gemv_t(int kind, const double* Xt, int64_t P, const
                                     const double* target_scale, const double* site_scale,
                                     const double* x, double* y, void* ws, size_t ws_bytes,
                                     void* stream) {
-  return kgemv_t_entry<false>(__func__, kind, Xt, P, X, n, d, amp, ls, target_scale, site_scale,
-                              x, y, ws, ws_bytes, stream);
+  return kgemv_t_entry<false>(__func__, KGen{kind, d, Xt, X, amp, ls, target_scale, site_scale}, P,
+                              n, x, y, ws, ws_bytes, stream);
 }
 
 extern "C" int vgposp_kernel_gemv_t_sq(int kind, const double* Xt, int64_t P, const double* X,
@@ -1872,8 +1913,8 @@ extern "C" int vgposp_kernel_gemv_t_sq(int kind, const double* Xt, int64_t P, co
                                        const double* target_scale, const double* site_scale,
                                        const double* x, double* y, void* ws, size_t ws_bytes,
                                        void* stream) {
-  return kgemv_t_entry<true>(__func__, kind, Xt, P, X, n, d, amp, ls, target_scale, site_scale, x,
-                             y, ws, ws_bytes, stream);
+  return kgemv_t_entry<true>(__func__, KGen{kind, d, Xt, X, amp, ls, target_scale, site_scale}, P,
+                             n, x, y, ws, ws_bytes, stream);
 }
 
 extern "C" size_t vgposp_critk_workspace_bytes(int64_t n, int64_t P, int kmax) {
@@ -1888,24 +1929,16 @@ extern "C" int vgposp_critk_init(const double* Sigma, int64_t n, int64_t lda, co
                                  double threshold, const unsigned char* allowed, void* ws,
                                  size_t ws_bytes, void* stream) {
   clear_error();
-  VG_CHECK_ARG(Sigma != nullptr, 1);
-  VG_CHECK_ARG(n >= 1 && n <= CR_NMAX, 2);
-  VG_CHECK_ARG(lda >= n, 3);
-  VG_CHECK_ARG(kind >= VGPOSP_KERNEL_EQ && kind <= VGPOSP_KERNEL_MATERN52, 5);
-  VG_CHECK_ARG(Xt != nullptr, 6);
-  VG_CHECK_ARG(P >= 1 && P <= CRX_PMAX, 7);
-  VG_CHECK_ARG(X != nullptr, 8);
-  VG_CHECK_ARG(d >= 1 && d <= 8, 9);
-  VG_CHECK_ARG(amp != nullptr, 10);
-  VG_CHECK_ARG(ls != nullptr, 11);
-  VG_CHECK_ARG(kmax >= 1 && kmax <= n, 15);
-  VG_CHECK_ARG(threshold >= 0.0, 16);
+  const SigmaStored sg{Sigma, lda, diag};
+  const KGen g{kind, d, Xt, X, amp, ls, target_scale, site_scale};
+  CR_TRY(check_sigma(__func__, 1, sg, n));
+  CR_TRY(check_cross(__func__, 5, g, P, n));
+  CR_TRY(check_rule(__func__, 15, kmax, n, nullptr, threshold));
   VG_CHECK_ARG(ws != nullptr, 18);
   const CritXWS w = critx_layout(ws, n, P, kmax, kgemv_t_bytes(P, n));
   VG_CHECK_WS(ws_bytes, w.bytes);
-  const KGen g{kind, d, Xt, X, amp, ls, target_scale, site_scale};
-  return critk_init_run(SigmaStored{Sigma, lda, diag}, g, n, P, weights, threshold, allowed, w,
-                        as_stream(stream));
+  return crit_init_run(sg, g, n, P, VGPOSP_CRIT_VARIANCE, threshold, nullptr, weights, allowed, w,
+                       as_stream(stream));
 }
 
 extern "C" int vgposp_critk_step(const double* Sigma, int64_t n, int64_t lda, const double* diag,
@@ -1915,41 +1948,22 @@ extern "C" int vgposp_critk_step(const double* Sigma, int64_t n, int64_t lda, co
                                  const int64_t* forced, int64_t j, int64_t* selected,
                                  double* sel_delta, void* ws, size_t ws_bytes, void* stream) {
   clear_error();
-  VG_CHECK_ARG(Sigma != nullptr, 1);
-  VG_CHECK_ARG(n >= 1 && n <= CR_NMAX, 2);
-  VG_CHECK_ARG(lda >= n, 3);
-  VG_CHECK_ARG(kind >= VGPOSP_KERNEL_EQ && kind <= VGPOSP_KERNEL_MATERN52, 5);
-  VG_CHECK_ARG(Xt != nullptr, 6);
-  VG_CHECK_ARG(P >= 1 && P <= CRX_PMAX, 7);
-  VG_CHECK_ARG(X != nullptr, 8);
-  VG_CHECK_ARG(d >= 1 && d <= 8, 9);
-  VG_CHECK_ARG(amp != nullptr, 10);
-  VG_CHECK_ARG(ls != nullptr, 11);
-  VG_CHECK_ARG(kmax >= 1 && kmax <= n, 14);
-  VG_CHECK_ARG(round >= 0 && round < kmax, 15);
-  VG_CHECK_ARG(forced == nullptr || j >= 0, 17);
-  VG_CHECK_ARG(selected != nullptr, 18);
+  const SigmaStored sg{Sigma, lda, diag};
+  const KGen g{kind, d, Xt, X, amp, ls, target_scale, site_scale};
+  CR_TRY(check_sigma(__func__, 1, sg, n));
+  CR_TRY(check_cross(__func__, 5, g, P, n));
+  CR_TRY(check_round(__func__, 14, kmax, n, round, forced, j, selected));
   VG_CHECK_ARG(ws != nullptr, 20);
   const CritXWS w = critx_layout(ws, n, P, kmax, kgemv_t_bytes(P, n));
   VG_CHECK_WS(ws_bytes, w.bytes);
-  const KGen g{kind, d, Xt, X, amp, ls, target_scale, site_scale};
-  return critk_step_run(SigmaStored{Sigma, lda, diag}, g, n, P, round, forced, j, selected,
-                        sel_delta, w, as_stream(stream));
+  return crit_step_run(sg, g, n, P, round, forced, j, selected, sel_delta, w, as_stream(stream));
 }
 
 extern "C" int vgposp_critk_buffers(void* ws, int64_t n, int64_t P, int kmax, double** nom,
                                     double** score, double** delta, double** W, double** U) {
   clear_error();
-  VG_CHECK_ARG(ws != nullptr, 1);
-  VG_CHECK_ARG(n >= 1, 2);
-  VG_CHECK_ARG(P >= 1, 3);
-  VG_CHECK_ARG(kmax >= 1, 4);
-  const CritXWS w = critx_layout(ws, n, P, kmax, kgemv_t_bytes(P, n));
-  if (nom) *nom = w.c.nom;
-  if (score) *score = w.c.s;
-  if (delta) *delta = w.c.delta;
-  if (W) *W = w.c.W;
-  if (U) *U = w.U;
+  CR_TRY(check_buffers(__func__, ws, n, &P, kmax));
+  critx_outputs(critx_layout(ws, n, P, kmax, kgemv_t_bytes(P, n)), nom, score, delta, W, U);
   return 0;
 }
 
@@ -1960,33 +1974,13 @@ extern "C" size_t vgposp_kernel_symv_workspace_bytes(int64_t n) {
 }
 
 template <bool SQ>
-static int ksymv_entry(const char* fn, int kind, const double* X, int64_t n, int d,
-                       const double* amp, const double* ls, const double* site_scale,
-                       const double* diag, const double* x, double* y, void* ws, size_t ws_bytes,
-                       void* stream) {
+static int ksymv_entry(const char* fn, const SGen& g, int64_t n, const double* x, double* y,
+                       void* ws, size_t ws_bytes, void* stream) {
   clear_error();
   if (n == 0) return 0;
-#define KS_ARG(cond, idx)                                \
-  if (!(cond)) {                                         \
-    set_error("%s: bad argument %d (%s)", fn, idx, #cond); \
-    return -(idx);                                       \
-  }
-  KS_ARG(kind >= VGPOSP_KERNEL_EQ && kind <= VGPOSP_KERNEL_MATERN52, 1)
-  KS_ARG(X != nullptr, 2)
-  KS_ARG(n >= 1 && n <= CR_NMAX, 3)
-  KS_ARG(d >= 1 && d <= 8, 4)
-  KS_ARG(amp != nullptr, 5)
-  KS_ARG(ls != nullptr, 6)
-  KS_ARG(x != nullptr, 9)
-  KS_ARG(y != nullptr, 10)
-#undef KS_ARG
-  if (ws == nullptr) { set_error("%s: workspace is null", fn); return VGPOSP_E_WS; }
+  CR_TRY(check_sigma(fn, 1, g, n));
   const KSymvWS w = ksymv_layout(ws, n);
-  if (ws_bytes < w.bytes) {
-    set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, w.bytes);
-    return VGPOSP_E_WS;
-  }
-  const SGen g{kind, d, X, amp, ls, site_scale, diag};
+  CR_TRY(check_pass(fn, 9, x, y, ws, ws_bytes, w.bytes));
   ksymv_launch<SQ>(g, n, x, y, w, nullptr, as_stream(stream));
   VG_LAUNCH_CHECK();
   return 0;
@@ -1996,16 +1990,16 @@ extern "C" int vgposp_kernel_symv(int kind, const double* X, int64_t n, int d, c
                                   const double* ls, const double* site_scale, const double* diag,
                                   const double* x, double* y, void* ws, size_t ws_bytes,
                                   void* stream) {
-  return ksymv_entry<false>(__func__, kind, X, n, d, amp, ls, site_scale, diag, x, y, ws, ws_bytes,
-                            stream);
+  return ksymv_entry<false>(__func__, SGen{kind, d, X, amp, ls, site_scale, diag}, n, x, y, ws,
+                            ws_bytes, stream);
 }
 
 extern "C" int vgposp_kernel_symv_sq(int kind, const double* X, int64_t n, int d,
                                      const double* amp, const double* ls,
                                      const double* site_scale, const double* diag, const double* x,
                                      double* y, void* ws, size_t ws_bytes, void* stream) {
-  return ksymv_entry<true>(__func__, kind, X, n, d, amp, ls, site_scale, diag, x, y, ws, ws_bytes,
-                           stream);
+  return ksymv_entry<true>(__func__, SGen{kind, d, X, amp, ls, site_scale, diag}, n, x, y, ws,
+                           ws_bytes, stream);
 }
 
 static CritWS critg_layout(void* base, int64_t n, int kmax) {
@@ -2023,20 +2017,14 @@ extern "C" int vgposp_critg_init(int kind, const double* X, int64_t n, int d, co
                                  const unsigned char* targets, const unsigned char* allowed,
                                  void* ws, size_t ws_bytes, void* stream) {
   clear_error();
-  VG_CHECK_ARG(kind >= VGPOSP_KERNEL_EQ && kind <= VGPOSP_KERNEL_MATERN52, 1);
-  VG_CHECK_ARG(X != nullptr, 2);
-  VG_CHECK_ARG(n >= 1 && n <= CR_NMAX, 3);
-  VG_CHECK_ARG(d >= 1 && d <= 8, 4);
-  VG_CHECK_ARG(amp != nullptr, 5);
-  VG_CHECK_ARG(ls != nullptr, 6);
-  VG_CHECK_ARG(kmax >= 1 && kmax <= n, 9);
-  VG_CHECK_ARG(criterion == VGPOSP_CRIT_VARIANCE || criterion == VGPOSP_CRIT_ENTROPY, 10);
-  VG_CHECK_ARG(threshold >= 0.0, 11);
+  const SGen sg{kind, d, X, amp, ls, site_scale, diag};
+  CR_TRY(check_sigma(__func__, 1, sg, n));
+  CR_TRY(check_rule(__func__, 9, kmax, n, &criterion, threshold));
   VG_CHECK_ARG(ws != nullptr, 14);
   const CritWS w = critg_layout(ws, n, kmax);
   VG_CHECK_WS(ws_bytes, w.bytes);
-  return crit_init_run(SGen{kind, d, X, amp, ls, site_scale, diag}, n, criterion, threshold,
-                       targets, allowed, w, as_stream(stream));
+  return crit_init_run(sg, InV{}, n, 0, criterion, threshold, targets, nullptr, allowed, w,
+                       as_stream(stream));
 }
 
 extern "C" int vgposp_critg_step(int kind, const double* X, int64_t n, int d, const double* amp,
@@ -2045,34 +2033,21 @@ extern "C" int vgposp_critg_step(int kind, const double* X, int64_t n, int d, co
                                  int64_t* selected, double* sel_delta, void* ws, size_t ws_bytes,
                                  void* stream) {
   clear_error();
-  VG_CHECK_ARG(kind >= VGPOSP_KERNEL_EQ && kind <= VGPOSP_KERNEL_MATERN52, 1);
-  VG_CHECK_ARG(X != nullptr, 2);
-  VG_CHECK_ARG(n >= 1 && n <= CR_NMAX, 3);
-  VG_CHECK_ARG(d >= 1 && d <= 8, 4);
-  VG_CHECK_ARG(amp != nullptr, 5);
-  VG_CHECK_ARG(ls != nullptr, 6);
-  VG_CHECK_ARG(kmax >= 1 && kmax <= n, 9);
-  VG_CHECK_ARG(round >= 0 && round < kmax, 10);
-  VG_CHECK_ARG(forced == nullptr || j >= 0, 12);
-  VG_CHECK_ARG(selected != nullptr, 13);
+  const SGen sg{kind, d, X, amp, ls, site_scale, diag};
+  CR_TRY(check_sigma(__func__, 1, sg, n));
+  CR_TRY(check_round(__func__, 9, kmax, n, round, forced, j, selected));
   VG_CHECK_ARG(ws != nullptr, 15);
   const CritWS w = critg_layout(ws, n, kmax);
   VG_CHECK_WS(ws_bytes, w.bytes);
-  return crit_step_run(SGen{kind, d, X, amp, ls, site_scale, diag}, n, round, forced, j, selected,
-                       sel_delta, w, as_stream(stream));
+  return crit_step_run(sg, InV{}, n, 0, round, forced, j, selected, sel_delta, w,
+                       as_stream(stream));
 }
 
 extern "C" int vgposp_critg_buffers(void* ws, int64_t n, int kmax, double** nom, double** score,
                                     double** delta, double** W) {
   clear_error();
-  VG_CHECK_ARG(ws != nullptr, 1);
-  VG_CHECK_ARG(n >= 1, 2);
-  VG_CHECK_ARG(kmax >= 1, 3);
-  const CritWS w = critg_layout(ws, n, kmax);
-  if (nom) *nom = w.nom;
-  if (score) *score = w.s;
-  if (delta) *delta = w.delta;
-  if (W) *W = w.W;
+  CR_TRY(check_buffers(__func__, ws, n, nullptr, kmax));
+  crit_outputs(critg_layout(ws, n, kmax), nom, score, delta, W);
   return 0;
 }
 
@@ -2086,6 +2061,7 @@ extern "C" size_t vgposp_critgk_workspace_bytes(int64_t n, int64_t P, int kmax) 
   return critgk_layout(nullptr, n, P, kmax).bytes;
 }
 
+// (n, diag) stand for Sigma: its points, kernel and site scale are those of the generated R
 extern "C" int vgposp_critgk_init(int64_t n, const double* diag, int kind, const double* Xt,
                                   int64_t P, const double* X, int d, const double* amp,
                                   const double* ls, const double* target_scale,
@@ -2093,22 +2069,15 @@ extern "C" int vgposp_critgk_init(int64_t n, const double* diag, int kind, const
                                   double threshold, const unsigned char* allowed, void* ws,
                                   size_t ws_bytes, void* stream) {
   clear_error();
+  const KGen g{kind, d, Xt, X, amp, ls, target_scale, site_scale};
   VG_CHECK_ARG(n >= 1 && n <= CR_NMAX, 1);
-  VG_CHECK_ARG(kind >= VGPOSP_KERNEL_EQ && kind <= VGPOSP_KERNEL_MATERN52, 3);
-  VG_CHECK_ARG(Xt != nullptr, 4);
-  VG_CHECK_ARG(P >= 1 && P <= CRX_PMAX, 5);
-  VG_CHECK_ARG(X != nullptr, 6);
-  VG_CHECK_ARG(d >= 1 && d <= 8, 7);
-  VG_CHECK_ARG(amp != nullptr, 8);
-  VG_CHECK_ARG(ls != nullptr, 9);
-  VG_CHECK_ARG(kmax >= 1 && kmax <= n, 13);
-  VG_CHECK_ARG(threshold >= 0.0, 14);
+  CR_TRY(check_cross(__func__, 3, g, P, n));
+  CR_TRY(check_rule(__func__, 13, kmax, n, nullptr, threshold));
   VG_CHECK_ARG(ws != nullptr, 16);
   const CritXWS w = critgk_layout(ws, n, P, kmax);
   VG_CHECK_WS(ws_bytes, w.bytes);
-  const KGen g{kind, d, Xt, X, amp, ls, target_scale, site_scale};
-  return critk_init_run(SGen{kind, d, X, amp, ls, site_scale, diag}, g, n, P, weights, threshold,
-                        allowed, w, as_stream(stream));
+  return crit_init_run(SGen{kind, d, X, amp, ls, site_scale, diag}, g, n, P, VGPOSP_CRIT_VARIANCE,
+                       threshold, nullptr, weights, allowed, w, as_stream(stream));
 }
 
 extern "C" int vgposp_critgk_step(int64_t n, const double* diag, int kind, const double* Xt,
@@ -2118,39 +2087,22 @@ extern "C" int vgposp_critgk_step(int64_t n, const double* diag, int kind, const
                                   const int64_t* forced, int64_t j, int64_t* selected,
                                   double* sel_delta, void* ws, size_t ws_bytes, void* stream) {
   clear_error();
+  const KGen g{kind, d, Xt, X, amp, ls, target_scale, site_scale};
   VG_CHECK_ARG(n >= 1 && n <= CR_NMAX, 1);
-  VG_CHECK_ARG(kind >= VGPOSP_KERNEL_EQ && kind <= VGPOSP_KERNEL_MATERN52, 3);
-  VG_CHECK_ARG(Xt != nullptr, 4);
-  VG_CHECK_ARG(P >= 1 && P <= CRX_PMAX, 5);
-  VG_CHECK_ARG(X != nullptr, 6);
-  VG_CHECK_ARG(d >= 1 && d <= 8, 7);
-  VG_CHECK_ARG(amp != nullptr, 8);
-  VG_CHECK_ARG(ls != nullptr, 9);
-  VG_CHECK_ARG(kmax >= 1 && kmax <= n, 12);
-  VG_CHECK_ARG(round >= 0 && round < kmax, 13);
-  VG_CHECK_ARG(forced == nullptr || j >= 0, 15);
-  VG_CHECK_ARG(selected != nullptr, 16);
+  CR_TRY(check_cross(__func__, 3, g, P, n));
+  CR_TRY(check_round(__func__, 12, kmax, n, round, forced, j, selected));
   VG_CHECK_ARG(ws != nullptr, 18);
   const CritXWS w = critgk_layout(ws, n, P, kmax);
   VG_CHECK_WS(ws_bytes, w.bytes);
-  const KGen g{kind, d, Xt, X, amp, ls, target_scale, site_scale};
-  return critk_step_run(SGen{kind, d, X, amp, ls, site_scale, diag}, g, n, P, round, forced, j,
-                        selected, sel_delta, w, as_stream(stream));
+  return crit_step_run(SGen{kind, d, X, amp, ls, site_scale, diag}, g, n, P, round, forced, j,
+                       selected, sel_delta, w, as_stream(stream));
 }
 
 extern "C" int vgposp_critgk_buffers(void* ws, int64_t n, int64_t P, int kmax, double** nom,
                                      double** score, double** delta, double** W, double** U) {
   clear_error();
-  VG_CHECK_ARG(ws != nullptr, 1);
-  VG_CHECK_ARG(n >= 1, 2);
-  VG_CHECK_ARG(P >= 1, 3);
-  VG_CHECK_ARG(kmax >= 1, 4);
-  const CritXWS w = critgk_layout(ws, n, P, kmax);
-  if (nom) *nom = w.c.nom;
-  if (score) *score = w.c.s;
-  if (delta) *delta = w.c.delta;
-  if (W) *W = w.c.W;
-  if (U) *U = w.U;
+  CR_TRY(check_buffers(__func__, ws, n, &P, kmax));
+  critx_outputs(critgk_layout(ws, n, P, kmax), nom, score, delta, W, U);
   return 0;
 }
 
@@ -2161,33 +2113,16 @@ extern "C" size_t vgposp_factor_symv_workspace_bytes(int64_t n, int64_t s) {
 }
 
 template <bool SQ>
-static int fsymv_entry(const char* fn, const double* F, int64_t n, int64_t S, int64_t ldf,
-                       const double* noise, const double* x, double* y, void* ws, size_t ws_bytes,
-                       void* stream) {
+static int fsymv_entry(const char* fn, const SFactor& f, int64_t n, const double* x, double* y,
+                       void* ws, size_t ws_bytes, void* stream) {
   clear_error();
   if (n == 0) return 0;
-#define FS_ARG(cond, idx)                                \
-  if (!(cond)) {                                         \
-    set_error("%s: bad argument %d (%s)", fn, idx, #cond); \
-    return -(idx);                                       \
-  }
-  FS_ARG(F != nullptr, 1)
-  FS_ARG(n >= 1 && n <= FC_NMAX, 2)
-  FS_ARG(S >= 1 && S <= FC_SMAX, 3)
-  FS_ARG(ldf >= S, 4)
-  FS_ARG(x != nullptr, 6)
-  FS_ARG(y != nullptr, 7)
-#undef FS_ARG
-  if (ws == nullptr) { set_error("%s: workspace is null", fn); return VGPOSP_E_WS; }
-  const FacWS w = fac_layout(ws, n, S);
-  if (ws_bytes < w.bytes) {
-    set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, w.bytes);
-    return VGPOSP_E_WS;
-  }
-  const SFactor f{F, S, ldf, noise};
+  CR_TRY(check_sigma(fn, 1, f, n, FC_NMAX));
+  const FacWS w = fac_layout(ws, n, f.S);
+  CR_TRY(check_pass(fn, 6, x, y, ws, ws_bytes, w.bytes));
   hipStream_t s = as_stream(stream);
   if (SQ) {
-    if (int rc = factor_diag_launch(f, n, w.dg, s)) return rc;
+    CR_TRY(factor_diag_launch(f, n, w.dg, s));
     return factor_symv_sq_launch(f, n, x, y, w, s);
   }
   return factor_symv_launch(f, n, x, y, w, nullptr, s);
@@ -2196,13 +2131,13 @@ static int fsymv_entry(const char* fn, const double* F, int64_t n, int64_t S, in
 extern "C" int vgposp_factor_symv(const double* F, int64_t n, int64_t s, int64_t ldf,
                                   const double* noise, const double* x, double* y, void* ws,
                                   size_t ws_bytes, void* stream) {
-  return fsymv_entry<false>(__func__, F, n, s, ldf, noise, x, y, ws, ws_bytes, stream);
+  return fsymv_entry<false>(__func__, SFactor{F, s, ldf, noise}, n, x, y, ws, ws_bytes, stream);
 }
 
 extern "C" int vgposp_factor_symv_sq(const double* F, int64_t n, int64_t s, int64_t ldf,
                                      const double* noise, const double* x, double* y, void* ws,
                                      size_t ws_bytes, void* stream) {
-  return fsymv_entry<true>(__func__, F, n, s, ldf, noise, x, y, ws, ws_bytes, stream);
+  return fsymv_entry<true>(__func__, SFactor{F, s, ldf, noise}, n, x, y, ws, ws_bytes, stream);
 }
 
 static CritWS critf_layout(void* base, int64_t n, int64_t S, int kmax) {
@@ -2219,17 +2154,13 @@ extern "C" int vgposp_critf_init(const double* F, int64_t n, int64_t s, int64_t 
                                  const unsigned char* targets, const unsigned char* allowed,
                                  void* ws, size_t ws_bytes, void* stream) {
   clear_error();
-  VG_CHECK_ARG(F != nullptr, 1);
-  VG_CHECK_ARG(n >= 1 && n <= CR_NMAX, 2);
-  VG_CHECK_ARG(s >= 1 && s <= FC_SMAX, 3);
-  VG_CHECK_ARG(ldf >= s, 4);
-  VG_CHECK_ARG(kmax >= 1 && kmax <= n, 6);
-  VG_CHECK_ARG(criterion == VGPOSP_CRIT_VARIANCE || criterion == VGPOSP_CRIT_ENTROPY, 7);
-  VG_CHECK_ARG(threshold >= 0.0, 8);
+  const SFactor sg{F, s, ldf, noise};
+  CR_TRY(check_sigma(__func__, 1, sg, n));
+  CR_TRY(check_rule(__func__, 6, kmax, n, &criterion, threshold));
   VG_CHECK_ARG(ws != nullptr, 11);
   const CritWS w = critf_layout(ws, n, s, kmax);
   VG_CHECK_WS(ws_bytes, w.bytes);
-  return crit_init_run(SFactor{F, s, ldf, noise}, n, criterion, threshold, targets, allowed, w,
+  return crit_init_run(sg, InV{}, n, 0, criterion, threshold, targets, nullptr, allowed, w,
                        as_stream(stream));
 }
 
@@ -2238,32 +2169,20 @@ extern "C" int vgposp_critf_step(const double* F, int64_t n, int64_t s, int64_t 
                                  int64_t j, int64_t* selected, double* sel_delta, void* ws,
                                  size_t ws_bytes, void* stream) {
   clear_error();
-  VG_CHECK_ARG(F != nullptr, 1);
-  VG_CHECK_ARG(n >= 1 && n <= CR_NMAX, 2);
-  VG_CHECK_ARG(s >= 1 && s <= FC_SMAX, 3);
-  VG_CHECK_ARG(ldf >= s, 4);
-  VG_CHECK_ARG(kmax >= 1 && kmax <= n, 6);
-  VG_CHECK_ARG(round >= 0 && round < kmax, 7);
-  VG_CHECK_ARG(forced == nullptr || j >= 0, 9);
-  VG_CHECK_ARG(selected != nullptr, 10);
+  const SFactor sg{F, s, ldf, noise};
+  CR_TRY(check_sigma(__func__, 1, sg, n));
+  CR_TRY(check_round(__func__, 6, kmax, n, round, forced, j, selected));
   VG_CHECK_ARG(ws != nullptr, 12);
   const CritWS w = critf_layout(ws, n, s, kmax);
   VG_CHECK_WS(ws_bytes, w.bytes);
-  return crit_step_run(SFactor{F, s, ldf, noise}, n, round, forced, j, selected, sel_delta, w,
+  return crit_step_run(sg, InV{}, n, 0, round, forced, j, selected, sel_delta, w,
                        as_stream(stream));
 }
 
 extern "C" int vgposp_critf_buffers(void* ws, int64_t n, int64_t s, int kmax, double** nom,
                                     double** score, double** delta, double** W) {
   clear_error();
-  VG_CHECK_ARG(ws != nullptr, 1);
-  VG_CHECK_ARG(n >= 1, 2);
-  VG_CHECK_ARG(s >= 1, 3);
-  VG_CHECK_ARG(kmax >= 1, 4);
-  const CritWS w = critf_layout(ws, n, s, kmax);
-  if (nom) *nom = w.nom;
-  if (score) *score = w.s;
-  if (delta) *delta = w.delta;
-  if (W) *W = w.W;
+  CR_TRY(check_buffers(__func__, ws, n, &s, kmax));
+  crit_outputs(critf_layout(ws, n, s, kmax), nom, score, delta, W);
   return 0;
 }

@@ -112,6 +112,32 @@ def _scale(name, a, count):
     return linalg.as_device(a)
 
 
+def _nonnegative(name, a, count):
+    """-> host float64 [count], finite and not negative (a noise vector, the targets' weights)."""
+    a = _host_vector(name, a, count)
+    if not np.isfinite(a).all() or (a < 0.0).any():
+        raise ValueError(f"{name} must be finite and not negative")
+    return a
+
+
+def _noise(noise, N):
+    """-> host float64 [N] from a scalar or a vector."""
+    return _nonnegative("noise", np.full(N, float(noise)) if np.ndim(noise) == 0 else noise, N)
+
+
+def _field(kind, points, amp, ls, scale_name, scale):
+    """What a SiteKernel and a CrossKernel hold of the sites, validated and on the device:
+    (kind, X, N, d, amp_value, ls_value, amp, ls, scale)."""
+    kind = linalg.kind_id(kind)
+    X = _points("points", points)
+    N, d = int(X.shape[0]), int(X.shape[1])
+    if not 1 <= d <= 8:
+        raise ValueError(f"points must have 1 <= d <= 8 coordinates, got {d}")
+    amp_value, ls_value = _positive_scalars(amp, ls)
+    return (kind, X, N, d, amp_value, ls_value, linalg._vec(amp_value), linalg._vec(ls_value),
+            _scale(scale_name, scale, N))
+
+
 class SiteKernel:
     """A covariance of the candidate sites that is never stored: Sigma = diag(scale) K(points,
     points) diag(scale) + diag(noise) for one stationary kernel ``kind`` (``amp``, ``ls`` scalars)
@@ -121,21 +147,16 @@ class SiteKernel:
     points, the scale and the diagonal scale^2 amp^2 + noise: N (d + 2) doubles instead of N^2."""
 
     def __init__(self, kind, points, amp, ls, scale=None, noise=0.0):
-        self.kind = linalg.kind_id(kind)
-        self.X = _points("points", points)
-        self.N, self.d = int(self.X.shape[0]), int(self.X.shape[1])
-        if not 1 <= self.d <= 8:
-            raise ValueError(f"points must have 1 <= d <= 8 coordinates, got {self.d}")
-        self.amp_value, self.ls_value = _positive_scalars(amp, ls)
-        self.amp, self.ls = linalg._vec(self.amp_value), linalg._vec(self.ls_value)
-        self.scale = _scale("scale", scale, self.N)
-        if np.ndim(noise) == 0:
-            noise = np.full(self.N, float(noise))
-        noise = _host_vector("noise", noise, self.N)
-        if not np.isfinite(noise).all() or (noise < 0.0).any():
-            raise ValueError("noise must be finite and not negative")
+        (self.kind, self.X, self.N, self.d, self.amp_value, self.ls_value, self.amp, self.ls,
+         self.scale) = _field(kind, points, amp, ls, "scale", scale)
+        noise = _noise(noise, self.N)
         a = np.ones(self.N) if self.scale is None else self.scale.cpu().numpy()
         self.diag = linalg.as_device(a * a * (self.amp_value * self.amp_value) + noise)
+
+    def field(self):
+        """The site side as ``CrossKernel.from_site`` shares it (the noise is no part of it)."""
+        return (self.kind, self.X, self.N, self.d, self.amp_value, self.ls_value, self.amp,
+                self.ls, self.scale)
 
     def args(self):
         """(kind, X, N, d, amp, ls, site_scale, diag) as the vgposp_critg_* entries take them."""
@@ -169,11 +190,7 @@ class FactoredCovariance:
     @staticmethod
     def _noise_vector(noise, N):
         """-> host float64 [N], or None when it is zero everywhere."""
-        if np.ndim(noise) == 0:
-            noise = np.full(N, float(noise))
-        noise = _host_vector("noise", noise, N)
-        if not np.isfinite(noise).all() or (noise < 0.0).any():
-            raise ValueError("noise must be finite and not negative")
+        noise = _noise(noise, N)
         return noise if noise.any() else None
 
     def _upload(self):
@@ -225,18 +242,16 @@ class CrossKernel:
     the targets, d <= 8; the scales (default ones) are finite and positive.  Everything is held
     on the device: (P + N) (d + 1) doubles instead of P N."""
 
-    def __init__(self, kind, points, target_points, amp, ls, site_scale=None, target_scale=None):
-        self.kind = linalg.kind_id(kind)
-        self.X, self.Xt = _points("points", points), _points("target_points", target_points)
-        self.N, self.d = int(self.X.shape[0]), int(self.X.shape[1])
+    def __init__(self, kind, points, target_points, amp, ls, site_scale=None, target_scale=None,
+                 *, _site=None):
+        # the site side: validated here, or a SiteKernel's own device tensors (from_site)
+        (self.kind, self.X, self.N, self.d, self.amp_value, self.ls_value, self.amp, self.ls,
+         self.site_scale) = (_field(kind, points, amp, ls, "site_scale", site_scale)
+                             if _site is None else _site.field())
+        self.Xt = _points("target_points", target_points)
         self.P = int(self.Xt.shape[0])
-        if not 1 <= self.d <= 8:
-            raise ValueError(f"points must have 1 <= d <= 8 coordinates, got {self.d}")
         if self.Xt.shape[1] != self.d:
             raise ValueError(f"target_points must be [P, {self.d}], got {tuple(self.Xt.shape)}")
-        self.amp_value, self.ls_value = _positive_scalars(amp, ls)
-        self.amp, self.ls = linalg._vec(self.amp_value), linalg._vec(self.ls_value)
-        self.site_scale = _scale("site_scale", site_scale, self.N)
         self.target_scale = _scale("target_scale", target_scale, self.P)
 
     @classmethod
@@ -245,17 +260,7 @@ class CrossKernel:
         kind, amp, ls, points and scale (the sensor noise is no part of it)."""
         if not isinstance(site, SiteKernel):
             raise ValueError("from_site needs a placement_criteria.SiteKernel")
-        gen = cls.__new__(cls)
-        gen.kind, gen.X, gen.N, gen.d = site.kind, site.X, site.N, site.d
-        gen.Xt = _points("target_points", target_points)
-        gen.P = int(gen.Xt.shape[0])
-        if gen.Xt.shape[1] != gen.d:
-            raise ValueError(f"target_points must be [P, {gen.d}], got {tuple(gen.Xt.shape)}")
-        gen.amp_value, gen.ls_value, gen.amp, gen.ls = (site.amp_value, site.ls_value, site.amp,
-                                                        site.ls)
-        gen.site_scale = site.scale
-        gen.target_scale = _scale("target_scale", target_scale, gen.P)
-        return gen
+        return cls(None, None, target_points, None, None, target_scale=target_scale, _site=site)
 
     def agrees_with(self, site):
         """Whether this cross-covariance and the ``SiteKernel`` describe one field: the same kind,
@@ -283,37 +288,23 @@ def check_cross_arguments(criterion, targets, cross_cov, target_weights, cross_k
                              "what the other stores")
         if not isinstance(cross_kernel, CrossKernel):
             raise ValueError("cross_kernel must be a placement_criteria.CrossKernel")
-        cross_cov = cross_kernel
-    if target_weights is not None and cross_cov is None:
-        raise ValueError("target_weights need cross_cov: targets inside V are not weighted")
-    if cross_cov is None:
+    elif cross_cov is None:
+        if target_weights is not None:
+            raise ValueError("target_weights need cross_cov: targets inside V are not weighted")
         return
-    if cross_kernel is not None:
-        if criterion != "variance":
-            raise ValueError("cross_kernel and target_weights apply to criterion='variance' only")
-        if targets is not None:
-            raise ValueError("cross_kernel and targets exclude each other: target_points are "
-                             "the targets")
-        return
+    name, rows = (("cross_cov", "the rows of cross_cov") if cross_kernel is None
+                  else ("cross_kernel", "target_points"))
     if criterion != "variance":
-        raise ValueError("cross_cov and target_weights apply to criterion='variance' only")
+        raise ValueError(f"{name} and target_weights apply to criterion='variance' only")
     if targets is not None:
-        raise ValueError("cross_cov and targets exclude each other: the rows of cross_cov are "
-                         "the targets")
+        raise ValueError(f"{name} and targets exclude each other: {rows} are the targets")
 
 
 def normalize_weights(P, target_weights):
     """-> device float64 [P], or None (all ones).  Weights are finite and not negative."""
     if target_weights is None:
         return None
-    w = (target_weights.detach().cpu().numpy() if isinstance(target_weights, torch.Tensor)
-         else np.asarray(target_weights))
-    w = np.ascontiguousarray(w, dtype=np.float64)
-    if w.shape != (P,):
-        raise ValueError(f"target_weights must have length {P}, got shape {w.shape}")
-    if not np.isfinite(w).all() or (w < 0.0).any():
-        raise ValueError("target_weights must be finite and not negative")
-    return linalg.as_device(w)
+    return linalg.as_device(_nonnegative("target_weights", target_weights, P))
 
 
 def _device_matrix(M):
@@ -323,6 +314,23 @@ def _device_matrix(M):
             and M.dtype == torch.float64 and M.stride(1) == 1 and M.stride(0) >= M.shape[1]):
         return M
     return linalg.as_device(M)
+
+
+class _Stored:
+    """A Sigma or an R held as a matrix, where a generated source would stand: ``args()`` is
+    (pointer, rows, pitch) and what the entry takes after them (the diagonal of a Sigma)."""
+
+    def __init__(self, M, *tail):
+        self.M, self.tail = M, tail
+
+    def args(self):
+        return (_p(self.M), int(self.M.shape[0]), self.M.stride(0), *self.tail)
+
+
+# (where Sigma comes from, where the targets outside V come from) -> the family of its entries
+_FAMILIES = {(_Stored, type(None)): "crit", (_Stored, _Stored): "critx",
+             (_Stored, CrossKernel): "critk", (SiteKernel, type(None)): "critg",
+             (SiteKernel, CrossKernel): "critgk", (FactoredCovariance, type(None)): "critf"}
 
 
 class CriterionPlacement:
@@ -425,72 +433,32 @@ class CriterionPlacement:
         self._allowed_dev, self._targets_dev = mask(self.allowed), mask(self.targets)
         self._placed_dev = (torch.as_tensor(self.placed, dtype=torch.int64, device=dev)
                             if self.m else None)
-        # the entry family: crit / critx / critk on a stored Sigma, critg / critgk on a SiteKernel,
-        # critf on a FactoredCovariance
-        if self.fac is not None:
-            self._family = "vgposp_critf"
-        elif self.site is not None:
-            self._family = "vgposp_critg" if self.gen is None else "vgposp_critgk"
-        elif self.gen is not None:
-            self._family = "vgposp_critk"
-        else:
-            self._family = "vgposp_crit" if self.R is None else "vgposp_critx"
-        sizes = (self.n, self.kmax) if self.P == 0 else (self.n, self.P, self.kmax)
-        if self.fac is not None:
-            sizes = (self.n, self.fac.S, self.kmax)
-        self.ws = linalg.workspace(query(self._family + "_workspace_bytes", *sizes))
+        # The entry family, resolved once from where Sigma and the targets come from: its name, the
+        # leading arguments of every call and the sizes its workspace is laid out by.  With both
+        # sides generated (n, diag) stand for Sigma: the CrossKernel carries the rest.
+        sigma = self.site or self.fac or _Stored(S, _p(self.diag))
+        cross = self.gen if self.R is None else _Stored(self.R)
+        self._family = "vgposp_" + _FAMILIES[type(sigma), type(cross)]
+        self._cross = cross is not None
+        self._lead = ((self.n, _p(self.site.diag)) if self.site is not None and self._cross
+                      else sigma.args()) + (cross.args() if self._cross else ())
+        self._sizes = ((self.n,) + ((self.fac.S,) if self.fac is not None else ())
+                       + ((self.P,) if self._cross else ()) + (self.kmax,))
+        self.ws = linalg.workspace(query(self._family + "_workspace_bytes", *self._sizes))
         self.selected = torch.full((self.kmax,), -1, dtype=torch.int64, device=dev)
         self.sel_delta = torch.zeros(self.kmax, dtype=torch.float64, device=dev)
         self.rounds = 0
 
-    def _sigma_args(self):
-        return _p(self.S), self.n, self.S.stride(0), _p(self.diag)
-
-    def _cross_args(self):
-        return _p(self.R), self.P, self.R.stride(0)
-
     def _step(self, r, forced=None, j=0):
-        tail = (r, _p(forced), j, _p(self.selected), _p(self.sel_delta), _p(self.ws),
-                self.ws.numel(), _stream())
-        if self.fac is not None:
-            call("vgposp_critf_step", *self.fac.args(), self.kmax, *tail)
-        elif self.site is not None and self.gen is None:
-            call("vgposp_critg_step", *self.site.args(), self.kmax, *tail)
-        elif self.site is not None:
-            call("vgposp_critgk_step", self.n, _p(self.site.diag), *self.gen.args(), self.kmax,
-                 *tail)
-        elif self.gen is not None:
-            call("vgposp_critk_step", *self._sigma_args(), *self.gen.args(), self.kmax, *tail)
-        elif self.R is None:
-            call("vgposp_crit_step", *self._sigma_args(), self.kmax, *tail)
-        else:
-            call("vgposp_critx_step", *self._sigma_args(), *self._cross_args(), self.kmax, *tail)
+        call(self._family + "_step", *self._lead, self.kmax, r, _p(forced), j, _p(self.selected),
+             _p(self.sel_delta), _p(self.ws), self.ws.numel(), _stream())
 
     def init(self):
-        if self.fac is not None:
-            call("vgposp_critf_init", *self.fac.args(), self.kmax, self.crit, self.threshold,
-                 _p(self._targets_dev), _p(self._allowed_dev), _p(self.ws), self.ws.numel(),
-                 _stream())
-        elif self.site is not None and self.gen is None:
-            call("vgposp_critg_init", *self.site.args(), self.kmax, self.crit, self.threshold,
-                 _p(self._targets_dev), _p(self._allowed_dev), _p(self.ws), self.ws.numel(),
-                 _stream())
-        elif self.site is not None:
-            call("vgposp_critgk_init", self.n, _p(self.site.diag), *self.gen.args(),
-                 _p(self.omega), self.kmax, self.threshold, _p(self._allowed_dev), _p(self.ws),
-                 self.ws.numel(), _stream())
-        elif self.gen is not None:
-            call("vgposp_critk_init", *self._sigma_args(), *self.gen.args(), _p(self.omega),
-                 self.kmax, self.threshold, _p(self._allowed_dev), _p(self.ws), self.ws.numel(),
-                 _stream())
-        elif self.R is None:
-            call("vgposp_crit_init", *self._sigma_args(), self.kmax, self.crit, self.threshold,
-                 _p(self._targets_dev), _p(self._allowed_dev), _p(self.ws), self.ws.numel(),
-                 _stream())
-        else:
-            call("vgposp_critx_init", *self._sigma_args(), *self._cross_args(), _p(self.omega),
-                 self.kmax, self.threshold, _p(self._allowed_dev), _p(self.ws), self.ws.numel(),
-                 _stream())
+        # targets in V: the rule and its mask; targets outside V: their weights, the variance rule
+        rule = ((_p(self.omega), self.kmax, self.threshold) if self._cross
+                else (self.kmax, self.crit, self.threshold, _p(self._targets_dev)))
+        call(self._family + "_init", *self._lead, *rule, _p(self._allowed_dev), _p(self.ws),
+             self.ws.numel(), _stream())
         for j in range(self.m):
             self._step(j, self._placed_dev, j)
         self.rounds = 0
@@ -514,17 +482,8 @@ class CriterionPlacement:
         sum_v omega_v D_vy^2), ``delta`` [N] (as scored by the last round, before its pick),
         ``W`` [placed + rounds, N] and, with ``cross_cov`` or ``cross_kernel``, ``U``
         [placed + rounds, P]."""
-        cross = self.R is not None or self.gen is not None
-        ptr = [ctypes.c_void_p() for _ in range(5 if cross else 4)]
-        if self.fac is not None:
-            call(self._family + "_buffers", _p(self.ws), self.n, self.fac.S, self.kmax,
-                 *map(ctypes.byref, ptr))
-        elif not cross:
-            call(self._family + "_buffers", _p(self.ws), self.n, self.kmax,
-                 *map(ctypes.byref, ptr))
-        else:
-            call(self._family + "_buffers", _p(self.ws), self.n, self.P, self.kmax,
-                 *map(ctypes.byref, ptr))
+        ptr = [ctypes.c_void_p() for _ in range(5 if self._cross else 4)]
+        call(self._family + "_buffers", _p(self.ws), *self._sizes, *map(ctypes.byref, ptr))
 
         def view(p, count):
             off = p.value - self.ws.data_ptr()
@@ -532,7 +491,7 @@ class CriterionPlacement:
         rows = self.m + self.rounds
         st = {"nom": view(ptr[0], self.N), "s": view(ptr[1], self.N),
               "delta": view(ptr[2], self.N), "W": view(ptr[3], rows * self.N).view(rows, self.N)}
-        if cross:
+        if self._cross:
             st["U"] = view(ptr[4], rows * self.P).view(rows, self.P)
         return st
 
