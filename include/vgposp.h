@@ -427,6 +427,8 @@ int vgposp_row_sumsq(const double* V, int64_t rows, int64_t cols, int64_t ldv, d
  * selected: int64 [kmax] device; sel_delta: f64 [kmax] device (delta of each pick) or NULL;
  * info: int32 device (Cholesky status of init).  evals: int64 [kmax] device or NULL (number of
  * delta evaluations the reference would have made in each round).
+ * Every vgposp_greedy_* entry reports a bad argument as "<its own name>: bad argument <the
+ * argument's position in its own prototype>" and returns minus that position.
  * --------------------------------------------------------------------------------------------- */
 size_t vgposp_greedy_workspace_bytes(int64_t n, int kmax);
 int vgposp_greedy_init(double* Sigma, int64_t n, int64_t lda, int kmax, int* info, void* ws,

@@ -78,7 +78,7 @@ def test_mask_and_force_argument_validation():
     assert lib.vgposp_greedy_mask(P8, 0, 2, P8, None) == -2
     assert lib.vgposp_greedy_mask(P8, 10, 11, P8, None) == -3
     assert lib.vgposp_greedy_mask(P8, 10, 2, None, None) == -4
-    assert lib.vgposp_greedy_force(10, 5, 5, P8, 0, P8, P8, BIG, None) == -5   # round < kmax
+    assert lib.vgposp_greedy_force(10, 5, 5, P8, 0, P8, P8, BIG, None) == -3   # round < kmax
     assert lib.vgposp_greedy_force(10, 5, 1, None, 0, P8, P8, BIG, None) == -4
     assert lib.vgposp_greedy_force(10, 5, 1, P8, -1, P8, P8, BIG, None) == -5
     assert lib.vgposp_greedy_force(10, 5, 1, P8, 0, None, P8, BIG, None) == -6

@@ -12,20 +12,16 @@ tiles, two candidate chunks, R.ROUNDS rounds) and G, the benchmark's family at
 placement_split((12, 12, 8), 0) (n = 1,152, EQ, ls = 2h, diagonal + 1e-2 + 1e-6, k = 16: 15
 mat-vec rounds).  Every test restores the width it found.
 """
-import ctypes
-
 import numpy as np
 import pytest
 
 from tests import greedy_state_reference as R
+from tests.greedy_driver import KEYS, PARAMS
+from tests.greedy_driver import Greedy as Driver
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 12345.678
-RC = 512                      # rows per chunk of the mat-vec (csrc/greedy.hip)
 G_SHAPE, G_K = (12, 12, 8), 16
-KEYS = ("delta", "piv", "xcol", "cache", "selected", "sel_delta", "evals", "state")
-PARAMS = (0.0, 1e-8, np.inf)
 
 
 def _same(a, b):
@@ -71,129 +67,9 @@ def cov_of(name):
     return R.fixture_cov("F1") if name == "F1" else g_cov(0)
 
 
-class Greedy:
-    """One greedy workspace driven through the C-ABI (the helper of tests/test_gpu_greedy_state.py,
-    with the speculation's counters and table): Sigma sits in a buffer of row pitch lda that starts
-    `shift` doubles into its allocation, everything around it holds SENTINEL; the workspace starts
-    as NaN bytes."""
-
-    def __init__(self, K, kmax, lda=None, shift=0):
-        import torch
-        from vgposp_amd._lib import query
-        self.n, self.kmax = int(K.shape[0]), int(kmax)
-        self.lda, self.shift = int(lda or self.n), int(shift)
-        self.buf = torch.empty(self.shift + self.n * self.lda, dtype=torch.float64, device="cuda")
-        self.S = ctypes.c_void_p(self.buf.data_ptr() + 8 * self.shift)
-        assert self.buf.data_ptr() % 16 == 0
-        self.load(K)
-        self.ws = torch.empty(query("vgposp_greedy_workspace_bytes", self.n, self.kmax),
-                              dtype=torch.uint8, device="cuda")
-        self.ws.fill_(0xFF)
-        self.info = torch.zeros(1, dtype=torch.int32, device="cuda")
-        self.selected = torch.full((self.kmax,), -1, dtype=torch.int64, device="cuda")
-        self.sel_delta = torch.zeros(self.kmax, dtype=torch.float64, device="cuda")
-        self.evals = torch.zeros(self.kmax, dtype=torch.int64, device="cuda")
-        d, p, plen, x, c = (ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64(),
-                            ctypes.c_void_p(), ctypes.c_void_p())
-        self._call("vgposp_greedy_buffers", self._ws(), self.n, self.kmax, ctypes.byref(d),
-                   ctypes.byref(p), ctypes.byref(plen))
-        self._call("vgposp_greedy_xcol", self._ws(), self.n, self.kmax, ctypes.byref(x))
-        self._call("vgposp_greedy_cache", self._ws(), self.n, self.kmax, ctypes.byref(c))
-        self.delta = self._view(d, self.n)
-        self.piv = self._view(p, plen.value)
-        self.xcol = self._view(x, self.n)
-        self.cache = self._view(c, self.n)
-        # prm, sdiag, nom, prec, delta, cache, W, V: everything ahead of the mat-vec partials,
-        # which sit (256-byte aligned, ceil(n / RC) rows of n) right ahead of xcol
-        part = -(-self.n // RC) * self.n * 8
-        self.state = self.ws[:x.value - self.ws.data_ptr() - (part + 255) // 256 * 256]
-        col, rnd, slots = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
-        self._call("vgposp_greedy_spec_table", self._ws(), self.n, self.kmax, ctypes.byref(col),
-                   ctypes.byref(rnd), ctypes.byref(slots))
-        self.slots = slots.value
-        self.tcol = self._view(col, self.slots, "int64")
-        self.tround = self._view(rnd, self.slots, "int64")
-        self._keep = []
-
-    def load(self, K):
-        import torch
-        host = np.full(self.shift + self.n * self.lda, SENTINEL)
-        host[self.shift:].reshape(self.n, self.lda)[:, :self.n] = K
-        self.host0 = host
-        self.src = torch.as_tensor(host).cuda()
-        self.buf.copy_(self.src)
-
-    def _view(self, ptr, count, dtype="float64"):
-        import torch
-        off = ptr.value - self.ws.data_ptr()
-        assert 0 <= off and off + 8 * count <= self.ws.numel()
-        return self.ws[off:off + 8 * count].view(getattr(torch, dtype))
-
-    @staticmethod
-    def _call(name, *args):
-        from vgposp_amd._lib import call
-        return call(name, *args)
-
-    def _ws(self):
-        return ctypes.c_void_p(self.ws.data_ptr())
-
-    @staticmethod
-    def _stream():
-        from vgposp_amd.linalg import _stream
-        return _stream()
-
-    def _p(self, t):
-        return ctypes.c_void_p(t.data_ptr())
-
-    def init(self):
-        self._call("vgposp_greedy_init_ex", self.S, self.n, self.lda, self.kmax, *PARAMS,
-                   self._p(self.info), self._ws(), self.ws.numel(), self._stream())
-        return self
-
-    def mask(self, blocked):
-        import torch
-        allowed = torch.as_tensor((~np.asarray(blocked, dtype=bool)).astype(np.uint8)).cuda()
-        self._keep.append(allowed)
-        self._call("vgposp_greedy_mask", self._ws(), self.n, self.kmax, self._p(allowed),
-                   self._stream())
-
-    def condition(self, placed, k, batch):
-        import torch
-        from vgposp_amd._lib import query
-        pl = torch.as_tensor(np.asarray(placed, dtype=np.int64)).cuda()
-        scratch = torch.empty(query("vgposp_greedy_condition_workspace_bytes", self.n, batch),
-                              dtype=torch.uint8, device="cuda")
-        scratch.fill_(0xFF)
-        self._keep += [pl, scratch]
-        self._call("vgposp_greedy_condition", self.S, self.n, self.lda, self.kmax, len(placed), k,
-                   batch, self._p(pl), self._p(self.selected), self._ws(), self.ws.numel(),
-                   self._p(scratch), scratch.numel(), self._stream())
-
-    def step(self, r, lazy):
-        self._call("vgposp_greedy_step", self.S, self.n, self.lda, self.kmax, r, int(lazy),
-                   self._p(self.selected), self._p(self.sel_delta), self._p(self.evals),
-                   self._ws(), self.ws.numel(), self._stream())
-
-    def read(self):
-        rec = {k: getattr(self, k).cpu().numpy().copy() for k in KEYS}
-        assert int(self.info.cpu()[0]) == 0
-        return rec
-
-    def stats(self):
-        """(passes, hits, cached) of the run so far."""
-        import torch
-        torch.cuda.synchronize()
-        v = [ctypes.c_int64(-1) for _ in range(3)]
-        self._call("vgposp_greedy_spec_stats", self._ws(), self.n, self.kmax,
-                   *[ctypes.byref(x) for x in v])
-        return tuple(x.value for x in v)
-
-    def table(self):
-        """[(column, fill round)] of the cached columns, in slot order."""
-        cached = self.stats()[2]
-        assert 0 <= cached <= self.slots
-        return list(zip((int(c) for c in self.tcol[:cached].cpu()),
-                        (int(r) for r in self.tround[:cached].cpu())))
+def Greedy(K, kmax, lda=None, shift=0):
+    """The whole of K with placement_algorithm2's constants."""
+    return Driver(K, K.shape[0], kmax, PARAMS, lda, shift)
 
 
 def rounds(g, first, k, lazy):

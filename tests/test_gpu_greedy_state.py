@@ -19,16 +19,13 @@ Inputs (tests/test_greedy_state_reference.py asserts their conditions on the CPU
 TRMV_COLS = 512 column tiles — and its leading blocks; F2 matern52 (9, 9, 8); F3 eq (9, 9, 8)
 with the TF variant's constants (eps = 1e-6 in the factor).
 """
-import ctypes
-
 import numpy as np
 import pytest
 
 from tests import greedy_state_reference as R
+from tests.greedy_driver import Greedy
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = 12345.678  # fills what surrounds Sigma in a padded buffer: read as data it is >> tol
 
 
 def _same(a, b):
@@ -40,118 +37,6 @@ def _same(a, b):
 def _device():
     import torch
     torch.cuda.set_device(0)
-
-
-class Greedy:
-    """One greedy workspace driven through the C-ABI directly: Sigma = K[:n, :n] sits in a buffer
-    of row pitch lda that starts `shift` doubles into its allocation, everything around it holds
-    SENTINEL; the workspace starts as NaN bytes, so anything read before it is written shows."""
-
-    def __init__(self, K, n, kmax, params, lda=None, shift=0):
-        import torch
-        from vgposp_amd._lib import query
-        self.n, self.kmax, self.lda, self.shift = int(n), int(kmax), int(lda or n), int(shift)
-        self.params = tuple(float(p) for p in params)
-        host = np.full(self.shift + self.n * self.lda, SENTINEL)
-        host[self.shift:].reshape(self.n, self.lda)[:, :self.n] = K[:n, :n]
-        self.host0 = host
-        self.buf = torch.as_tensor(host).cuda()
-        assert self.buf.data_ptr() % 16 == 0
-        self.S = ctypes.c_void_p(self.buf.data_ptr() + 8 * self.shift)
-        self.ws = torch.empty(query("vgposp_greedy_workspace_bytes", self.n, self.kmax),
-                              dtype=torch.uint8, device="cuda")
-        self.ws.fill_(0xFF)
-        self.info = torch.zeros(1, dtype=torch.int32, device="cuda")
-        self.selected = torch.full((self.kmax,), -1, dtype=torch.int64, device="cuda")
-        self.sel_delta = torch.zeros(self.kmax, dtype=torch.float64, device="cuda")
-        self.evals = torch.zeros(self.kmax, dtype=torch.int64, device="cuda")
-        d, p, plen, x, c = (ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64(),
-                            ctypes.c_void_p(), ctypes.c_void_p())
-        self._call("vgposp_greedy_buffers", self._ws(), self.n, self.kmax, ctypes.byref(d),
-                   ctypes.byref(p), ctypes.byref(plen))
-        self._call("vgposp_greedy_xcol", self._ws(), self.n, self.kmax, ctypes.byref(x))
-        self._call("vgposp_greedy_cache", self._ws(), self.n, self.kmax, ctypes.byref(c))
-        assert plen.value == 2 + 2 * self.kmax
-        self.delta = self._view(d, self.n)
-        self.piv = self._view(p, plen.value)
-        self.xcol = self._view(x, self.n)
-        self.cache = self._view(c, self.n)
-        self._keep = []
-
-    def _view(self, ptr, count):
-        import torch
-        off = ptr.value - self.ws.data_ptr()
-        assert 0 <= off and off + 8 * count <= self.ws.numel()
-        return self.ws[off:off + 8 * count].view(torch.float64)
-
-    @staticmethod
-    def _call(name, *args):
-        from vgposp_amd._lib import call
-        return call(name, *args)
-
-    def _ws(self):
-        return ctypes.c_void_p(self.ws.data_ptr())
-
-    @staticmethod
-    def _stream():
-        from vgposp_amd.linalg import _stream
-        return _stream()
-
-    def _p(self, t):
-        return ctypes.c_void_p(t.data_ptr())
-
-    def init(self):
-        self._call("vgposp_greedy_init_ex", self.S, self.n, self.lda, self.kmax, *self.params,
-                   self._p(self.info), self._ws(), self.ws.numel(), self._stream())
-        return self
-
-    def mask(self, blocked):
-        import torch
-        allowed = torch.as_tensor((~np.asarray(blocked, dtype=bool)).astype(np.uint8)).cuda()
-        self._keep.append(allowed)
-        self._call("vgposp_greedy_mask", self._ws(), self.n, self.kmax, self._p(allowed),
-                   self._stream())
-
-    def condition(self, placed, k, batch):
-        import torch
-        from vgposp_amd._lib import query
-        pl = torch.as_tensor(np.asarray(placed, dtype=np.int64)).cuda()
-        nbytes = query("vgposp_greedy_condition_workspace_bytes", self.n, batch)
-        assert nbytes > 0
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
-        scratch.fill_(0xFF)
-        self._keep += [pl, scratch]
-        self._call("vgposp_greedy_condition", self.S, self.n, self.lda, self.kmax, len(placed), k,
-                   batch, self._p(pl), self._p(self.selected), self._ws(), self.ws.numel(),
-                   self._p(scratch), scratch.numel(), self._stream())
-
-    def step(self, r, lazy):
-        self._call("vgposp_greedy_step", self.S, self.n, self.lda, self.kmax, r, int(lazy),
-                   self._p(self.selected), self._p(self.sel_delta), self._p(self.evals),
-                   self._ws(), self.ws.numel(), self._stream())
-
-    def update(self, r, c0, c1, extract=1):
-        self._call("vgposp_greedy_update_ex", self.S, self.n, self.lda, self.kmax, r, c0, c1,
-                   self._p(self.selected), int(extract), self._ws(), self.ws.numel(),
-                   self._stream())
-
-    def select(self, r, lazy, c0, c1):
-        self._call("vgposp_greedy_select", self.n, self.kmax, r, int(lazy), c0, c1,
-                   self._p(self.selected), self._p(self.sel_delta), self._p(self.evals),
-                   self._ws(), self.ws.numel(), self._stream())
-
-    def extract(self, r, own0, own1):
-        self._call("vgposp_greedy_extract", self.S, self.n, self.lda, self.kmax, r, own0, own1,
-                   self._p(self.selected), self._ws(), self.ws.numel(), self._stream())
-
-    def read(self):
-        rec = {k: getattr(self, k).cpu().numpy().copy()
-               for k in ("delta", "piv", "xcol", "cache", "selected", "sel_delta", "evals")}
-        assert int(self.info.cpu()[0]) == 0
-        return rec
-
-    def matrix(self):
-        return self.buf.cpu().numpy().copy()
 
 
 STATE_KEYS = ("delta", "cache", "piv", "selected", "sel_delta", "evals")

@@ -24,7 +24,21 @@ void clear_error();
     }                                                                                 \
   } while (0)
 
-#define VG_CHECK_WS(have, need)                                                       \
+// VG_CHECK_ARG for a check that entries share: `fn` in scope is the entry's name (a helper's
+// __func__ is not).  VG_TRY passes a failed check on.
+#define VG_ARG(cond, idx)                                                             \
+  do {                                                                                \
+    if (!(cond)) {                                                                    \
+      ::vgposp::set_error("%s: bad argument %d (%s)", fn, (idx), #cond);              \
+      return -(idx);                                                                  \
+    }                                                                                 \
+  } while (0)
+#define VG_TRY(expr)                  \
+  do {                                \
+    if (int rc_ = (expr)) return rc_; \
+  } while (0)
+
+#define VG_CHECK_WS(have, need)                                                      \
   do {                                                                                \
     const size_t _need = (need);                                                      \
     if ((have) < _need) {                                                             \
@@ -33,15 +47,17 @@ void clear_error();
     }                                                                                 \
   } while (0)
 
-#define VG_HIP(expr)                                                                  \
+// VG_HIP_AS: reported under the name `fn` (a helper that works for several entries)
+#define VG_HIP_AS(fn, expr)                                                           \
   do {                                                                                \
     hipError_t _e = (expr);                                                           \
     if (_e != hipSuccess) {                                                           \
-      ::vgposp::set_error("%s: HIP error %s at %s:%d", __func__, hipGetErrorString(_e), \
+      ::vgposp::set_error("%s: HIP error %s at %s:%d", fn, hipGetErrorString(_e),     \
                           __FILE__, __LINE__);                                        \
       return VGPOSP_E_HIP;                                                            \
     }                                                                                 \
   } while (0)
+#define VG_HIP(expr) VG_HIP_AS(__func__, expr)
 
 #define VG_LAUNCH_CHECK() VG_HIP(hipGetLastError())
 

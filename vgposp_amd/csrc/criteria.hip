@@ -1598,44 +1598,32 @@ static int crit_step_run(const Sigma& sg, const Cross& cr, int64_t n, int64_t P,
 }
 
 // ---- the entries' argument checks, one per group of arguments ----
-// VG_CHECK_ARG for a check that entries share: `fn` is the entry's name (a helper's __func__ is
-// not), `at` the position of the group's first argument in that entry.
-#define CR_ARG(cond, idx)                                    \
-  do {                                                       \
-    if (!(cond)) {                                           \
-      set_error("%s: bad argument %d (%s)", fn, (idx), #cond); \
-      return -(idx);                                         \
-    }                                                        \
-  } while (0)
-#define CR_TRY(expr)                     \
-  do {                                   \
-    if (int rc_ = (expr)) return rc_;    \
-  } while (0)
+// VG_ARG: `fn` is the entry's name, `at` the position of the group's first argument in that entry.
 
 // (Sigma, n, lda, diag)
 static int check_sigma(const char* fn, int at, const SigmaStored& sg, int64_t n) {
-  CR_ARG(sg.S != nullptr, at);
-  CR_ARG(n >= 1 && n <= CR_NMAX, at + 1);
-  CR_ARG(sg.lda >= n, at + 2);
+  VG_ARG(sg.S != nullptr, at);
+  VG_ARG(n >= 1 && n <= CR_NMAX, at + 1);
+  VG_ARG(sg.lda >= n, at + 2);
   return 0;
 }
 // (kind, X, n, d, amp, ls, site_scale, diag)
 static int check_sigma(const char* fn, int at, const SGen& g, int64_t n) {
-  CR_ARG(g.kind >= VGPOSP_KERNEL_EQ && g.kind <= VGPOSP_KERNEL_MATERN52, at);
-  CR_ARG(g.X != nullptr, at + 1);
-  CR_ARG(n >= 1 && n <= CR_NMAX, at + 2);
-  CR_ARG(g.d >= 1 && g.d <= 8, at + 3);
-  CR_ARG(g.amp != nullptr, at + 4);
-  CR_ARG(g.ls != nullptr, at + 5);
+  VG_ARG(g.kind >= VGPOSP_KERNEL_EQ && g.kind <= VGPOSP_KERNEL_MATERN52, at);
+  VG_ARG(g.X != nullptr, at + 1);
+  VG_ARG(n >= 1 && n <= CR_NMAX, at + 2);
+  VG_ARG(g.d >= 1 && g.d <= 8, at + 3);
+  VG_ARG(g.amp != nullptr, at + 4);
+  VG_ARG(g.ls != nullptr, at + 5);
   return 0;
 }
 // (F, n, s, ldf, noise); nmax: the passes alone go beyond the rounds' CR_NMAX
 static int check_sigma(const char* fn, int at, const SFactor& f, int64_t n,
                        int64_t nmax = CR_NMAX) {
-  CR_ARG(f.F != nullptr, at);
-  CR_ARG(n >= 1 && n <= nmax, at + 1);
-  CR_ARG(f.S >= 1 && f.S <= FC_SMAX, at + 2);
-  CR_ARG(f.ldf >= f.S, at + 3);
+  VG_ARG(f.F != nullptr, at);
+  VG_ARG(n >= 1 && n <= nmax, at + 1);
+  VG_ARG(f.S >= 1 && f.S <= FC_SMAX, at + 2);
+  VG_ARG(f.ldf >= f.S, at + 3);
   return 0;
 }
 
@@ -1643,28 +1631,28 @@ static int check_sigma(const char* fn, int at, const SFactor& f, int64_t n,
 // entries have no Sigma group and carry n inside this one, after P (stored) or after X (generated).
 static int check_cross(const char* fn, int at, const CrossStored& c, int64_t P, int64_t n,
                        bool with_n = false) {
-  CR_ARG(c.R != nullptr, at);
-  CR_ARG(P >= 1 && P <= CRX_PMAX, at + 1);
+  VG_ARG(c.R != nullptr, at);
+  VG_ARG(P >= 1 && P <= CRX_PMAX, at + 1);
   if (with_n) {
-    CR_ARG(n >= 1 && n <= CR_NMAX, at + 2);
+    VG_ARG(n >= 1 && n <= CR_NMAX, at + 2);
     ++at;
   }
-  CR_ARG(c.ldr >= n, at + 2);
+  VG_ARG(c.ldr >= n, at + 2);
   return 0;
 }
 static int check_cross(const char* fn, int at, const KGen& g, int64_t P, int64_t n,
                        bool with_n = false) {
-  CR_ARG(g.kind >= VGPOSP_KERNEL_EQ && g.kind <= VGPOSP_KERNEL_MATERN52, at);
-  CR_ARG(g.Xt != nullptr, at + 1);
-  CR_ARG(P >= 1 && P <= CRX_PMAX, at + 2);
-  CR_ARG(g.X != nullptr, at + 3);
+  VG_ARG(g.kind >= VGPOSP_KERNEL_EQ && g.kind <= VGPOSP_KERNEL_MATERN52, at);
+  VG_ARG(g.Xt != nullptr, at + 1);
+  VG_ARG(P >= 1 && P <= CRX_PMAX, at + 2);
+  VG_ARG(g.X != nullptr, at + 3);
   if (with_n) {
-    CR_ARG(n >= 1 && n <= CR_NMAX, at + 4);
+    VG_ARG(n >= 1 && n <= CR_NMAX, at + 4);
     ++at;
   }
-  CR_ARG(g.d >= 1 && g.d <= 8, at + 4);
-  CR_ARG(g.amp != nullptr, at + 5);
-  CR_ARG(g.ls != nullptr, at + 6);
+  VG_ARG(g.d >= 1 && g.d <= 8, at + 4);
+  VG_ARG(g.amp != nullptr, at + 5);
+  VG_ARG(g.ls != nullptr, at + 6);
   return 0;
 }
 
@@ -1672,39 +1660,39 @@ static int check_cross(const char* fn, int at, const KGen& g, int64_t P, int64_t
 // criterion == nullptr
 static int check_rule(const char* fn, int at, int kmax, int64_t n, const int* criterion,
                       double threshold) {
-  CR_ARG(kmax >= 1 && kmax <= n, at);
+  VG_ARG(kmax >= 1 && kmax <= n, at);
   if (criterion) {
-    CR_ARG(*criterion == VGPOSP_CRIT_VARIANCE || *criterion == VGPOSP_CRIT_ENTROPY, at + 1);
+    VG_ARG(*criterion == VGPOSP_CRIT_VARIANCE || *criterion == VGPOSP_CRIT_ENTROPY, at + 1);
     ++at;
   }
-  CR_ARG(threshold >= 0.0, at + 1);
+  VG_ARG(threshold >= 0.0, at + 1);
   return 0;
 }
 
 // (kmax, round, forced, j, selected, sel_delta) of a step
 static int check_round(const char* fn, int at, int kmax, int64_t n, int round,
                        const int64_t* forced, int64_t j, const int64_t* selected) {
-  CR_ARG(kmax >= 1 && kmax <= n, at);
-  CR_ARG(round >= 0 && round < kmax, at + 1);
-  CR_ARG(forced == nullptr || j >= 0, at + 3);
-  CR_ARG(selected != nullptr, at + 4);
+  VG_ARG(kmax >= 1 && kmax <= n, at);
+  VG_ARG(round >= 0 && round < kmax, at + 1);
+  VG_ARG(forced == nullptr || j >= 0, at + 3);
+  VG_ARG(selected != nullptr, at + 4);
   return 0;
 }
 
 // (ws, n[, mid], kmax) of a _buffers entry; mid: P or s where the entry has one
 static int check_buffers(const char* fn, const void* ws, int64_t n, const int64_t* mid, int kmax) {
-  CR_ARG(ws != nullptr, 1);
-  CR_ARG(n >= 1, 2);
-  if (mid) CR_ARG(*mid >= 1, 3);
-  CR_ARG(kmax >= 1, mid ? 4 : 3);
+  VG_ARG(ws != nullptr, 1);
+  VG_ARG(n >= 1, 2);
+  if (mid) VG_ARG(*mid >= 1, 3);
+  VG_ARG(kmax >= 1, mid ? 4 : 3);
   return 0;
 }
 
 // (x, y, ws, ws_bytes) of a pass entry, x at `at`: a missing workspace is VGPOSP_E_WS there
 static int check_pass(const char* fn, int at, const double* x, const double* y, const void* ws,
                       size_t ws_bytes, size_t need) {
-  CR_ARG(x != nullptr, at);
-  CR_ARG(y != nullptr, at + 1);
+  VG_ARG(x != nullptr, at);
+  VG_ARG(y != nullptr, at + 1);
   if (ws == nullptr) {
     set_error("%s: workspace is null", fn);
     return VGPOSP_E_WS;
@@ -1744,9 +1732,9 @@ static int symv_entry(const char* fn, const double* A, int64_t n, int64_t lda, c
                       const double* x, double* y, void* ws, size_t ws_bytes, void* stream) {
   clear_error();
   if (n == 0) return 0;
-  CR_TRY(check_sigma(fn, 1, SigmaStored{A, lda, diag}, n));
+  VG_TRY(check_sigma(fn, 1, SigmaStored{A, lda, diag}, n));
   const SymvWS w = symv_layout(ws, n);
-  CR_TRY(check_pass(fn, 5, x, y, ws, ws_bytes, w.bytes));
+  VG_TRY(check_pass(fn, 5, x, y, ws, ws_bytes, w.bytes));
   symv_launch<SQ>(A, n, lda, diag, x, y, w, nullptr, as_stream(stream));
   VG_LAUNCH_CHECK();
   return 0;
@@ -1775,8 +1763,8 @@ extern "C" int vgposp_crit_init(const double* Sigma, int64_t n, int64_t lda, con
                                 void* ws, size_t ws_bytes, void* stream) {
   clear_error();
   const SigmaStored sg{Sigma, lda, diag};
-  CR_TRY(check_sigma(__func__, 1, sg, n));
-  CR_TRY(check_rule(__func__, 5, kmax, n, &criterion, threshold));
+  VG_TRY(check_sigma(__func__, 1, sg, n));
+  VG_TRY(check_rule(__func__, 5, kmax, n, &criterion, threshold));
   VG_CHECK_ARG(ws != nullptr, 10);
   const CritWS w = crit_layout(ws, n, kmax);
   VG_CHECK_WS(ws_bytes, w.bytes);
@@ -1790,8 +1778,8 @@ extern "C" int vgposp_crit_step(const double* Sigma, int64_t n, int64_t lda, con
                                 void* stream) {
   clear_error();
   const SigmaStored sg{Sigma, lda, diag};
-  CR_TRY(check_sigma(__func__, 1, sg, n));
-  CR_TRY(check_round(__func__, 5, kmax, n, round, forced, j, selected));
+  VG_TRY(check_sigma(__func__, 1, sg, n));
+  VG_TRY(check_round(__func__, 5, kmax, n, round, forced, j, selected));
   VG_CHECK_ARG(ws != nullptr, 11);
   const CritWS w = crit_layout(ws, n, kmax);
   VG_CHECK_WS(ws_bytes, w.bytes);
@@ -1802,7 +1790,7 @@ extern "C" int vgposp_crit_step(const double* Sigma, int64_t n, int64_t lda, con
 extern "C" int vgposp_crit_buffers(void* ws, int64_t n, int kmax, double** nom, double** score,
                                    double** delta, double** W) {
   clear_error();
-  CR_TRY(check_buffers(__func__, ws, n, nullptr, kmax));
+  VG_TRY(check_buffers(__func__, ws, n, nullptr, kmax));
   crit_outputs(crit_layout(ws, n, kmax), nom, score, delta, W);
   return 0;
 }
@@ -1817,8 +1805,8 @@ static int gemv_t_entry(const char* fn, const double* R, int64_t P, int64_t n, i
                         const double* x, double* y, void* ws, size_t ws_bytes, void* stream) {
   clear_error();
   if (P == 0 || n == 0) return 0;
-  CR_TRY(check_cross(fn, 1, CrossStored{R, ldr}, P, n, true));
-  CR_TRY(check_pass(fn, 5, x, y, ws, ws_bytes, gemv_t_bytes(P, n)));
+  VG_TRY(check_cross(fn, 1, CrossStored{R, ldr}, P, n, true));
+  VG_TRY(check_pass(fn, 5, x, y, ws, ws_bytes, gemv_t_bytes(P, n)));
   gemv_t_launch<SQ>(R, P, n, ldr, x, y, static_cast<double*>(ws), nullptr, as_stream(stream));
   VG_LAUNCH_CHECK();
   return 0;
@@ -1847,9 +1835,9 @@ extern "C" int vgposp_critx_init(const double* Sigma, int64_t n, int64_t lda, co
   clear_error();
   const SigmaStored sg{Sigma, lda, diag};
   const CrossStored cr{R, ldr};
-  CR_TRY(check_sigma(__func__, 1, sg, n));
-  CR_TRY(check_cross(__func__, 5, cr, P, n));
-  CR_TRY(check_rule(__func__, 9, kmax, n, nullptr, threshold));
+  VG_TRY(check_sigma(__func__, 1, sg, n));
+  VG_TRY(check_cross(__func__, 5, cr, P, n));
+  VG_TRY(check_rule(__func__, 9, kmax, n, nullptr, threshold));
   VG_CHECK_ARG(ws != nullptr, 12);
   const CritXWS w = critx_layout(ws, n, P, kmax, gemv_t_bytes(P, n));
   VG_CHECK_WS(ws_bytes, w.bytes);
@@ -1864,9 +1852,9 @@ extern "C" int vgposp_critx_step(const double* Sigma, int64_t n, int64_t lda, co
   clear_error();
   const SigmaStored sg{Sigma, lda, diag};
   const CrossStored cr{R, ldr};
-  CR_TRY(check_sigma(__func__, 1, sg, n));
-  CR_TRY(check_cross(__func__, 5, cr, P, n));
-  CR_TRY(check_round(__func__, 8, kmax, n, round, forced, j, selected));
+  VG_TRY(check_sigma(__func__, 1, sg, n));
+  VG_TRY(check_cross(__func__, 5, cr, P, n));
+  VG_TRY(check_round(__func__, 8, kmax, n, round, forced, j, selected));
   VG_CHECK_ARG(ws != nullptr, 14);
   const CritXWS w = critx_layout(ws, n, P, kmax, gemv_t_bytes(P, n));
   VG_CHECK_WS(ws_bytes, w.bytes);
@@ -1876,7 +1864,7 @@ extern "C" int vgposp_critx_step(const double* Sigma, int64_t n, int64_t lda, co
 extern "C" int vgposp_critx_buffers(void* ws, int64_t n, int64_t P, int kmax, double** nom,
                                     double** score, double** delta, double** W, double** U) {
   clear_error();
-  CR_TRY(check_buffers(__func__, ws, n, &P, kmax));
+  VG_TRY(check_buffers(__func__, ws, n, &P, kmax));
   critx_outputs(critx_layout(ws, n, P, kmax, gemv_t_bytes(P, n)), nom, score, delta, W, U);
   return 0;
 }
@@ -1892,8 +1880,8 @@ static int kgemv_t_entry(const char* fn, const KGen& g, int64_t P, int64_t n, co
                          double* y, void* ws, size_t ws_bytes, void* stream) {
   clear_error();
   if (P == 0 || n == 0) return 0;
-  CR_TRY(check_cross(fn, 1, g, P, n, true));
-  CR_TRY(check_pass(fn, 11, x, y, ws, ws_bytes, kgemv_t_bytes(P, n)));
+  VG_TRY(check_cross(fn, 1, g, P, n, true));
+  VG_TRY(check_pass(fn, 11, x, y, ws, ws_bytes, kgemv_t_bytes(P, n)));
   kgemv_t_launch<SQ>(g, P, n, x, y, static_cast<double*>(ws), nullptr, as_stream(stream));
   VG_LAUNCH_CHECK();
   return 0;
@@ -1931,9 +1919,9 @@ extern "C" int vgposp_critk_init(const double* Sigma, int64_t n, int64_t lda, co
   clear_error();
   const SigmaStored sg{Sigma, lda, diag};
   const KGen g{kind, d, Xt, X, amp, ls, target_scale, site_scale};
-  CR_TRY(check_sigma(__func__, 1, sg, n));
-  CR_TRY(check_cross(__func__, 5, g, P, n));
-  CR_TRY(check_rule(__func__, 15, kmax, n, nullptr, threshold));
+  VG_TRY(check_sigma(__func__, 1, sg, n));
+  VG_TRY(check_cross(__func__, 5, g, P, n));
+  VG_TRY(check_rule(__func__, 15, kmax, n, nullptr, threshold));
   VG_CHECK_ARG(ws != nullptr, 18);
   const CritXWS w = critx_layout(ws, n, P, kmax, kgemv_t_bytes(P, n));
   VG_CHECK_WS(ws_bytes, w.bytes);
@@ -1950,9 +1938,9 @@ extern "C" int vgposp_critk_step(const double* Sigma, int64_t n, int64_t lda, co
   clear_error();
   const SigmaStored sg{Sigma, lda, diag};
   const KGen g{kind, d, Xt, X, amp, ls, target_scale, site_scale};
-  CR_TRY(check_sigma(__func__, 1, sg, n));
-  CR_TRY(check_cross(__func__, 5, g, P, n));
-  CR_TRY(check_round(__func__, 14, kmax, n, round, forced, j, selected));
+  VG_TRY(check_sigma(__func__, 1, sg, n));
+  VG_TRY(check_cross(__func__, 5, g, P, n));
+  VG_TRY(check_round(__func__, 14, kmax, n, round, forced, j, selected));
   VG_CHECK_ARG(ws != nullptr, 20);
   const CritXWS w = critx_layout(ws, n, P, kmax, kgemv_t_bytes(P, n));
   VG_CHECK_WS(ws_bytes, w.bytes);
@@ -1962,7 +1950,7 @@ extern "C" int vgposp_critk_step(const double* Sigma, int64_t n, int64_t lda, co
 extern "C" int vgposp_critk_buffers(void* ws, int64_t n, int64_t P, int kmax, double** nom,
                                     double** score, double** delta, double** W, double** U) {
   clear_error();
-  CR_TRY(check_buffers(__func__, ws, n, &P, kmax));
+  VG_TRY(check_buffers(__func__, ws, n, &P, kmax));
   critx_outputs(critx_layout(ws, n, P, kmax, kgemv_t_bytes(P, n)), nom, score, delta, W, U);
   return 0;
 }
@@ -1978,9 +1966,9 @@ static int ksymv_entry(const char* fn, const SGen& g, int64_t n, const double* x
                        void* ws, size_t ws_bytes, void* stream) {
   clear_error();
   if (n == 0) return 0;
-  CR_TRY(check_sigma(fn, 1, g, n));
+  VG_TRY(check_sigma(fn, 1, g, n));
   const KSymvWS w = ksymv_layout(ws, n);
-  CR_TRY(check_pass(fn, 9, x, y, ws, ws_bytes, w.bytes));
+  VG_TRY(check_pass(fn, 9, x, y, ws, ws_bytes, w.bytes));
   ksymv_launch<SQ>(g, n, x, y, w, nullptr, as_stream(stream));
   VG_LAUNCH_CHECK();
   return 0;
@@ -2018,8 +2006,8 @@ extern "C" int vgposp_critg_init(int kind, const double* X, int64_t n, int d, co
                                  void* ws, size_t ws_bytes, void* stream) {
   clear_error();
   const SGen sg{kind, d, X, amp, ls, site_scale, diag};
-  CR_TRY(check_sigma(__func__, 1, sg, n));
-  CR_TRY(check_rule(__func__, 9, kmax, n, &criterion, threshold));
+  VG_TRY(check_sigma(__func__, 1, sg, n));
+  VG_TRY(check_rule(__func__, 9, kmax, n, &criterion, threshold));
   VG_CHECK_ARG(ws != nullptr, 14);
   const CritWS w = critg_layout(ws, n, kmax);
   VG_CHECK_WS(ws_bytes, w.bytes);
@@ -2034,8 +2022,8 @@ extern "C" int vgposp_critg_step(int kind, const double* X, int64_t n, int d, co
                                  void* stream) {
   clear_error();
   const SGen sg{kind, d, X, amp, ls, site_scale, diag};
-  CR_TRY(check_sigma(__func__, 1, sg, n));
-  CR_TRY(check_round(__func__, 9, kmax, n, round, forced, j, selected));
+  VG_TRY(check_sigma(__func__, 1, sg, n));
+  VG_TRY(check_round(__func__, 9, kmax, n, round, forced, j, selected));
   VG_CHECK_ARG(ws != nullptr, 15);
   const CritWS w = critg_layout(ws, n, kmax);
   VG_CHECK_WS(ws_bytes, w.bytes);
@@ -2046,7 +2034,7 @@ extern "C" int vgposp_critg_step(int kind, const double* X, int64_t n, int d, co
 extern "C" int vgposp_critg_buffers(void* ws, int64_t n, int kmax, double** nom, double** score,
                                     double** delta, double** W) {
   clear_error();
-  CR_TRY(check_buffers(__func__, ws, n, nullptr, kmax));
+  VG_TRY(check_buffers(__func__, ws, n, nullptr, kmax));
   crit_outputs(critg_layout(ws, n, kmax), nom, score, delta, W);
   return 0;
 }
@@ -2071,8 +2059,8 @@ extern "C" int vgposp_critgk_init(int64_t n, const double* diag, int kind, const
   clear_error();
   const KGen g{kind, d, Xt, X, amp, ls, target_scale, site_scale};
   VG_CHECK_ARG(n >= 1 && n <= CR_NMAX, 1);
-  CR_TRY(check_cross(__func__, 3, g, P, n));
-  CR_TRY(check_rule(__func__, 13, kmax, n, nullptr, threshold));
+  VG_TRY(check_cross(__func__, 3, g, P, n));
+  VG_TRY(check_rule(__func__, 13, kmax, n, nullptr, threshold));
   VG_CHECK_ARG(ws != nullptr, 16);
   const CritXWS w = critgk_layout(ws, n, P, kmax);
   VG_CHECK_WS(ws_bytes, w.bytes);
@@ -2089,8 +2077,8 @@ extern "C" int vgposp_critgk_step(int64_t n, const double* diag, int kind, const
   clear_error();
   const KGen g{kind, d, Xt, X, amp, ls, target_scale, site_scale};
   VG_CHECK_ARG(n >= 1 && n <= CR_NMAX, 1);
-  CR_TRY(check_cross(__func__, 3, g, P, n));
-  CR_TRY(check_round(__func__, 12, kmax, n, round, forced, j, selected));
+  VG_TRY(check_cross(__func__, 3, g, P, n));
+  VG_TRY(check_round(__func__, 12, kmax, n, round, forced, j, selected));
   VG_CHECK_ARG(ws != nullptr, 18);
   const CritXWS w = critgk_layout(ws, n, P, kmax);
   VG_CHECK_WS(ws_bytes, w.bytes);
@@ -2101,7 +2089,7 @@ extern "C" int vgposp_critgk_step(int64_t n, const double* diag, int kind, const
 extern "C" int vgposp_critgk_buffers(void* ws, int64_t n, int64_t P, int kmax, double** nom,
                                      double** score, double** delta, double** W, double** U) {
   clear_error();
-  CR_TRY(check_buffers(__func__, ws, n, &P, kmax));
+  VG_TRY(check_buffers(__func__, ws, n, &P, kmax));
   critx_outputs(critgk_layout(ws, n, P, kmax), nom, score, delta, W, U);
   return 0;
 }
@@ -2117,12 +2105,12 @@ static int fsymv_entry(const char* fn, const SFactor& f, int64_t n, const double
                        void* ws, size_t ws_bytes, void* stream) {
   clear_error();
   if (n == 0) return 0;
-  CR_TRY(check_sigma(fn, 1, f, n, FC_NMAX));
+  VG_TRY(check_sigma(fn, 1, f, n, FC_NMAX));
   const FacWS w = fac_layout(ws, n, f.S);
-  CR_TRY(check_pass(fn, 6, x, y, ws, ws_bytes, w.bytes));
+  VG_TRY(check_pass(fn, 6, x, y, ws, ws_bytes, w.bytes));
   hipStream_t s = as_stream(stream);
   if (SQ) {
-    CR_TRY(factor_diag_launch(f, n, w.dg, s));
+    VG_TRY(factor_diag_launch(f, n, w.dg, s));
     return factor_symv_sq_launch(f, n, x, y, w, s);
   }
   return factor_symv_launch(f, n, x, y, w, nullptr, s);
@@ -2155,8 +2143,8 @@ extern "C" int vgposp_critf_init(const double* F, int64_t n, int64_t s, int64_t 
                                  void* ws, size_t ws_bytes, void* stream) {
   clear_error();
   const SFactor sg{F, s, ldf, noise};
-  CR_TRY(check_sigma(__func__, 1, sg, n));
-  CR_TRY(check_rule(__func__, 6, kmax, n, &criterion, threshold));
+  VG_TRY(check_sigma(__func__, 1, sg, n));
+  VG_TRY(check_rule(__func__, 6, kmax, n, &criterion, threshold));
   VG_CHECK_ARG(ws != nullptr, 11);
   const CritWS w = critf_layout(ws, n, s, kmax);
   VG_CHECK_WS(ws_bytes, w.bytes);
@@ -2170,8 +2158,8 @@ extern "C" int vgposp_critf_step(const double* F, int64_t n, int64_t s, int64_t 
                                  size_t ws_bytes, void* stream) {
   clear_error();
   const SFactor sg{F, s, ldf, noise};
-  CR_TRY(check_sigma(__func__, 1, sg, n));
-  CR_TRY(check_round(__func__, 6, kmax, n, round, forced, j, selected));
+  VG_TRY(check_sigma(__func__, 1, sg, n));
+  VG_TRY(check_round(__func__, 6, kmax, n, round, forced, j, selected));
   VG_CHECK_ARG(ws != nullptr, 12);
   const CritWS w = critf_layout(ws, n, s, kmax);
   VG_CHECK_WS(ws_bytes, w.bytes);
@@ -2182,7 +2170,7 @@ extern "C" int vgposp_critf_step(const double* F, int64_t n, int64_t s, int64_t 
 extern "C" int vgposp_critf_buffers(void* ws, int64_t n, int64_t s, int kmax, double** nom,
                                     double** score, double** delta, double** W) {
   clear_error();
-  CR_TRY(check_buffers(__func__, ws, n, &s, kmax));
+  VG_TRY(check_buffers(__func__, ws, n, &s, kmax));
   crit_outputs(critf_layout(ws, n, s, kmax), nom, score, delta, W);
   return 0;
 }

@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cfloat>
+#include <type_traits>
 
 #include "dense.h"
 
@@ -688,439 +689,11 @@ __global__ __launch_bounds__(CH) void greedy_select_kernel(int64_t n, int round,
   }
 }
 
-}  // namespace vgposp
-
-using namespace vgposp;
-
-extern "C" size_t vgposp_greedy_workspace_bytes(int64_t n, int kmax) {
-  if (n <= 0 || kmax <= 0) return 0;
-  return greedy_layout(nullptr, n, kmax).bytes;
-}
-
-// Grid of a mat-vec kernel over columns [c0, c1) (the tile origin is even: column pairs), and
-// whether it may load a column pair with one 16-byte access.
-static dim3 trmv_grid(int64_t n, int64_t c0, int64_t c1) {
-  return dim3((unsigned)ceil_div(c1 - (c0 & ~(int64_t)1), TRMV_COLS), (unsigned)ceil_div(n, RC));
-}
-static int trmv_vec(const double* M, int64_t lda) {
-  return (reinterpret_cast<uintptr_t>(M) % 16 == 0) && (lda % 2 == 0);
-}
-
-// Q_ii = |M e_i|^2 for columns [c0, c1) -> part (reduced in the round-0 update)
-static void launch_colsq(const double* M, int64_t n, int64_t lda, int64_t c0, int64_t c1,
-                         const GreedyWS& w, hipStream_t s) {
-  const bool whole = c0 == 0 && c1 == n;  // a slab reports no algorithmic figures
-  const double tri = 0.5 * (double)n * (n + 1);
-  ProfScope ps("greedy_colsq", s, whole ? 2.0 * tri : 0.0,
-               whole ? 8.0 * (tri + (double)ceil_div(n, RC) * n) : 0.0);
-  hipLaunchKernelGGL(greedy_trmv_kernel<true>, trmv_grid(n, c0, c1), dim3(CT), 0, s, M, n, lda,
-                     nullptr, 0, nullptr, w.part, c0, c1, trmv_vec(M, lda));
-}
-
-// The checks of vgposp_greedy_prepare, then what it does: `info` cleared and the init kernel.
-static int greedy_prepare(const char* fn, double* Sigma, int64_t n, int64_t lda, int kmax,
-                          double jitter, double threshold, double cache_init, int* info, void* ws,
-                          size_t ws_bytes, hipStream_t s, GreedyWS* w) {
-  if (Sigma == nullptr) { set_error("%s: bad argument 1", fn); return -1; }
-  if (!(n >= 1 && n <= (int64_t)MAXCH * CH)) { set_error("%s: bad argument 2", fn); return -2; }
-  if (lda < n) { set_error("%s: bad argument 3", fn); return -3; }
-  if (!(kmax >= 1 && kmax <= n)) { set_error("%s: bad argument 4", fn); return -4; }
-  if (!(jitter >= 0.0 && jitter < 1e300)) { set_error("%s: bad argument 5", fn); return -5; }
-  if (!(threshold >= 0.0)) { set_error("%s: bad argument 6", fn); return -6; }
-  if (cache_init != cache_init) { set_error("%s: bad argument 7", fn); return -7; }
-  if (info == nullptr) { set_error("%s: info is null", fn); return -8; }
-  if (ws == nullptr) { set_error("%s: workspace is null", fn); return VGPOSP_E_WS; }
-  *w = greedy_layout(ws, n, kmax);
-  if (ws_bytes < w->bytes) {
-    set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, w->bytes);
-    return VGPOSP_E_WS;
-  }
-  VG_HIP(vg_memset(info, 0, sizeof(int), s));
-  hipLaunchKernelGGL(greedy_init_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, Sigma,
-                     n, lda, jitter, threshold, cache_init, *w);
-  VG_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int vgposp_greedy_init_ex(double* Sigma, int64_t n, int64_t lda, int kmax,
-                                     double jitter, double threshold, double cache_init, int* info,
-                                     void* ws, size_t ws_bytes, void* stream) {
-  clear_error();
-  VG_CHECK_ARG(info != nullptr, 8);  // by position here; the workspace text names the family
-  VG_CHECK_ARG(ws != nullptr, 9);
-  hipStream_t s = as_stream(stream);
-  GreedyWS w;
-  int rc = greedy_prepare("vgposp_greedy_init", Sigma, n, lda, kmax, jitter, threshold,
-                          cache_init, info, ws, ws_bytes, s, &w);
-  if (rc) return rc;
-  // early: after a failed pivot (a singular cov_vv) every later launch of the factorization and
-  // inverse reads `info` on the device and exits, so the host's jitter retry does not pay for a
-  // whole O(n^3) factorization + inverse first — and nothing here synchronises the host
-  rc = potrf_one(Sigma, n, lda, /*invert=*/1, nullptr, info, greedy_fact_ws(ws, w, n), s,
-                 /*early=*/true);
-  if (rc) return rc;
-  launch_colsq(Sigma, n, lda, 0, n, w, s);
-  VG_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int vgposp_greedy_init(double* Sigma, int64_t n, int64_t lda, int kmax, int* info,
-                                  void* ws, size_t ws_bytes, void* stream) {
-  clear_error();
-  VG_CHECK_ARG(info != nullptr, 5);  // argument numbers of this signature
-  VG_CHECK_ARG(ws != nullptr, 6);
-  return vgposp_greedy_init_ex(Sigma, n, lda, kmax, 0.0, DELTA_EPS, __builtin_huge_val(), info,
-                               ws, ws_bytes, stream);
-}
-
-static int greedy_check(const char* fn, const double* Sigma, int64_t n, int64_t lda, int kmax,
-                        int round, void* ws, size_t ws_bytes, GreedyWS* w) {
-  if (Sigma == nullptr) { set_error("%s: bad argument 1", fn); return -1; }
-  if (!(n >= 1 && n <= (int64_t)MAXCH * CH)) { set_error("%s: bad argument 2", fn); return -2; }
-  if (lda < n) { set_error("%s: bad argument 3", fn); return -3; }
-  if (!(kmax >= 1 && kmax <= n)) { set_error("%s: bad argument 4", fn); return -4; }
-  if (!(round >= 0 && round < kmax)) { set_error("%s: bad argument 5", fn); return -5; }
-  if (ws == nullptr) { set_error("%s: workspace is null", fn); return VGPOSP_E_WS; }
-  *w = greedy_layout(ws, n, kmax);
-  if (ws_bytes < w->bytes) {
-    set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, w->bytes);
-    return VGPOSP_E_WS;
-  }
-  return 0;
-}
-
-extern "C" int vgposp_greedy_update_ex(const double* Sigma, int64_t n, int64_t lda, int kmax,
-                                       int round, int64_t c0, int64_t c1, const int64_t* selected,
-                                       int extract, void* ws, size_t ws_bytes, void* stream) {
-  clear_error();
-  GreedyWS w;
-  int rc = greedy_check(__func__, Sigma, n, lda, kmax, round, ws, ws_bytes, &w);
-  if (rc) return rc;
-  VG_CHECK_ARG(c0 >= 0 && c0 <= c1 && c1 <= n, 6);
-  VG_CHECK_ARG(selected != nullptr || round == 0, 8);
-  hipStream_t s = as_stream(stream);
-  if (c1 == c0) return 0;
-  if (round > 0) {
-    if (extract) {
-      hipLaunchKernelGGL(greedy_extract_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s,
-                         Sigma, n, lda, selected, round, w.xcol, (int64_t)0, n);
-      VG_LAUNCH_CHECK();
-    }
-    // algorithmic: the lower triangle of L^-1 in rows >= a, columns [c0, c1) (a is device-side;
-    // bench.py recomputes the exact bytes from the selections)
-    ProfScope ps("greedy_trmv", s, 0.0, 8.0 * (0.5 * (double)n * (n + 1) + 2.0 * n));
-    hipLaunchKernelGGL(greedy_trmv_kernel<false>, trmv_grid(n, c0, c1), dim3(CT), 0, s, Sigma, n,
-                       lda, selected, round, w.xcol, w.part, c0, c1, trmv_vec(Sigma, lda));
-    VG_LAUNCH_CHECK();
-  }
-  {
-    ProfScope psu("greedy_update", s, 0.0, 8.0 * (double)(c1 - c0) * (6 + 2.0 * round));
-    const int64_t b0 = c0 / CH, b1 = ceil_div(c1, CH);
-    // grid covers the CH-aligned blocks spanning [c0, c1); blockIdx is offset by b0
-    hipLaunchKernelGGL(greedy_update_kernel, dim3((unsigned)(b1 - b0)), dim3(CH), 0, s, Sigma, n,
-                       lda, selected, round, w, c0, c1, 0);
-    VG_LAUNCH_CHECK();
-  }
-  return 0;
-}
-
-extern "C" int vgposp_greedy_update(const double* Sigma, int64_t n, int64_t lda, int kmax,
-                                    int round, int64_t c0, int64_t c1, const int64_t* selected,
-                                    void* ws, size_t ws_bytes, void* stream) {
-  return vgposp_greedy_update_ex(Sigma, n, lda, kmax, round, c0, c1, selected, 1, ws, ws_bytes,
-                                 stream);
-}
-
-extern "C" int vgposp_greedy_extract(const double* Sigma, int64_t n, int64_t lda, int kmax,
-                                     int round, int64_t own0, int64_t own1,
-                                     const int64_t* selected, void* ws, size_t ws_bytes,
-                                     void* stream) {
-  clear_error();
-  GreedyWS w;
-  int rc = greedy_check(__func__, Sigma, n, lda, kmax, round, ws, ws_bytes, &w);
-  if (rc) return rc;
-  VG_CHECK_ARG(round >= 1, 5);
-  VG_CHECK_ARG(own0 >= 0 && own0 <= own1 && own1 <= n, 6);
-  VG_CHECK_ARG(selected != nullptr, 8);
-  hipStream_t s = as_stream(stream);
-  hipLaunchKernelGGL(greedy_extract_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s,
-                     Sigma, n, lda, selected, round, w.xcol, own0, own1);
-  VG_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" size_t vgposp_greedy_slab_tmp_bytes(int64_t n, int64_t c0, int64_t c1) {
-  if (n <= 0 || c0 < 0 || c1 <= c0 || c1 > n) return 0;
-  return partial_inverse_tmp_bytes(n, c0, c1);
-}
-
-extern "C" int vgposp_greedy_prepare(double* Sigma, int64_t n, int64_t lda, int kmax,
-                                     double jitter, double threshold, double cache_init, int* info,
-                                     void* ws, size_t ws_bytes, void* stream) {
-  clear_error();
-  GreedyWS w;
-  return greedy_prepare(__func__, Sigma, n, lda, kmax, jitter, threshold, cache_init, info, ws,
-                        ws_bytes, as_stream(stream), &w);
-}
-
-// The preamble of the entry points that only look into a workspace: (ws, n, kmax) -> its layout.
-static int greedy_ws(const char* fn, void* ws, int64_t n, int kmax, GreedyWS* w) {
-  clear_error();
-  if (ws == nullptr) { set_error("%s: bad argument 1 (ws != nullptr)", fn); return -1; }
-  if (!(n >= 1)) { set_error("%s: bad argument 2 (n >= 1)", fn); return -2; }
-  if (!(kmax >= 1)) { set_error("%s: bad argument 3 (kmax >= 1)", fn); return -3; }
-  *w = greedy_layout(ws, n, kmax);
-  return 0;
-}
-
-extern "C" int vgposp_greedy_fact_ws(void* ws, int64_t n, int kmax, void** fws,
-                                     size_t* fws_bytes) {
-  GreedyWS w;
-  if (int rc = greedy_ws(__func__, ws, n, kmax, &w)) return rc;
-  VG_CHECK_ARG(fws != nullptr && fws_bytes != nullptr, 4);
-  *fws = greedy_fact_ws(ws, w, n);
-  *fws_bytes = potrf_ws_bytes(n);
-  return 0;
-}
-
-extern "C" int vgposp_greedy_finish_slab(double* Sigma, int64_t n, int64_t lda, int kmax,
-                                         int64_t c0, int64_t c1, double* tmp, size_t tmp_bytes,
-                                         void* ws, size_t ws_bytes, void* stream) {
-  clear_error();
-  VG_CHECK_ARG(Sigma != nullptr, 1);
-  VG_CHECK_ARG(n >= 1 && n <= (int64_t)MAXCH * CH, 2);
-  VG_CHECK_ARG(lda >= n, 3);
-  VG_CHECK_ARG(kmax >= 1 && kmax <= n, 4);
-  VG_CHECK_ARG(c0 >= 0 && c0 <= c1 && c0 % 128 == 0, 5);
-  VG_CHECK_ARG(c1 <= n && (c1 % 128 == 0 || c1 == n), 6);
-  VG_CHECK_ARG(c1 == c0 || (tmp != nullptr && tmp_bytes >= partial_inverse_tmp_bytes(n, c0, c1)),
-               7);
-  VG_CHECK_ARG(ws != nullptr, 9);
-  GreedyWS w = greedy_layout(ws, n, kmax);
-  VG_CHECK_WS(ws_bytes, w.bytes);
-  if (c1 == c0) return 0;
-  hipStream_t s = as_stream(stream);
-  // M changes here: no cached column survives (header, table and the "is cached" bytes)
-  VG_HIP(vg_memset(w.spec, 0, (size_t)(SPEC_HDR + 2 * spec_slots(kmax)) * 8 + n, s));
-  int rc = partial_inverse(Sigma, n, lda, c0, c1, tmp, greedy_fact_ws(ws, w, n), s);
-  if (rc) return rc;
-  launch_colsq(Sigma, n, lda, c0, c1, w, s);
-  VG_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int vgposp_greedy_init_slab(double* Sigma, int64_t n, int64_t lda, int kmax,
-                                       double jitter, double threshold, double cache_init,
-                                       int64_t c0, int64_t c1, double* tmp, size_t tmp_bytes,
-                                       int* info, void* ws, size_t ws_bytes, void* stream) {
-  clear_error();
-  VG_CHECK_ARG(c0 >= 0 && c0 <= c1 && c0 % 128 == 0, 8);
-  VG_CHECK_ARG(c1 <= n && (c1 % 128 == 0 || c1 == n), 9);
-  VG_CHECK_ARG(c1 == c0 || (tmp != nullptr && tmp_bytes >= partial_inverse_tmp_bytes(n, c0, c1)),
-               10);
-  int rc = vgposp_greedy_prepare(Sigma, n, lda, kmax, jitter, threshold, cache_init, info, ws,
-                                 ws_bytes, stream);
-  if (rc) return rc;
-  GreedyWS w = greedy_layout(ws, n, kmax);
-  // (the slab path stays classical, like the sharded factorization it stands in for)
-  if ((rc = potrf_one(Sigma, n, lda, /*invert=*/0, nullptr, info, greedy_fact_ws(ws, w, n),
-                      as_stream(stream), /*early=*/false, /*strassen=*/false)))
-    return rc;
-  return vgposp_greedy_finish_slab(Sigma, n, lda, kmax, c0, c1, tmp, tmp_bytes, ws, ws_bytes,
-                                   stream);
-}
-
-extern "C" int vgposp_greedy_xcol(void* ws, int64_t n, int kmax, double** xcol) {
-  GreedyWS w;
-  if (int rc = greedy_ws(__func__, ws, n, kmax, &w)) return rc;
-  VG_CHECK_ARG(xcol != nullptr, 4);
-  *xcol = w.xcol;
-  return 0;
-}
-
-extern "C" int vgposp_greedy_select(int64_t n, int kmax, int round, int lazy, int64_t c0,
-                                    int64_t c1, int64_t* selected, double* sel_delta,
-                                    int64_t* evals, void* ws, size_t ws_bytes, void* stream) {
-  clear_error();
-  GreedyWS w;
-  double dummy = 0.0;
-  int rc = greedy_check(__func__, &dummy, n, n, kmax, round, ws, ws_bytes, &w);
-  if (rc) return rc;
-  VG_CHECK_ARG(c0 >= 0 && c0 <= c1 && c1 <= n, 5);
-  VG_CHECK_ARG(selected != nullptr, 7);
-  hipStream_t s = as_stream(stream);
-  const unsigned nch = (unsigned)ceil_div(n, CH);
-  hipLaunchKernelGGL(greedy_fresh_max_kernel, dim3(nch), dim3(CH), 0, s, n, w);
-  VG_LAUNCH_CHECK();
-  if (lazy) {
-    ProfScope psr("greedy_refresh", s, 0.0, 8.0 * 3.0 * n);
-    hipLaunchKernelGGL(greedy_refresh_kernel, dim3(nch), dim3(CH), 0, s, n, w);
-    VG_LAUNCH_CHECK();
-  }
-  ProfScope pss("greedy_select", s, 0.0, 0.0);
-  hipLaunchKernelGGL(greedy_select_kernel, dim3(1), dim3(CH), 0, s, n, round, lazy ? 1 : 0,
-                     selected, sel_delta, evals, w, c0, c1);
-  VG_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int vgposp_greedy_select_window(int64_t n, int kmax, int round, int64_t I0, int64_t I1,
-                                           int64_t I2, int cutoff, int64_t c0, int64_t c1,
-                                           int64_t* selected, double* sel_delta, int64_t* evals,
-                                           void* ws, size_t ws_bytes, void* stream) {
-  clear_error();
-  GreedyWS w;
-  double dummy = 0.0;
-  int rc = greedy_check(__func__, &dummy, n, n, kmax, round, ws, ws_bytes, &w);
-  if (rc) return rc;
-  VG_CHECK_ARG(I0 >= 1 && I1 >= 1 && I2 >= 1 && I0 * I1 * I2 == n, 4);
-  VG_CHECK_ARG(cutoff >= 0, 7);
-  VG_CHECK_ARG(c0 >= 0 && c0 <= c1 && c1 <= n, 8);
-  VG_CHECK_ARG(selected != nullptr, 10);
-  hipStream_t s = as_stream(stream);
-  const unsigned nch = (unsigned)ceil_div(n, CH);
-  {
-    ProfScope psw("greedy_window", s, 0.0, 0.0);
-    if (round == 0) {
-      hipLaunchKernelGGL(greedy_cache_all_kernel, dim3(nch), dim3(CH), 0, s, n, w);
-    } else {
-      const int64_t span = 2 * (int64_t)cutoff;
-      const int64_t total = span * span * span;
-      const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(total, 256), 4096));
-      hipLaunchKernelGGL(greedy_window_kernel, dim3(g), dim3(256), 0, s, selected, round, I0, I1,
-                         I2, cutoff, w);
-    }
-    VG_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(greedy_cache_max_kernel, dim3(nch), dim3(CH), 0, s, n, w);
-  VG_LAUNCH_CHECK();
-  ProfScope pss("greedy_select", s, 0.0, 0.0);
-  hipLaunchKernelGGL(greedy_select_kernel, dim3(1), dim3(CH), 0, s, n, round, 2, selected,
-                     sel_delta, evals, w, c0, c1);
-  VG_LAUNCH_CHECK();
-  return 0;
-}
-
-namespace vgposp {
-// The mat-vec part of a speculative round: plan, the T right-hand sides, one pass (or none), the
-// speculated columns into their slots.  A fixed launch sequence, hit or miss.
-template <int T>
-static void launch_spec_pass(const double* Sigma, int64_t n, int64_t lda, int kmax, int round,
-                             const int64_t* selected, const GreedyWS& w, hipStream_t s) {
-  hipLaunchKernelGGL(greedy_spec_plan_kernel, dim3(1), dim3(CH), 0, s, n, round, T,
-                     spec_slots(kmax), selected, w);
-  hipLaunchKernelGGL(greedy_extract_cols_kernel<T>, dim3((unsigned)ceil_div(n * T, 256)),
-                     dim3(256), 0, s, Sigma, n, lda, w.spec + H_COL, T, 0, w.spec + H_HIT, w.X);
-  {
-    ProfScope ps("greedy_trmv_spec", s, 0.0, 8.0 * (0.5 * (double)n * (n + 1) + (double)T * n));
-    hipLaunchKernelGGL(greedy_trmv_spec_kernel<T>, trmv_grid(n, 0, n), dim3(CT), 0, s, Sigma, n,
-                       lda, w.spec, w.X, w.part, w.spart, trmv_vec(Sigma, lda));
-  }
-  hipLaunchKernelGGL(greedy_spec_reduce_kernel, dim3((unsigned)ceil_div(n, CH), T - 1), dim3(CH),
-                     0, s, n, w);
-}
-}  // namespace vgposp
-
-extern "C" int vgposp_greedy_step(const double* Sigma, int64_t n, int64_t lda, int kmax, int round,
-                                  int lazy, int64_t* selected, double* sel_delta, int64_t* evals,
-                                  void* ws, size_t ws_bytes, void* stream) {
-  const int width = g_spec_width.load(std::memory_order_relaxed);
-  int rc;
-  if (width == 1 || round <= 0) {
-    rc = vgposp_greedy_update(Sigma, n, lda, kmax, round, 0, n, selected, ws, ws_bytes, stream);
-  } else {
-    clear_error();
-    GreedyWS w;
-    rc = greedy_check(__func__, Sigma, n, lda, kmax, round, ws, ws_bytes, &w);
-    if (rc) return rc;
-    VG_CHECK_ARG(selected != nullptr, 7);
-    hipStream_t s = as_stream(stream);
-    hipLaunchKernelGGL(greedy_extract_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s,
-                       Sigma, n, lda, selected, round, w.xcol, (int64_t)0, n);
-    VG_LAUNCH_CHECK();
-    if (width == 2)
-      launch_spec_pass<2>(Sigma, n, lda, kmax, round, selected, w, s);
-    else if (width == 4)
-      launch_spec_pass<4>(Sigma, n, lda, kmax, round, selected, w, s);
-    else
-      launch_spec_pass<8>(Sigma, n, lda, kmax, round, selected, w, s);
-    VG_LAUNCH_CHECK();
-    ProfScope psu("greedy_update", s, 0.0, 8.0 * (double)n * (6 + 2.0 * round));
-    hipLaunchKernelGGL(greedy_update_kernel, dim3((unsigned)ceil_div(n, CH)), dim3(CH), 0, s,
-                       Sigma, n, lda, selected, round, w, (int64_t)0, n, 1);
-    VG_LAUNCH_CHECK();
-  }
-  if (rc) return rc;
-  return vgposp_greedy_select(n, kmax, round, lazy, 0, n, selected, sel_delta, evals, ws, ws_bytes,
-                              stream);
-}
-
-extern "C" int vgposp_greedy_set_speculation(int width) {
-  clear_error();
-  VG_CHECK_ARG(width == 1 || width == 2 || width == 4 || width == 8, 1);
-  g_spec_width.store(width, std::memory_order_relaxed);
-  return 0;
-}
-
-extern "C" int vgposp_greedy_speculation(void) { return g_spec_width.load(); }
-
-extern "C" int vgposp_greedy_spec_stats(void* ws, int64_t n, int kmax, int64_t* passes,
-                                        int64_t* hits, int64_t* cached) {
-  GreedyWS w;
-  if (int rc = greedy_ws(__func__, ws, n, kmax, &w)) return rc;
-  long long h[3];
-  VG_HIP(hipMemcpy(h, w.spec, sizeof(h), hipMemcpyDeviceToHost));
-  if (cached) *cached = h[H_COUNT];
-  if (passes) *passes = h[H_PASSES];
-  if (hits) *hits = h[H_HITS];
-  return 0;
-}
-
-extern "C" int vgposp_greedy_spec_table(void* ws, int64_t n, int kmax, int64_t** column,
-                                        int64_t** fill_round, int64_t* slots) {
-  GreedyWS w;
-  if (int rc = greedy_ws(__func__, ws, n, kmax, &w)) return rc;
-  if (column) *column = (int64_t*)(w.spec + SPEC_HDR);
-  if (fill_round) *fill_round = (int64_t*)(w.spec + SPEC_HDR + spec_slots(kmax));
-  if (slots) *slots = spec_slots(kmax);
-  return 0;
-}
-
-extern "C" int vgposp_greedy_buffers(void* ws, int64_t n, int kmax, double** delta, double** piv,
-                                     int64_t* piv_len) {
-  GreedyWS w;
-  if (int rc = greedy_ws(__func__, ws, n, kmax, &w)) return rc;
-  if (delta) *delta = w.delta;
-  if (piv) *piv = w.piv;
-  if (piv_len) *piv_len = 2 + 2 * (int64_t)kmax;
-  return 0;
-}
-
-extern "C" int vgposp_greedy_cache(void* ws, int64_t n, int kmax, double** cache) {
-  GreedyWS w;
-  if (int rc = greedy_ws(__func__, ws, n, kmax, &w)) return rc;
-  VG_CHECK_ARG(cache != nullptr, 4);
-  *cache = w.cache;
-  return 0;
-}
-
-namespace vgposp {
+// The odd-order padding candidate (GreedyPlacement pad_odd) is never an arg-max.
 __global__ void greedy_exclude_kernel(unsigned char* selmask, int64_t idx) { selmask[idx] = 1; }
-}  // namespace vgposp
-
-extern "C" int vgposp_greedy_exclude(void* ws, int64_t n, int kmax, int64_t idx, void* stream) {
-  using namespace vgposp;
-  GreedyWS w;
-  if (int rc = greedy_ws(__func__, ws, n, kmax, &w)) return rc;
-  VG_CHECK_ARG(idx >= 0 && idx < n, 4);
-  hipLaunchKernelGGL(greedy_exclude_kernel, dim3(1), dim3(1), 0, as_stream(stream), w.selmask, idx);
-  VG_LAUNCH_CHECK();
-  return 0;
-}
 
 // ---- candidate set S != V and pre-installed sensors A0 (Krause's S / U split, which
 // placement_algorithm2.py:128-160 assumes away: "assume U is empty, assume V = S", A = []) ----
-namespace vgposp {
 
 // selmask[i] |= !allowed[i]: a masked location is never an arg-max, but greedy_update_kernel keeps
 // updating its nom / prec, so it stays in A_bar (denominator, :408-413) like every unselected one.
@@ -1220,6 +793,176 @@ __global__ __launch_bounds__(CT) void greedy_trmv_batch_kernel(
   }
 }
 
+// ---- host side: the argument checks.  A checker takes the entry's name `fn` and the position of
+// its group in THAT entry: a message is always "<entry>: bad argument <the entry's own position>".
+// The checker an entry starts with clears the last error. ----
+// (n, kmax) at `at`, `at` + 1
+static int check_sizes(const char* fn, int at, int64_t n, int kmax) {
+  clear_error();
+  VG_ARG(n >= 1 && n <= (int64_t)MAXCH * CH, at);
+  VG_ARG(kmax >= 1 && kmax <= n, at + 1);
+  return 0;
+}
+// (Sigma, n, lda, kmax): arguments 1 to 4 of every entry that has a matrix
+static int check_matrix(const char* fn, const double* Sigma, int64_t n, int64_t lda, int kmax) {
+  clear_error();
+  VG_ARG(Sigma != nullptr, 1);
+  VG_ARG(n >= 1 && n <= (int64_t)MAXCH * CH, 2);
+  VG_ARG(lda >= n, 3);
+  VG_ARG(kmax >= 1 && kmax <= n, 4);
+  return 0;
+}
+// (c0, c1, tmp, tmp_bytes): a slab of the partitioned inverse, 128-aligned or ending at n
+static int check_slab(const char* fn, int at, int64_t n, int64_t c0, int64_t c1, const double* tmp,
+                      size_t tmp_bytes) {
+  VG_ARG(c0 >= 0 && c0 <= c1 && c0 % 128 == 0, at);
+  VG_ARG(c1 <= n && (c1 % 128 == 0 || c1 == n), at + 1);
+  VG_ARG(c1 == c0 || (tmp != nullptr && tmp_bytes >= partial_inverse_tmp_bytes(n, c0, c1)),
+         at + 2);
+  return 0;
+}
+// (jitter, threshold, cache_init) at 5 to 7 everywhere; a null info by position or by name
+static int check_init(const char* fn, double jitter, double threshold, double cache_init,
+                      int at_info, const int* info, bool by_name) {
+  VG_ARG(jitter >= 0.0 && jitter < 1e300, 5);
+  VG_ARG(threshold >= 0.0, 6);
+  VG_ARG(cache_init == cache_init, 7);
+  if (!by_name) VG_ARG(info != nullptr, at_info);
+  if (info == nullptr) set_error("%s: info is null", fn);
+  return info == nullptr ? -at_info : 0;
+}
+// (ws, ws_bytes): a null ws is argument `at`, or with at = 0 "workspace is null" and VGPOSP_E_WS
+static int check_ws(const char* fn, int at, const void* ws, size_t ws_bytes, size_t need) {
+  if (at) VG_ARG(ws != nullptr, at);
+  if (ws == nullptr) set_error("%s: workspace is null", fn);
+  else if (ws_bytes < need) set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, need);
+  return ws != nullptr && ws_bytes >= need ? 0 : VGPOSP_E_WS;
+}
+// (ws, n, kmax) of the entries that only look into a workspace
+static int check_view(const char* fn, const void* ws, int64_t n, int kmax) {
+  clear_error();
+  VG_ARG(ws != nullptr, 1);
+  VG_ARG(n >= 1, 2);
+  VG_ARG(kmax >= 1, 3);
+  return 0;
+}
+
+// Grid of a mat-vec kernel over columns [c0, c1) (the tile origin is even: column pairs), and
+// whether it may load a column pair with one 16-byte access.
+static dim3 trmv_grid(int64_t n, int64_t c0, int64_t c1) {
+  return dim3((unsigned)ceil_div(c1 - (c0 & ~(int64_t)1), TRMV_COLS), (unsigned)ceil_div(n, RC));
+}
+static int trmv_vec(const double* M, int64_t lda) {
+  return (reinterpret_cast<uintptr_t>(M) % 16 == 0) && (lda % 2 == 0);
+}
+
+// `info` cleared and the init kernel (vgposp_greedy_prepare)
+static int run_prepare(const char* fn, double* Sigma, int64_t n, int64_t lda, double jitter,
+                       double threshold, double cache_init, int* info, const GreedyWS& w,
+                       hipStream_t s) {
+  VG_HIP_AS(fn, vg_memset(info, 0, sizeof(int), s));
+  hipLaunchKernelGGL(greedy_init_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, Sigma,
+                     n, lda, jitter, threshold, cache_init, w);
+  VG_HIP_AS(fn, hipGetLastError());
+  return 0;
+}
+
+// Q_ii = |M e_i|^2 for columns [c0, c1) -> part (reduced in the round-0 update)
+static void launch_colsq(const double* M, int64_t n, int64_t lda, int64_t c0, int64_t c1,
+                         const GreedyWS& w, hipStream_t s) {
+  const bool whole = c0 == 0 && c1 == n;  // a slab reports no algorithmic figures
+  const double tri = 0.5 * (double)n * (n + 1);
+  ProfScope ps("greedy_colsq", s, whole ? 2.0 * tri : 0.0,
+               whole ? 8.0 * (tri + (double)ceil_div(n, RC) * n) : 0.0);
+  hipLaunchKernelGGL(greedy_trmv_kernel<true>, trmv_grid(n, c0, c1), dim3(CT), 0, s, M, n, lda,
+                     nullptr, 0, nullptr, w.part, c0, c1, trmv_vec(M, lda));
+}
+
+// L^-1 in columns [c0, c1) of a factored Sigma and their column norms (vgposp_greedy_finish_slab)
+static int run_finish_slab(const char* fn, double* Sigma, int64_t n, int64_t lda, int kmax,
+                           int64_t c0, int64_t c1, double* tmp, void* ws, const GreedyWS& w,
+                           hipStream_t s) {
+  if (c1 == c0) return 0;
+  // M changes here: no cached column survives (header, table and the "is cached" bytes)
+  VG_HIP_AS(fn, vg_memset(w.spec, 0, (size_t)(SPEC_HDR + 2 * spec_slots(kmax)) * 8 + n, s));
+  VG_TRY(partial_inverse(Sigma, n, lda, c0, c1, tmp, greedy_fact_ws(ws, w, n), s));
+  launch_colsq(Sigma, n, lda, c0, c1, w, s);
+  VG_HIP_AS(fn, hipGetLastError());
+  return 0;
+}
+
+// xcol = the last pick's column of L^-1 where [own0, own1) holds it, zeros elsewhere
+static void launch_extract(const double* Sigma, int64_t n, int64_t lda, const int64_t* selected,
+                           int round, const GreedyWS& w, int64_t own0, int64_t own1,
+                           hipStream_t s) {
+  hipLaunchKernelGGL(greedy_extract_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s,
+                     Sigma, n, lda, selected, round, w.xcol, own0, own1);
+}
+
+// q = M^T xcol in columns [c0, c1) -> part
+static void launch_trmv(const double* Sigma, int64_t n, int64_t lda, const int64_t* selected,
+                        int round, const GreedyWS& w, int64_t c0, int64_t c1, hipStream_t s) {
+  // algorithmic: the lower triangle of L^-1 in rows >= a, columns [c0, c1) (a is device-side;
+  // bench.py recomputes the exact bytes from the selections)
+  ProfScope ps("greedy_trmv", s, 0.0, 8.0 * (0.5 * (double)n * (n + 1) + 2.0 * n));
+  hipLaunchKernelGGL(greedy_trmv_kernel<false>, trmv_grid(n, c0, c1), dim3(CT), 0, s, Sigma, n,
+                     lda, selected, round, w.xcol, w.part, c0, c1, trmv_vec(Sigma, lda));
+}
+
+// Rank-1 rows, nom, P_yy and fresh deltas of columns [c0, c1) from the partials `part` (spec: the
+// plan says where the pick's column is); the CH-aligned blocks spanning [c0, c1), from c0 / CH on
+static void launch_update(const double* Sigma, int64_t n, int64_t lda, const int64_t* selected,
+                          int round, GreedyWS w, int64_t c0, int64_t c1, double* part, int spec,
+                          hipStream_t s) {
+  w.part = part;
+  ProfScope ps("greedy_update", s, 0.0, 8.0 * (double)(c1 - c0) * (6 + 2.0 * round));
+  hipLaunchKernelGGL(greedy_update_kernel, dim3((unsigned)(ceil_div(c1, CH) - c0 / CH)), dim3(CH),
+                     0, s, Sigma, n, lda, selected, round, w, c0, c1, spec);
+}
+
+// The arg-max of a round.  mode 0: full greedy, 1: lazy (the stale entries above the best fresh
+// key are refreshed first), 2: over the cache (algorithm 3).
+static void launch_select(int64_t n, int round, int mode, int64_t* selected, double* sel_delta,
+                          int64_t* evals, const GreedyWS& w, int64_t c0, int64_t c1,
+                          hipStream_t s) {
+  const unsigned nch = (unsigned)ceil_div(n, CH);
+  hipLaunchKernelGGL(mode == 2 ? greedy_cache_max_kernel : greedy_fresh_max_kernel, dim3(nch),
+                     dim3(CH), 0, s, n, w);
+  if (mode == 1) {
+    ProfScope psr("greedy_refresh", s, 0.0, 8.0 * 3.0 * n);
+    hipLaunchKernelGGL(greedy_refresh_kernel, dim3(nch), dim3(CH), 0, s, n, w);
+  }
+  ProfScope pss("greedy_select", s, 0.0, 0.0);
+  hipLaunchKernelGGL(greedy_select_kernel, dim3(1), dim3(CH), 0, s, n, round, mode, selected,
+                     sel_delta, evals, w, c0, c1);
+}
+
+// f(T), T = width (2, 4 or 8) at compile time; LO: the smallest built (a dead 2 then names LO)
+template <int LO, class F>
+static void with_width(int width, F&& f) {
+  if (LO <= 2 && width == 2) return f(std::integral_constant<int, std::max(LO, 2)>{});
+  if (width == 4) return f(std::integral_constant<int, 4>{});
+  f(std::integral_constant<int, 8>{});
+}
+
+// The mat-vec part of a speculative round: plan, the T right-hand sides, one pass (or none), the
+// speculated columns into their slots.  A fixed launch sequence, hit or miss.
+template <int T>
+static void launch_spec_pass(const double* Sigma, int64_t n, int64_t lda, int kmax, int round,
+                             const int64_t* selected, const GreedyWS& w, hipStream_t s) {
+  hipLaunchKernelGGL(greedy_spec_plan_kernel, dim3(1), dim3(CH), 0, s, n, round, T,
+                     spec_slots(kmax), selected, w);
+  hipLaunchKernelGGL(greedy_extract_cols_kernel<T>, dim3((unsigned)ceil_div(n * T, 256)),
+                     dim3(256), 0, s, Sigma, n, lda, w.spec + H_COL, T, 0, w.spec + H_HIT, w.X);
+  {
+    ProfScope ps("greedy_trmv_spec", s, 0.0, 8.0 * (0.5 * (double)n * (n + 1) + (double)T * n));
+    hipLaunchKernelGGL(greedy_trmv_spec_kernel<T>, trmv_grid(n, 0, n), dim3(CT), 0, s, Sigma, n,
+                       lda, w.spec, w.X, w.part, w.spart, trmv_vec(Sigma, lda));
+  }
+  hipLaunchKernelGGL(greedy_spec_reduce_kernel, dim3((unsigned)ceil_div(n, CH), T - 1), dim3(CH),
+                     0, s, n, w);
+}
+
 struct CondScratch {
   double *X, *part;
   size_t bytes;
@@ -1234,9 +977,8 @@ static CondScratch cond_layout(void* base, int64_t n, int batch) {
   c.bytes = xb + align_up((size_t)batch * ceil_div(n, RC) * n * 8);
   return c;
 }
-
 static bool cond_batch_ok(int batch) { return batch == 1 || batch == 4 || batch == 8; }
-
+// The columns q of placed[j0 .. j0 + nt) in one pass over L^-1 -> c.part, a slice per column
 template <int T>
 static void launch_cond_batch(const double* Sigma, int64_t n, int64_t lda, const int64_t* forced,
                               int64_t j0, int nt, const CondScratch& c, hipStream_t s) {
@@ -1253,19 +995,289 @@ static void launch_cond_batch(const double* Sigma, int64_t n, int64_t lda, const
                        Sigma, n, lda, forced, j0, nt, c.X, c.part);
 }
 
+// vgposp_greedy_init (info, ws at 5, 6; the variant parameters are constants) and _init_ex (8, 9)
+static int init_entry(const char* fn, int at_info, double* Sigma, int64_t n, int64_t lda, int kmax,
+                      double jitter, double threshold, double cache_init, int* info, void* ws,
+                      size_t ws_bytes, void* stream) {
+  VG_TRY(check_matrix(fn, Sigma, n, lda, kmax));
+  VG_TRY(check_init(fn, jitter, threshold, cache_init, at_info, info, false));
+  const GreedyWS w = greedy_layout(ws, n, kmax);
+  VG_TRY(check_ws(fn, at_info + 1, ws, ws_bytes, w.bytes));
+  hipStream_t s = as_stream(stream);
+  VG_TRY(run_prepare(fn, Sigma, n, lda, jitter, threshold, cache_init, info, w, s));
+  // early: after a failed pivot (a singular cov_vv) every later launch of the factorization and
+  // inverse reads `info` on the device and exits, so the host's jitter retry does not pay for a
+  // whole O(n^3) factorization + inverse first — and nothing here synchronises the host
+  VG_TRY(potrf_one(Sigma, n, lda, /*invert=*/1, nullptr, info, greedy_fact_ws(ws, w, n), s,
+                   /*early=*/true));
+  launch_colsq(Sigma, n, lda, 0, n, w, s);
+  VG_HIP_AS(fn, hipGetLastError());
+  return 0;
+}
+
+// vgposp_greedy_update (extract = 1) and _update_ex: the same positions up to `selected`
+static int update_entry(const char* fn, const double* Sigma, int64_t n, int64_t lda, int kmax,
+                        int round, int64_t c0, int64_t c1, const int64_t* selected, int extract,
+                        void* ws, size_t ws_bytes, void* stream) {
+  VG_TRY(check_matrix(fn, Sigma, n, lda, kmax));
+  VG_ARG(round >= 0 && round < kmax, 5);
+  VG_ARG(c0 >= 0 && c0 <= c1 && c1 <= n, 6);
+  VG_ARG(selected != nullptr || round == 0, 8);
+  const GreedyWS w = greedy_layout(ws, n, kmax);
+  VG_TRY(check_ws(fn, 0, ws, ws_bytes, w.bytes));
+  hipStream_t s = as_stream(stream);
+  if (c1 == c0) return 0;
+  if (round > 0) {
+    if (extract) launch_extract(Sigma, n, lda, selected, round, w, 0, n, s);
+    launch_trmv(Sigma, n, lda, selected, round, w, c0, c1, s);
+  }
+  launch_update(Sigma, n, lda, selected, round, w, c0, c1, w.part, 0, s);
+  VG_HIP_AS(fn, hipGetLastError());
+  return 0;
+}
+
 }  // namespace vgposp
+
+using namespace vgposp;
+
+extern "C" size_t vgposp_greedy_workspace_bytes(int64_t n, int kmax) {
+  if (n <= 0 || kmax <= 0) return 0;
+  return greedy_layout(nullptr, n, kmax).bytes;
+}
+
+extern "C" int vgposp_greedy_init_ex(double* Sigma, int64_t n, int64_t lda, int kmax,
+                                     double jitter, double threshold, double cache_init, int* info,
+                                     void* ws, size_t ws_bytes, void* stream) {
+  return init_entry(__func__, 8, Sigma, n, lda, kmax, jitter, threshold, cache_init, info, ws,
+                    ws_bytes, stream);
+}
+
+extern "C" int vgposp_greedy_init(double* Sigma, int64_t n, int64_t lda, int kmax, int* info,
+                                  void* ws, size_t ws_bytes, void* stream) {
+  return init_entry(__func__, 5, Sigma, n, lda, kmax, 0.0, DELTA_EPS, __builtin_huge_val(), info,
+                    ws, ws_bytes, stream);
+}
+
+extern "C" int vgposp_greedy_update_ex(const double* Sigma, int64_t n, int64_t lda, int kmax,
+                                       int round, int64_t c0, int64_t c1, const int64_t* selected,
+                                       int extract, void* ws, size_t ws_bytes, void* stream) {
+  return update_entry(__func__, Sigma, n, lda, kmax, round, c0, c1, selected, extract, ws,
+                      ws_bytes, stream);
+}
+
+extern "C" int vgposp_greedy_update(const double* Sigma, int64_t n, int64_t lda, int kmax,
+                                    int round, int64_t c0, int64_t c1, const int64_t* selected,
+                                    void* ws, size_t ws_bytes, void* stream) {
+  return update_entry(__func__, Sigma, n, lda, kmax, round, c0, c1, selected, 1, ws, ws_bytes,
+                      stream);
+}
+
+extern "C" int vgposp_greedy_extract(const double* Sigma, int64_t n, int64_t lda, int kmax,
+                                     int round, int64_t own0, int64_t own1,
+                                     const int64_t* selected, void* ws, size_t ws_bytes,
+                                     void* stream) {
+  VG_TRY(check_matrix(__func__, Sigma, n, lda, kmax));
+  VG_CHECK_ARG(round >= 1 && round < kmax, 5);
+  VG_CHECK_ARG(own0 >= 0 && own0 <= own1 && own1 <= n, 6);
+  VG_CHECK_ARG(selected != nullptr, 8);
+  const GreedyWS w = greedy_layout(ws, n, kmax);
+  VG_TRY(check_ws(__func__, 0, ws, ws_bytes, w.bytes));
+  launch_extract(Sigma, n, lda, selected, round, w, own0, own1, as_stream(stream));
+  VG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" size_t vgposp_greedy_slab_tmp_bytes(int64_t n, int64_t c0, int64_t c1) {
+  if (n <= 0 || c0 < 0 || c1 <= c0 || c1 > n) return 0;
+  return partial_inverse_tmp_bytes(n, c0, c1);
+}
+
+extern "C" int vgposp_greedy_prepare(double* Sigma, int64_t n, int64_t lda, int kmax,
+                                     double jitter, double threshold, double cache_init, int* info,
+                                     void* ws, size_t ws_bytes, void* stream) {
+  VG_TRY(check_matrix(__func__, Sigma, n, lda, kmax));
+  VG_TRY(check_init(__func__, jitter, threshold, cache_init, 8, info, true));
+  const GreedyWS w = greedy_layout(ws, n, kmax);
+  VG_TRY(check_ws(__func__, 0, ws, ws_bytes, w.bytes));
+  return run_prepare(__func__, Sigma, n, lda, jitter, threshold, cache_init, info, w,
+                     as_stream(stream));
+}
+
+extern "C" int vgposp_greedy_fact_ws(void* ws, int64_t n, int kmax, void** fws,
+                                     size_t* fws_bytes) {
+  VG_TRY(check_view(__func__, ws, n, kmax));
+  VG_CHECK_ARG(fws != nullptr && fws_bytes != nullptr, 4);
+  *fws = greedy_fact_ws(ws, greedy_layout(ws, n, kmax), n);
+  *fws_bytes = potrf_ws_bytes(n);
+  return 0;
+}
+
+extern "C" int vgposp_greedy_finish_slab(double* Sigma, int64_t n, int64_t lda, int kmax,
+                                         int64_t c0, int64_t c1, double* tmp, size_t tmp_bytes,
+                                         void* ws, size_t ws_bytes, void* stream) {
+  VG_TRY(check_matrix(__func__, Sigma, n, lda, kmax));
+  VG_TRY(check_slab(__func__, 5, n, c0, c1, tmp, tmp_bytes));
+  const GreedyWS w = greedy_layout(ws, n, kmax);
+  VG_TRY(check_ws(__func__, 9, ws, ws_bytes, w.bytes));
+  return run_finish_slab(__func__, Sigma, n, lda, kmax, c0, c1, tmp, ws, w, as_stream(stream));
+}
+
+extern "C" int vgposp_greedy_init_slab(double* Sigma, int64_t n, int64_t lda, int kmax,
+                                       double jitter, double threshold, double cache_init,
+                                       int64_t c0, int64_t c1, double* tmp, size_t tmp_bytes,
+                                       int* info, void* ws, size_t ws_bytes, void* stream) {
+  VG_TRY(check_matrix(__func__, Sigma, n, lda, kmax));
+  VG_TRY(check_init(__func__, jitter, threshold, cache_init, 12, info, true));
+  VG_TRY(check_slab(__func__, 8, n, c0, c1, tmp, tmp_bytes));
+  const GreedyWS w = greedy_layout(ws, n, kmax);
+  VG_TRY(check_ws(__func__, 0, ws, ws_bytes, w.bytes));
+  hipStream_t s = as_stream(stream);
+  VG_TRY(run_prepare(__func__, Sigma, n, lda, jitter, threshold, cache_init, info, w, s));
+  // (the slab path stays classical, like the sharded factorization it stands in for)
+  VG_TRY(potrf_one(Sigma, n, lda, /*invert=*/0, nullptr, info, greedy_fact_ws(ws, w, n), s,
+                   /*early=*/false, /*strassen=*/false));
+  return run_finish_slab(__func__, Sigma, n, lda, kmax, c0, c1, tmp, ws, w, s);
+}
+
+extern "C" int vgposp_greedy_xcol(void* ws, int64_t n, int kmax, double** xcol) {
+  VG_TRY(check_view(__func__, ws, n, kmax));
+  VG_CHECK_ARG(xcol != nullptr, 4);
+  *xcol = greedy_layout(ws, n, kmax).xcol;
+  return 0;
+}
+
+extern "C" int vgposp_greedy_select(int64_t n, int kmax, int round, int lazy, int64_t c0,
+                                    int64_t c1, int64_t* selected, double* sel_delta,
+                                    int64_t* evals, void* ws, size_t ws_bytes, void* stream) {
+  VG_TRY(check_sizes(__func__, 1, n, kmax));
+  VG_CHECK_ARG(round >= 0 && round < kmax, 3);
+  VG_CHECK_ARG(c0 >= 0 && c0 <= c1 && c1 <= n, 5);
+  VG_CHECK_ARG(selected != nullptr, 7);
+  const GreedyWS w = greedy_layout(ws, n, kmax);
+  VG_TRY(check_ws(__func__, 0, ws, ws_bytes, w.bytes));
+  launch_select(n, round, lazy ? 1 : 0, selected, sel_delta, evals, w, c0, c1, as_stream(stream));
+  VG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int vgposp_greedy_select_window(int64_t n, int kmax, int round, int64_t I0, int64_t I1,
+                                           int64_t I2, int cutoff, int64_t c0, int64_t c1,
+                                           int64_t* selected, double* sel_delta, int64_t* evals,
+                                           void* ws, size_t ws_bytes, void* stream) {
+  VG_TRY(check_sizes(__func__, 1, n, kmax));
+  VG_CHECK_ARG(round >= 0 && round < kmax, 3);
+  VG_CHECK_ARG(I0 >= 1 && I1 >= 1 && I2 >= 1 && I0 * I1 * I2 == n, 4);
+  VG_CHECK_ARG(cutoff >= 0, 7);
+  VG_CHECK_ARG(c0 >= 0 && c0 <= c1 && c1 <= n, 8);
+  VG_CHECK_ARG(selected != nullptr, 10);
+  const GreedyWS w = greedy_layout(ws, n, kmax);
+  VG_TRY(check_ws(__func__, 0, ws, ws_bytes, w.bytes));
+  hipStream_t s = as_stream(stream);
+  {
+    ProfScope psw("greedy_window", s, 0.0, 0.0);
+    if (round == 0) {
+      hipLaunchKernelGGL(greedy_cache_all_kernel, dim3((unsigned)ceil_div(n, CH)), dim3(CH), 0, s,
+                         n, w);
+    } else {
+      const int64_t span = 2 * (int64_t)cutoff;
+      const int64_t total = span * span * span;
+      const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(total, 256), 4096));
+      hipLaunchKernelGGL(greedy_window_kernel, dim3(g), dim3(256), 0, s, selected, round, I0, I1,
+                         I2, cutoff, w);
+    }
+  }
+  launch_select(n, round, 2, selected, sel_delta, evals, w, c0, c1, s);
+  VG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int vgposp_greedy_step(const double* Sigma, int64_t n, int64_t lda, int kmax, int round,
+                                  int lazy, int64_t* selected, double* sel_delta, int64_t* evals,
+                                  void* ws, size_t ws_bytes, void* stream) {
+  VG_TRY(check_matrix(__func__, Sigma, n, lda, kmax));
+  VG_CHECK_ARG(round >= 0 && round < kmax, 5);
+  VG_CHECK_ARG(selected != nullptr, 7);
+  const GreedyWS w = greedy_layout(ws, n, kmax);
+  VG_TRY(check_ws(__func__, 0, ws, ws_bytes, w.bytes));
+  hipStream_t s = as_stream(stream);
+  const int width = g_spec_width.load(std::memory_order_relaxed);
+  const bool spec = width > 1 && round > 0;
+  if (round > 0) launch_extract(Sigma, n, lda, selected, round, w, 0, n, s);
+  if (spec)
+    with_width<2>(width, [&](auto t) {
+      launch_spec_pass<decltype(t)::value>(Sigma, n, lda, kmax, round, selected, w, s);
+    });
+  else if (round > 0)
+    launch_trmv(Sigma, n, lda, selected, round, w, 0, n, s);
+  launch_update(Sigma, n, lda, selected, round, w, 0, n, w.part, spec, s);
+  launch_select(n, round, lazy ? 1 : 0, selected, sel_delta, evals, w, 0, n, s);
+  VG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int vgposp_greedy_set_speculation(int width) {
+  clear_error();
+  VG_CHECK_ARG(width == 1 || width == 2 || width == 4 || width == 8, 1);
+  g_spec_width.store(width, std::memory_order_relaxed);
+  return 0;
+}
+
+extern "C" int vgposp_greedy_speculation(void) { return g_spec_width.load(); }
+
+extern "C" int vgposp_greedy_spec_stats(void* ws, int64_t n, int kmax, int64_t* passes,
+                                        int64_t* hits, int64_t* cached) {
+  VG_TRY(check_view(__func__, ws, n, kmax));
+  long long h[3];
+  VG_HIP(hipMemcpy(h, greedy_layout(ws, n, kmax).spec, sizeof(h), hipMemcpyDeviceToHost));
+  if (cached) *cached = h[H_COUNT];
+  if (passes) *passes = h[H_PASSES];
+  if (hits) *hits = h[H_HITS];
+  return 0;
+}
+
+extern "C" int vgposp_greedy_spec_table(void* ws, int64_t n, int kmax, int64_t** column,
+                                        int64_t** fill_round, int64_t* slots) {
+  VG_TRY(check_view(__func__, ws, n, kmax));
+  const GreedyWS w = greedy_layout(ws, n, kmax);
+  if (column) *column = (int64_t*)(w.spec + SPEC_HDR);
+  if (fill_round) *fill_round = (int64_t*)(w.spec + SPEC_HDR + spec_slots(kmax));
+  if (slots) *slots = spec_slots(kmax);
+  return 0;
+}
+
+extern "C" int vgposp_greedy_buffers(void* ws, int64_t n, int kmax, double** delta, double** piv,
+                                     int64_t* piv_len) {
+  VG_TRY(check_view(__func__, ws, n, kmax));
+  const GreedyWS w = greedy_layout(ws, n, kmax);
+  if (delta) *delta = w.delta;
+  if (piv) *piv = w.piv;
+  if (piv_len) *piv_len = 2 + 2 * (int64_t)kmax;
+  return 0;
+}
+
+extern "C" int vgposp_greedy_cache(void* ws, int64_t n, int kmax, double** cache) {
+  VG_TRY(check_view(__func__, ws, n, kmax));
+  VG_CHECK_ARG(cache != nullptr, 4);
+  *cache = greedy_layout(ws, n, kmax).cache;
+  return 0;
+}
+
+extern "C" int vgposp_greedy_exclude(void* ws, int64_t n, int kmax, int64_t idx, void* stream) {
+  VG_TRY(check_view(__func__, ws, n, kmax));
+  VG_CHECK_ARG(idx >= 0 && idx < n, 4);
+  hipLaunchKernelGGL(greedy_exclude_kernel, dim3(1), dim3(1), 0, as_stream(stream),
+                     greedy_layout(ws, n, kmax).selmask, idx);
+  VG_LAUNCH_CHECK();
+  return 0;
+}
 
 extern "C" int vgposp_greedy_mask(void* ws, int64_t n, int kmax, const unsigned char* allowed,
                                   void* stream) {
-  using namespace vgposp;
-  clear_error();
   VG_CHECK_ARG(ws != nullptr, 1);
-  VG_CHECK_ARG(n >= 1 && n <= (int64_t)MAXCH * CH, 2);
-  VG_CHECK_ARG(kmax >= 1 && kmax <= n, 3);
+  VG_TRY(check_sizes(__func__, 2, n, kmax));
   VG_CHECK_ARG(allowed != nullptr, 4);
-  GreedyWS w = greedy_layout(ws, n, kmax);
   hipLaunchKernelGGL(greedy_mask_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0,
-                     as_stream(stream), n, allowed, w.selmask);
+                     as_stream(stream), n, allowed, greedy_layout(ws, n, kmax).selmask);
   VG_LAUNCH_CHECK();
   return 0;
 }
@@ -1273,15 +1285,13 @@ extern "C" int vgposp_greedy_mask(void* ws, int64_t n, int kmax, const unsigned 
 extern "C" int vgposp_greedy_force(int64_t n, int kmax, int round, const int64_t* forced,
                                    int64_t j, int64_t* selected, void* ws, size_t ws_bytes,
                                    void* stream) {
-  using namespace vgposp;
-  clear_error();
-  GreedyWS w;
-  double dummy = 0.0;
-  int rc = greedy_check(__func__, &dummy, n, n, kmax, round, ws, ws_bytes, &w);
-  if (rc) return rc;
+  VG_TRY(check_sizes(__func__, 1, n, kmax));
+  VG_CHECK_ARG(round >= 0 && round < kmax, 3);
   VG_CHECK_ARG(forced != nullptr, 4);
   VG_CHECK_ARG(j >= 0, 5);
   VG_CHECK_ARG(selected != nullptr, 6);
+  const GreedyWS w = greedy_layout(ws, n, kmax);
+  VG_TRY(check_ws(__func__, 0, ws, ws_bytes, w.bytes));
   hipLaunchKernelGGL(greedy_force_kernel, dim3(1), dim3(256), 0, as_stream(stream), n, round,
                      forced, j, selected, w);
   VG_LAUNCH_CHECK();
@@ -1289,7 +1299,6 @@ extern "C" int vgposp_greedy_force(int64_t n, int kmax, int round, const int64_t
 }
 
 extern "C" size_t vgposp_greedy_condition_workspace_bytes(int64_t n, int batch) {
-  using namespace vgposp;
   if (n <= 0 || !cond_batch_ok(batch)) return 0;
   return batch == 1 ? 256 : cond_layout(nullptr, n, batch).bytes;
 }
@@ -1298,60 +1307,46 @@ extern "C" int vgposp_greedy_condition(const double* Sigma, int64_t n, int64_t l
                                        int m, int k, int batch, const int64_t* placed,
                                        int64_t* selected, void* ws, size_t ws_bytes,
                                        void* scratch, size_t scratch_bytes, void* stream) {
-  using namespace vgposp;
-  clear_error();
-  GreedyWS w;
-  int rc = greedy_check(__func__, Sigma, n, lda, kmax, 0, ws, ws_bytes, &w);
-  if (rc) return rc;
+  VG_TRY(check_matrix(__func__, Sigma, n, lda, kmax));
   VG_CHECK_ARG(m >= 1 && m <= kmax, 5);
   VG_CHECK_ARG(k >= 0 && (int64_t)m + k <= kmax, 6);
   VG_CHECK_ARG(batch >= 1 && cond_batch_ok(batch), 7);
   VG_CHECK_ARG(placed != nullptr, 8);
   VG_CHECK_ARG(selected != nullptr, 9);
+  const GreedyWS w = greedy_layout(ws, n, kmax);
+  VG_TRY(check_ws(__func__, 0, ws, ws_bytes, w.bytes));
   VG_CHECK_ARG(scratch != nullptr, 12);
-  const size_t need = vgposp_greedy_condition_workspace_bytes(n, batch);
+  const size_t need = batch == 1 ? 256 : cond_layout(nullptr, n, batch).bytes;
   if (scratch_bytes < need) {
     set_error("%s: scratch %zu < %zu bytes", __func__, scratch_bytes, need);
     return VGPOSP_E_WS;
   }
   hipStream_t s = as_stream(stream);
-  auto force = [&](int round) {
-    return vgposp_greedy_force(n, kmax, round, placed, round, selected, ws, ws_bytes, stream);
-  };
-  // round 0: nom = diag(Sigma), prec = Q_ii from init's column norms; A <- [a_0]
-  if ((rc = vgposp_greedy_update(Sigma, n, lda, kmax, 0, 0, n, selected, ws, ws_bytes, stream)))
-    return rc;
-  if ((rc = force(0))) return rc;
-  // rounds 1 .. m-1 condition on a_0 .. a_{m-2}; a_{m-1}'s column is left to the next
+  // round r conditions on a_{r-1} = placed[r - 1], then A <- A + [a_r]; round 0: nom =
+  // diag(Sigma), prec = Q_ii from init's column norms.  a_{m-1}'s column is left to the next
   // vgposp_greedy_step (round m), whose own mat-vec reads selected[m - 1]
+  auto place = [&](int r, double* part) {
+    launch_update(Sigma, n, lda, selected, r, w, 0, n, part, 0, s);
+    hipLaunchKernelGGL(greedy_force_kernel, dim3(1), dim3(256), 0, s, n, r, placed, r, selected, w);
+  };
+  place(0, w.part);
   if (batch == 1) {
     for (int r = 1; r < m; ++r) {
-      if ((rc = vgposp_greedy_update(Sigma, n, lda, kmax, r, 0, n, selected, ws, ws_bytes,
-                                     stream)))
-        return rc;
-      if ((rc = force(r))) return rc;
+      launch_extract(Sigma, n, lda, selected, r, w, 0, n, s);
+      launch_trmv(Sigma, n, lda, selected, r, w, 0, n, s);
+      place(r, w.part);
     }
-    return 0;
-  }
-  const CondScratch c = cond_layout(scratch, n, batch);
-  const int64_t slice = ceil_div(n, RC) * n;
-  for (int j0 = 0; j0 < m - 1; j0 += batch) {
-    const int nt = std::min(batch, m - 1 - j0);
-    if (batch == 4)
-      launch_cond_batch<4>(Sigma, n, lda, placed, j0, nt, c, s);
-    else
-      launch_cond_batch<8>(Sigma, n, lda, placed, j0, nt, c, s);
-    VG_LAUNCH_CHECK();
-    for (int j = 0; j < nt; ++j) {
-      const int r = j0 + j + 1;  // the update that conditions on a_{r-1} = placed[j0 + j]
-      GreedyWS wj = w;
-      wj.part = c.part + (int64_t)j * slice;
-      ProfScope psu("greedy_update", s, 0.0, 8.0 * (double)n * (6 + 2.0 * r));
-      hipLaunchKernelGGL(greedy_update_kernel, dim3((unsigned)ceil_div(n, CH)), dim3(CH), 0, s,
-                         Sigma, n, lda, selected, r, wj, (int64_t)0, n, 0);
-      VG_LAUNCH_CHECK();
-      if ((rc = force(r))) return rc;
+  } else {
+    const CondScratch c = cond_layout(scratch, n, batch);
+    const int64_t slice = ceil_div(n, RC) * n;
+    for (int j0 = 0; j0 < m - 1; j0 += batch) {
+      const int nt = std::min(batch, m - 1 - j0);
+      with_width<4>(batch, [&](auto t) {
+        launch_cond_batch<decltype(t)::value>(Sigma, n, lda, placed, j0, nt, c, s);
+      });
+      for (int j = 0; j < nt; ++j) place(j0 + j + 1, c.part + (int64_t)j * slice);
     }
   }
+  VG_LAUNCH_CHECK();
   return 0;
 }

@@ -31,9 +31,11 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from ._lib import call
+from ._lib import CholeskyError, call, query
 from .constraints import reject_constraints
+from .dist_cholesky import DIST_MIN, DistCholesky, greedy_cholesky_ops
 from .linalg import _p, _stream
+from .placement_algorithm2 import PIVOT_RTOL, SINGULAR_EPS, GreedyPlacement
 
 
 def slab_bounds(n, world, balance=True):
@@ -70,7 +72,6 @@ class HipGreedyBackend:
     """The per-rank device state: a GreedyPlacement plus tensor views of its delta / pivot."""
 
     def __init__(self, Sigma, kmax, copy=False, jitter=0.0, candidates=None, placed=None):
-        from .placement_algorithm2 import GreedyPlacement
         reject_constraints("the sharded placement", candidates, placed)
         self._src = Sigma if copy else None
         self.g = GreedyPlacement(Sigma, kmax, copy=copy, jitter=jitter)
@@ -79,17 +80,19 @@ class HipGreedyBackend:
         self.sdiag = None
         self.n = self.g.n
         self.kmax = self.g.kmax
-        d, p, plen = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
+        d, p, x = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
         call("vgposp_greedy_buffers", _p(self.g.ws), self.n, self.kmax, ctypes.byref(d),
-             ctypes.byref(p), ctypes.byref(plen))
-        base = self.g.ws.data_ptr()
-        self._delta = self.g.ws[d.value - base:d.value - base + 8 * self.n].view(torch.float64)
-        self._piv = self.g.ws[p.value - base:p.value - base + 8 * plen.value].view(torch.float64)
-
-        x = ctypes.c_void_p()
+             ctypes.byref(p), None)
         call("vgposp_greedy_xcol", _p(self.g.ws), self.n, self.kmax, ctypes.byref(x))
-        self._xcol = self.g.ws[x.value - base:x.value - base + 8 * self.n].view(torch.float64)
+        self._delta, self._xcol = self._view(d, self.n), self._view(x, self.n)
+        self._piv = self._view(p, 2 + 2 * self.kmax)
         self._tmp = None
+
+    def _view(self, ptr, count):
+        """float64 [count] view of the workspace at a device pointer the library returned."""
+        off = ptr.value - self.g.ws.data_ptr()
+        assert 0 <= off and off + 8 * count <= self.g.ws.numel(), (off, count)
+        return self.g.ws[off:off + 8 * count].view(torch.float64)
 
     def snapshot_diag(self):
         """diag(Sigma) as the factorization will see it (a device copy, no host sync)."""
@@ -108,7 +111,6 @@ class HipGreedyBackend:
         """No failed pivot, and (check_pivots) no pivot ratio L_ii^2 / sigma_ii at rounding level.
         The factored buffer holds L^-1 in the columns this rank inverted (all of them unless
         partitioned) and L elsewhere."""
-        from .placement_algorithm2 import PIVOT_RTOL
         g = self.g
         ok = g.info.reshape(-1)[0] == 0
         if check_pivots:
@@ -133,15 +135,18 @@ class HipGreedyBackend:
             raise RuntimeError("the jitter retry needs the backend to own a copy of Sigma")
         self.__init__(self._src, self.kmax, copy=True, jitter=eps)
 
+    def _slab_tmp(self, c0, c1):
+        """(pointer, bytes) of the scratch of the slab [c0, c1)'s inverse, grown on demand."""
+        need = query("vgposp_greedy_slab_tmp_bytes", self.g.n, c0, c1)
+        if self._tmp is None or self._tmp.numel() < need:
+            self._tmp = torch.empty(max(need, 8), dtype=torch.uint8, device=self.g.S.device)
+        return _p(self._tmp), self._tmp.numel()
+
     def init_slab(self, c0, c1):
         """Factor Sigma, form L^-1 only in columns [c0, c1) (vgposp_greedy_init_slab)."""
-        from ._lib import query
         g = self.g
-        need = query("vgposp_greedy_slab_tmp_bytes", g.n, c0, c1)
-        if self._tmp is None or self._tmp.numel() < need:
-            self._tmp = torch.empty(max(need, 8), dtype=torch.uint8, device=g.S.device)
         call("vgposp_greedy_init_slab", _p(g.S), g.n, g.S.stride(0), g.kmax, *g.params, c0, c1,
-             _p(self._tmp), self._tmp.numel(), _p(g.info), _p(g.ws), g.ws.numel(), _stream())
+             *self._slab_tmp(c0, c1), _p(g.info), _p(g.ws), g.ws.numel(), _stream())
         g.rounds = 0
 
     def prepare(self):
@@ -152,18 +157,13 @@ class HipGreedyBackend:
         g.rounds = 0
 
     def chol_ops(self):
-        from .dist_cholesky import greedy_cholesky_ops
         return greedy_cholesky_ops(self.g)
 
     def finish_slab(self, c0, c1):
         """After the factorization: L^-1 in columns [c0, c1) and their column norms."""
-        from ._lib import query
         g = self.g
-        need = query("vgposp_greedy_slab_tmp_bytes", g.n, c0, c1)
-        if self._tmp is None or self._tmp.numel() < need:
-            self._tmp = torch.empty(max(need, 8), dtype=torch.uint8, device=g.S.device)
         call("vgposp_greedy_finish_slab", _p(g.S), g.n, g.S.stride(0), g.kmax, c0, c1,
-             _p(self._tmp), self._tmp.numel(), _p(g.ws), g.ws.numel(), _stream())
+             *self._slab_tmp(c0, c1), _p(g.ws), g.ws.numel(), _stream())
 
     def extract(self, rnd, own0, own1):
         g = self.g
@@ -258,7 +258,6 @@ class ShardedGreedyPlacement:
     def _factor(self):
         self.b.snapshot_diag()
         if self.partition and self.world > 1 and self.dist_factor:
-            from .dist_cholesky import DIST_MIN, DistCholesky
             self.b.prepare()
             dc = DistCholesky(self.b.chol_ops(), self.group,
                               DIST_MIN if self.dist_min is None else self.dist_min)
@@ -273,8 +272,6 @@ class ShardedGreedyPlacement:
         """snippets of placement_algorithm2.py:151-219 over the ranks.  A singular cov_vv takes
         the single-GPU path's jitter retry (SINGULAR_EPS relative to the mean diagonal), decided
         identically on every rank."""
-        from ._lib import CholeskyError
-        from .placement_algorithm2 import SINGULAR_EPS
         self._factor()
         if not self.b.factor_ok(self.c0, self.c1, self.partition, check_pivots=True):
             scale = self.b.diag_scale()
