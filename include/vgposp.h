@@ -39,6 +39,7 @@ extern "C" {
 
 #define VGPOSP_E_HIP (-100)
 #define VGPOSP_E_WS (-101)
+#define VGPOSP_E_UNSUPPORTED (-102) /* a run-time library or one of its kernels is missing */
 
 /* PSD kernel families (tfp.positive_semidefinite_kernels). */
 #define VGPOSP_KERNEL_EQ 0       /* ExponentiatedQuadratic: 3D_sin_wave.py:158-159, main_tests.py:617 */
@@ -158,6 +159,46 @@ int vgposp_gemm_strassen(int transa, int transb, int64_t m, int64_t n, int64_t k
                          const double* A, int64_t lda, const double* B, int64_t ldb, double beta,
                          double* C, int64_t ldc, int levels, void* ws, size_t ws_bytes,
                          void* stream);
+
+/* The same product with fp64 emulated on the int8 matrix cores (the integer modular scheme,
+ * "Ozaki scheme II"; DESIGN.md §4 "fp64 products on the int8 matrix cores"): rows of op(A) and
+ * columns of op(B) are scaled by powers of two and truncated to integers below 2^s, sixteen int8
+ * residue planes per operand go through sixteen exact int8 -> int32 products of hipBLASLt, and
+ * every element is rebuilt exactly (Garner, a 128-bit integer, one rounding).  The error is the
+ * truncation alone: |dC_ij| <= 2 k 2^-s max_k|a_ik| max_k|b_kj| with s = floor((125.37 - 1 -
+ * ceil(log2 k)) / 2), at most 57; integer-valued operands below 2^s give the exact product.  A row
+ * of op(A) or column of op(B) with a non-finite entry makes its row or column of C NaN.
+ * k <= 65,536.  hipBLASLt is bound at run time (dlopen of libhipblaslt.so.1, the process's own copy
+ * first) and never linked: vgposp_gemm_emulation_available tells whether it resolved, and
+ * vgposp_gemm_emulated returns VGPOSP_E_UNSUPPORTED without it.  ws holds
+ * vgposp_gemm_emulated_workspace_bytes (the planes of both operands and the int32 results of one
+ * output block, together at most 24 GiB + the planes' excess over it).  Deterministic; all four
+ * layouts; C may overlap A or B.
+ * The fused Cholesky + inverse takes its large plain products (every dimension a multiple of 256
+ * and >= min_dim, the products Strassen takes at the same threshold) this way when the
+ * process-wide setting below has moduli = 16 and the library resolves; moduli = 0 turns it off.
+ * ON BY DEFAULT with min_dim 8192 (the 65k step 18.7 % faster), which leaves every
+ * n < 32,768 as it was; where the library does not resolve, everything is as without it.  The
+ * workspace queries of the factorization and of the greedy
+ * placement grow by the emulation scratch of the largest such product, appended behind the
+ * Strassen scratch, which keeps its size and place and serves when the library fails at run
+ * time.  Change the setting only between a workspace query and its use, consistently.
+ * Test hooks: set_unavailable(1) makes the library count as absent, set_block_cap(bytes) lowers
+ * the 24 GiB cap (0 restores it), garner runs the reconstruction of one element on the host
+ * (sixteen residues -> sixteen symmetric mixed-radix digits and their integer rounded to fp64),
+ * vgposp_gemm_set_abort_flag sets the calling thread's device abort flag of every dense product
+ * (a device int; non-zero = launches return without writing; NULL = none). */
+int vgposp_gemm_emulation_available(void);
+int vgposp_gemm_emulation_set_unavailable(int off);
+int vgposp_gemm_emulation_set_block_cap(size_t bytes);
+int vgposp_gemm_emulation_garner(const int32_t* residues, int32_t* digits, double* value);
+int vgposp_gemm_set_abort_flag(const void* flag);
+int vgposp_potrf_set_emulation(int64_t min_dim, int moduli);
+int vgposp_potrf_emulation(int64_t* min_dim, int* moduli);
+size_t vgposp_gemm_emulated_workspace_bytes(int64_t m, int64_t n, int64_t k);
+int vgposp_gemm_emulated(int transa, int transb, int64_t m, int64_t n, int64_t k, double alpha,
+                         const double* A, int64_t lda, const double* B, int64_t ldb, double beta,
+                         double* C, int64_t ldc, void* ws, size_t ws_bytes, void* stream);
 
 /* Grouped vgposp_gemm: `count` independent products, problem g with flags[5g..5g+4] = (transa,
  * transb, uplo_c, tri_a, tri_b), dims[3g..3g+2] = (m, n, k), alpha[g], beta[g], A[g] (lda[g]),

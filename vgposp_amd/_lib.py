@@ -92,6 +92,16 @@ SIGNATURES = {
     "vgposp_gemm_strassen": (_i32, [_i32, _i32, _i64, _i64, _i64, _f64, _c_void_p, _i64, _c_void_p,
                                     _i64, _f64, _c_void_p, _i64, _i32, _c_void_p, _size,
                                     _c_void_p]),
+    "vgposp_gemm_emulation_available": (_i32, []),
+    "vgposp_gemm_emulation_set_unavailable": (_i32, [_i32]),
+    "vgposp_gemm_emulation_set_block_cap": (_i32, [_size]),
+    "vgposp_gemm_emulation_garner": (_i32, [_c_void_p, _c_void_p, ctypes.POINTER(_f64)]),
+    "vgposp_gemm_set_abort_flag": (_i32, [_c_void_p]),
+    "vgposp_potrf_set_emulation": (_i32, [_i64, _i32]),
+    "vgposp_potrf_emulation": (_i32, [ctypes.POINTER(_i64), ctypes.POINTER(_i32)]),
+    "vgposp_gemm_emulated_workspace_bytes": (_size, [_i64, _i64, _i64]),
+    "vgposp_gemm_emulated": (_i32, [_i32, _i32, _i64, _i64, _i64, _f64, _c_void_p, _i64, _c_void_p,
+                                    _i64, _f64, _c_void_p, _i64, _c_void_p, _size, _c_void_p]),
     "vgposp_kernel_matrix_matvec_workspace_bytes": (_size, [_i64, _i64]),
     "vgposp_kernel_matrix_matvec": (_i32, [_i32, _c_void_p, _i64, _c_void_p, _i64, _i32,
                                            _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p,
@@ -379,7 +389,7 @@ def query(name, *args):
 # records to the build they were measured on)
 KERNEL_SOURCES = {
     # potrf.hip decides the step's GEMM shapes (structured splits, Strassen routing)
-    "gemm_f64": ["gemm.hip", "potrf.hip", "common.h", "Makefile"],
+    "gemm_f64": ["gemm.hip", "potrf.hip", "gemm_emul.hip", "common.h", "Makefile"],
     "greedy_trmv": ["greedy.hip", "common.h", "Makefile"],
     "greedy_colsq": ["greedy.hip", "common.h", "Makefile"],
     "criteria_symv": ["criteria.hip", "common.h", "Makefile"],

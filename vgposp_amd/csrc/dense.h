@@ -22,12 +22,24 @@ int gemm_launch_batched(int transa, int transb, int64_t m, int64_t n, int64_t k,
                         hipStream_t stream);
 int gemm_auto_splits(int64_t m, int64_t n, int64_t k, int uplo_c, int transa);
 void gemm_set_abort(const int* flag);
+const int* gemm_abort_flag();
 int gemm_strassen(int transa, int transb, int64_t m, int64_t n, int64_t k, double alpha,
                   const double* A, int64_t lda, const double* B, int64_t ldb, double beta, double* C,
                   int64_t ldc, int levels, int64_t min_dim, double* ws, int64_t ws_elems,
                   hipStream_t stream);
 int64_t gemm_strassen_ws_elems(int64_t m, int64_t n, int64_t k, int levels, int64_t min_dim);
 void gemm_strassen_config(int64_t* min_dim, int* levels);
+
+// ---- gemm_emul.hip --------------------------------------------------------------------------
+// fp64 products on the int8 matrix cores.  gemm_emulated returns 1, with nothing written, when
+// the int8 library is absent or has no kernel for a block shape: the caller takes its fp64 path.
+bool gemm_emul_available();
+size_t gemm_emul_ws_bytes(int64_t m, int64_t n, int64_t k);
+void gemm_emul_config(int64_t* min_dim, int* moduli);
+int gemm_emul_scale_bits(int64_t k);
+int gemm_emulated(int transa, int transb, int64_t m, int64_t n, int64_t k, double alpha,
+                  const double* A, int64_t lda, const double* B, int64_t ldb, double beta, double* C,
+                  int64_t ldc, void* ws, hipStream_t stream);
 
 // ---- potrf.hip ------------------------------------------------------------------------------
 int potrf_one(double* A, int64_t n, int64_t lda, int invert, double* diag_out, int* info,

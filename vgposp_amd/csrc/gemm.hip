@@ -1513,8 +1513,15 @@ void gemm_strassen_config(int64_t* min_dim, int* levels) {
 }
 
 void gemm_set_abort(const int* flag) { tl_gemm_abort = flag; }
+const int* gemm_abort_flag() { return tl_gemm_abort; }
 
 }  // namespace vgposp
+
+extern "C" int vgposp_gemm_set_abort_flag(const void* flag) {
+  vgposp::clear_error();
+  vgposp::gemm_set_abort(static_cast<const int*>(flag));
+  return 0;
+}
 
 extern "C" int vgposp_gemm_set_split_depth(int min_k) {
   using namespace vgposp;

@@ -340,6 +340,11 @@ struct Fact {
   double* str_ws = nullptr;
   int64_t str_elems = 0, str_min = 0;
   int str_levels = 0;
+  // int8 emulation scratch (potrf_one only; null = off or the library absent): emu_bytes bytes
+  // behind the Strassen scratch, for plain products whose dimensions are all >= emu_min
+  void* emu_ws = nullptr;
+  size_t emu_bytes = 0;
+  int64_t emu_min = 0;
   double* leaf(int64_t col0) const { return linv_all + (col0 / NB) * NB * NB; }
   double* xblk(int64_t col0) const { return xinv + col0 * NBI; }
   int64_t stride(const void* p) const {
@@ -366,12 +371,21 @@ static bool strassen_eligible(int64_t m, int64_t n, int64_t k, int64_t min_dim) 
   return gemm_strassen_ws_elems(m, n, k, 1, min_dim) > 0;
 }
 
+// The same question for the int8 emulation (gemm_emul.hip): the shapes Strassen takes at the same
+// threshold, as long as the int32 accumulation is exact (k <= 65,536).  min_dim 0 = off.
+static bool emul_eligible(int64_t m, int64_t n, int64_t k, int64_t min_dim) {
+  return min_dim > 0 && m % 256 == 0 && n % 256 == 0 && k % 256 == 0 && m >= min_dim &&
+         n >= min_dim && k >= min_dim && k <= 65536;
+}
+
 // With Strassen scratch, a structured product whose plain part would be eligible is split once
 // into two half-size structured products and that plain product (half of its flops), and so on
-// down: the plain parts then go through gemm_strassen.  Without scratch, or below the threshold,
-// each is the single structured launch.
+// down: the plain parts then go through gemm_emulated or gemm_strassen.  Without scratch, or below
+// the thresholds, each is the single structured launch.
 static bool split_plain(const Fact& f, int64_t m, int64_t n, int64_t k) {
-  return f.str_ws != nullptr && f.batch == 1 && strassen_eligible(m, n, k, f.str_min);
+  if (f.batch != 1) return false;
+  return (f.str_ws != nullptr && strassen_eligible(m, n, k, f.str_min)) ||
+         (f.emu_ws != nullptr && emul_eligible(m, n, k, f.emu_min));
 }
 
 // C = alpha op(A) op(B) + beta C with the split count of vgposp_gemm_splitk, reduced to what the
@@ -380,7 +394,21 @@ static bool split_plain(const Fact& f, int64_t m, int64_t n, int64_t k) {
 static int pgemm(const Fact& f, int transa, int transb, int64_t m, int64_t n, int64_t k,
                  double alpha, const double* A, int64_t lda, const double* B, int64_t ldb,
                  double beta, double* C, int64_t ldc, int uplo_c, int tri_a, int tri_b) {
-  if (uplo_c == VGPOSP_FULL && !tri_a && !tri_b && split_plain(f, m, n, k)) {
+  if (uplo_c == VGPOSP_FULL && !tri_a && !tri_b && f.batch == 1 && f.emu_ws != nullptr &&
+      emul_eligible(m, n, k, f.emu_min)) {
+    const size_t need = gemm_emul_ws_bytes(m, n, k);
+    if (need > f.emu_bytes) {
+      set_error("potrf: emulation scratch %zu < %zu bytes for the %lld x %lld x %lld product",
+                f.emu_bytes, need, (long long)m, (long long)n, (long long)k);
+      return VGPOSP_E_WS;
+    }
+    const int rc = gemm_emulated(transa, transb, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc,
+                                 f.emu_ws, f.s);
+    if (rc != 1) return rc;
+    // the int8 library failed at run time (no handle, no kernel): the fp64 paths below
+  }
+  if (uplo_c == VGPOSP_FULL && !tri_a && !tri_b && f.batch == 1 && f.str_ws != nullptr &&
+      strassen_eligible(m, n, k, f.str_min)) {
     // the scratch was sized by StrassenNeed's walk over these launches: a product it did not
     // plan for is an error here, not a quietly shallower gemm_strassen
     const int64_t need = gemm_strassen_ws_elems(m, n, k, f.str_levels, f.str_min);
@@ -609,14 +637,15 @@ static int potrf_rec(const Fact& f, double* A, int64_t n, int64_t col0, bool blo
 
 // The workspace of every entry point, as element offsets from its base: leaf inverses | trtri
 // scratch | block inverses | TRSM scratch (both only for n > NBI) | split-K partials (n > NB) |
-// 64 spare doubles | Strassen scratch.  The sharded entry points and partial_inverse read the
+// 64 spare doubles | Strassen scratch | int8 emulation scratch.  The sharded entry points and partial_inverse read the
 // first five in a workspace that another call filled, so their offsets depend on n alone.
 struct PotrfLayout {
-  int64_t n, work, xinv, tmp, part, part_elems, strassen, strassen_elems, total;
+  int64_t n, work, xinv, tmp, part, part_elems, strassen, strassen_elems, emul, emul_elems, total;
   size_t bytes() const { return (size_t)total * sizeof(double); }
 };
 
-static PotrfLayout potrf_layout(int64_t n, int64_t part_elems, int64_t strassen_elems) {
+static PotrfLayout potrf_layout(int64_t n, int64_t part_elems, int64_t strassen_elems,
+                                int64_t emul_elems = 0) {
   const int64_t n1 = n > NB ? split_point(n) : 0, blk = n > NBI ? n * NBI : 0;
   PotrfLayout l{n};
   l.work = ceil_div(n, NB) * NB * NB;
@@ -626,7 +655,10 @@ static PotrfLayout potrf_layout(int64_t n, int64_t part_elems, int64_t strassen_
   l.part_elems = n > NB ? part_elems : 0;
   l.strassen = l.part + l.part_elems + 64;
   l.strassen_elems = strassen_elems;
-  l.total = l.strassen + strassen_elems;
+  // (nothing is added, not even the alignment, when there is no emulation scratch)
+  l.emul = emul_elems > 0 ? (l.strassen + strassen_elems + 31) / 32 * 32 : l.strassen + strassen_elems;
+  l.emul_elems = emul_elems;
+  l.total = l.emul + emul_elems;
   return l;
 }
 
@@ -634,28 +666,35 @@ static PotrfLayout potrf_layout(int64_t n, int64_t part_elems, int64_t strassen_
 // the plain products that potrf_rec / trsm_rec / psyrk and trtri_rec / ptrmm_b / ptrmm_a launch
 // for this n (a walk over the same splits, a few hundred nodes at n = 65,536).  0 when no product
 // is eligible: nothing is appended then and every launch is the classical one.
+// The same walk sizes the emulation scratch (emu_min > 0): the largest gemm_emul_ws_bytes.
 struct StrassenNeed {
   int64_t min_dim;
   int levels;
+  int64_t emu_min = 0;
   int64_t need = 0;
+  size_t emu_need = 0;
+  bool eligible(int64_t m, int64_t n, int64_t k) const {
+    return (levels > 0 && strassen_eligible(m, n, k, min_dim)) || emul_eligible(m, n, k, emu_min);
+  }
   void plain(int64_t m, int64_t n, int64_t k) {
-    need = std::max(need, gemm_strassen_ws_elems(m, n, k, levels, min_dim));
+    if (levels > 0) need = std::max(need, gemm_strassen_ws_elems(m, n, k, levels, min_dim));
+    if (emul_eligible(m, n, k, emu_min)) emu_need = std::max(emu_need, gemm_emul_ws_bytes(m, n, k));
   }
   void syrk(int64_t n, int64_t k) {
     const int64_t h = n / 2;
-    if (n % 2 != 0 || !strassen_eligible(h, h, k, min_dim)) return;
+    if (n % 2 != 0 || !eligible(h, h, k)) return;
     plain(h, h, k);
     syrk(h, k);
   }
   void trmm_b(int64_t m, int64_t n) {
     const int64_t h = n / 2;
-    if (n % 2 != 0 || !strassen_eligible(m, h, h, min_dim)) return;
+    if (n % 2 != 0 || !eligible(m, h, h)) return;
     plain(m, h, h);
     trmm_b(m, h);
   }
   void trmm_a(int64_t m, int64_t n) {
     const int64_t h = m / 2;
-    if (m % 2 != 0 || !strassen_eligible(h, n, h, min_dim)) return;
+    if (m % 2 != 0 || !eligible(h, n, h)) return;
     plain(h, n, h);
     trmm_a(h, n);
   }
@@ -667,7 +706,8 @@ struct StrassenNeed {
     if (b != a) trsm(m, b);
   }
   void node(int64_t n) {  // potrf_rec and trtri_rec of an order-n diagonal block
-    if (n <= NBI || n < 2 * min_dim) return;  // (every product below has a dimension < min_dim)
+    const int64_t lo = levels <= 0 ? emu_min : emu_min <= 0 ? min_dim : std::min(min_dim, emu_min);
+    if (n <= NBI || n < 2 * lo) return;  // (every product below has a dimension < the thresholds)
     const int64_t n1 = split_point(n), n2 = n - n1;
     trsm(n2, n1);
     syrk(n2, n1);
@@ -678,18 +718,45 @@ struct StrassenNeed {
   }
 };
 
-static int64_t potrf_strassen_elems(int64_t n, int64_t min_dim, int levels) {
-  if (levels <= 0 || n <= NBI) return 0;
-  StrassenNeed s{min_dim, levels};
+// The process-wide settings of the large plain products, read once per call: scratch sizes,
+// thresholds and levels belong together.  emu_min > 0 only with the setting on AND the int8
+// library resolved, so the workspace queries and the factorization agree.
+struct BigCfg {
+  int64_t min_dim = 0;
+  int levels = 0;
+  int64_t emu_min = 0;
+};
+
+static BigCfg big_config(bool on = true) {
+  BigCfg c;
+  if (!on) return c;
+  gemm_strassen_config(&c.min_dim, &c.levels);
+  int64_t emin;
+  int moduli;
+  gemm_emul_config(&emin, &moduli);
+  if (moduli > 0 && gemm_emul_available()) c.emu_min = emin;
+  return c;
+}
+
+struct BigNeed {
+  int64_t strassen_elems = 0, emul_elems = 0;
+};
+
+static BigNeed potrf_big_need(int64_t n, const BigCfg& c) {
+  BigNeed b;
+  if ((c.levels <= 0 && c.emu_min <= 0) || n <= NBI) return b;
+  StrassenNeed s{c.min_dim, c.levels, c.emu_min};
   s.node(n);
-  return s.need;
+  b.strassen_elems = s.need;
+  b.emul_elems = (int64_t)((s.emu_need + 7) / 8);
+  return b;
 }
 
 // One matrix: 64 MiB of partials.  Without Strassen scratch this is what the sharded entry points
 // and partial_inverse address (potrf_one's scratch, if any, lies behind it).
-static PotrfLayout potrf_layout_one(int64_t n, int64_t strassen_elems = 0,
+static PotrfLayout potrf_layout_one(int64_t n, const BigNeed& big = BigNeed{},
                                     int64_t part_elems = PART_ELEMS) {
-  return potrf_layout(n, part_elems, strassen_elems);
+  return potrf_layout(n, part_elems, big.strassen_elems, big.emul_elems);
 }
 
 // The partials an order-n factorization can use.  Its products have both output dimensions <= n
@@ -707,18 +774,11 @@ static PotrfLayout potrf_layout_batched(int64_t n, bool use_part) {
 }
 
 size_t potrf_ws_bytes(int64_t n) {
-  int64_t min_dim;
-  int levels;
-  gemm_strassen_config(&min_dim, &levels);
-  return potrf_layout_one(n, potrf_strassen_elems(n, min_dim, levels)).bytes();
+  return potrf_layout_one(n, potrf_big_need(n, big_config())).bytes();
 }
 
 size_t potrf_ws_bytes_compact(int64_t n) {
-  int64_t min_dim;
-  int levels;
-  gemm_strassen_config(&min_dim, &levels);
-  return potrf_layout_one(n, potrf_strassen_elems(n, min_dim, levels), part_elems_compact(n))
-      .bytes();
+  return potrf_layout_one(n, potrf_big_need(n, big_config()), part_elems_compact(n)).bytes();
 }
 
 size_t potrf_ws_bytes_opt(int64_t n, bool use_part) {
@@ -748,6 +808,8 @@ static Fact make_fact(const PotrfLayout& l, int64_t lda, void* ws, double* diag_
          l.part_elems > 0 ? base + l.part : nullptr, stream, l.part_elems};
   f.str_ws = l.strassen_elems > 0 ? base + l.strassen : nullptr;
   f.str_elems = l.strassen_elems;
+  f.emu_ws = l.emul_elems > 0 ? base + l.emul : nullptr;
+  f.emu_bytes = 8 * (size_t)l.emul_elems;
   return f;
 }
 
@@ -782,14 +844,13 @@ int potrf_one(double* A, int64_t n, int64_t lda, int invert, double* diag_out, i
               void* ws, hipStream_t stream, bool early, bool strassen, bool compact) {
   if (int rc = ensure_leaf_attr()) return rc;
   const bool blocks = n > NBI;
-  int64_t min_dim = 0;
-  int levels = 0;  // the setting is read once: scratch size, threshold and levels belong together
-  if (strassen) gemm_strassen_config(&min_dim, &levels);
-  Fact f = make_fact(potrf_layout_one(n, potrf_strassen_elems(n, min_dim, levels),
+  const BigCfg cfg = big_config(strassen);
+  Fact f = make_fact(potrf_layout_one(n, potrf_big_need(n, cfg),
                                       compact ? part_elems_compact(n) : PART_ELEMS),
                      lda, ws, diag_out, info, stream);
-  f.str_min = min_dim;
-  f.str_levels = levels;
+  f.str_min = cfg.min_dim;
+  f.str_levels = cfg.levels;
+  f.emu_min = cfg.emu_min;
   f.early = early;
   AbortScope scope(early ? info : nullptr);
   int rc = potrf_rec(f, A, n, 0, blocks);
