@@ -200,6 +200,41 @@ int vgposp_gemm_emulated(int transa, int transb, int64_t m, int64_t n, int64_t k
                          const double* A, int64_t lda, const double* B, int64_t ldb, double beta,
                          double* C, int64_t ldc, void* ws, size_t ws_bytes, void* stream);
 
+/* The structured products of the factorization on the same int8 path, each as a staircase of
+ * rectangular block products over planes that are split ONCE:
+ *   VGPOSP_EMUL_SYRK_LOWER  C (n x n, lower triangle only) = alpha A A^T + beta C,  A n x k (m = n;
+ *                           B is not read); the strict upper triangle of C is neither read nor
+ *                           written;
+ *   VGPOSP_EMUL_TRMM_B      C (m x n) = alpha A X + beta C,  A m x n, X = B n x n lower triangular
+ *                           stored [k][j] (k = n);
+ *   VGPOSP_EMUL_TRMM_A      C (m x n) = alpha X B + beta C,  X = A m x m lower triangular stored
+ *                           [i][k], B m x n (k = m).
+ * The strict upper triangle of X is never loaded.  Error bound and non-finite rule as above, with
+ * the maxima taken over the entries that are read.  ws may be of any size: the planner cuts the
+ * product into tiles whose planes and int32 block fit ws_bytes (and the block cap);
+ * VGPOSP_E_UNSUPPORTED when not even one block fits or the library has no kernel.  C must not
+ * overlap A or B.  vgposp_gemm_emulation_tri_plan is the planner alone (no GPU): the steps, 14
+ * int64 each (tile, tile rows r0 r1, tile columns c0 c1, the depth ka kb its planes hold, the
+ * step's rows i0 i1, columns j0 j1 and depth k0 k1, the tile's bytes), and the int8 flops
+ * (2 * 16 * rows * columns * depth rounded up to 128, summed); it returns the number of steps or -1.
+ * The fused Cholesky + inverse sends a structured product here exactly where it would otherwise
+ * split it for the plain-product emulation (vgposp_potrf_set_emulation_structured(0) turns that
+ * off; on by default).  Test hook: set_tri_block(width) sets the staircase's block width (a
+ * multiple of 128; 0 restores the default, 2,048). */
+#define VGPOSP_EMUL_SYRK_LOWER 0
+#define VGPOSP_EMUL_TRMM_B 1
+#define VGPOSP_EMUL_TRMM_A 2
+#define VGPOSP_EMUL_TRI_STEP_FIELDS 14
+int vgposp_gemm_emulation_set_tri_block(int64_t width);
+int vgposp_potrf_set_emulation_structured(int on);
+int vgposp_potrf_emulation_structured(void);
+int64_t vgposp_gemm_emulation_tri_plan(int kind, int64_t m, int64_t n, int64_t k, size_t bytes,
+                                       int64_t* steps, int64_t cap_steps, double* flops);
+int vgposp_gemm_emulated_tri(int kind, int64_t m, int64_t n, int64_t k, double alpha,
+                             const double* A, int64_t lda, const double* B, int64_t ldb,
+                             double beta, double* C, int64_t ldc, void* ws, size_t ws_bytes,
+                             void* stream);
+
 /* Grouped vgposp_gemm: `count` independent products, problem g with flags[5g..5g+4] = (transa,
  * transb, uplo_c, tri_a, tri_b), dims[3g..3g+2] = (m, n, k), alpha[g], beta[g], A[g] (lda[g]),
  * B[g] (ldb[g]), C[g] (ldc[g]), all in ONE launch (problem on blockIdx.y) plus one grouped split-K

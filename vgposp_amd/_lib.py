@@ -102,6 +102,13 @@ SIGNATURES = {
     "vgposp_gemm_emulated_workspace_bytes": (_size, [_i64, _i64, _i64]),
     "vgposp_gemm_emulated": (_i32, [_i32, _i32, _i64, _i64, _i64, _f64, _c_void_p, _i64, _c_void_p,
                                     _i64, _f64, _c_void_p, _i64, _c_void_p, _size, _c_void_p]),
+    "vgposp_gemm_emulation_set_tri_block": (_i32, [_i64]),
+    "vgposp_potrf_set_emulation_structured": (_i32, [_i32]),
+    "vgposp_potrf_emulation_structured": (_i32, []),
+    "vgposp_gemm_emulation_tri_plan": (_i64, [_i32, _i64, _i64, _i64, _size, _c_void_p, _i64,
+                                              ctypes.POINTER(_f64)]),
+    "vgposp_gemm_emulated_tri": (_i32, [_i32, _i64, _i64, _i64, _f64, _c_void_p, _i64, _c_void_p,
+                                        _i64, _f64, _c_void_p, _i64, _c_void_p, _size, _c_void_p]),
     "vgposp_kernel_matrix_matvec_workspace_bytes": (_size, [_i64, _i64]),
     "vgposp_kernel_matrix_matvec": (_i32, [_i32, _c_void_p, _i64, _c_void_p, _i64, _i32,
                                            _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p,

@@ -40,6 +40,12 @@ int gemm_emul_scale_bits(int64_t k);
 int gemm_emulated(int transa, int transb, int64_t m, int64_t n, int64_t k, double alpha,
                   const double* A, int64_t lda, const double* B, int64_t ldb, double beta, double* C,
                   int64_t ldc, void* ws, hipStream_t stream);
+// The structured products (kind: VGPOSP_EMUL_SYRK_LOWER / _TRMM_B / _TRMM_A) as a staircase of
+// int8 block products within ws_bytes; 1 with nothing written like gemm_emulated.
+bool gemm_emul_tri_enabled();
+int gemm_emulated_tri(int kind, int64_t m, int64_t n, int64_t k, double alpha, const double* A,
+                      int64_t lda, const double* B, int64_t ldb, double beta, double* C,
+                      int64_t ldc, void* ws, size_t ws_bytes, hipStream_t stream);
 
 // ---- potrf.hip ------------------------------------------------------------------------------
 int potrf_one(double* A, int64_t n, int64_t lda, int invert, double* diag_out, int* info,

@@ -388,6 +388,16 @@ static bool split_plain(const Fact& f, int64_t m, int64_t n, int64_t k) {
          (f.emu_ws != nullptr && emul_eligible(m, n, k, f.emu_min));
 }
 
+// A structured product that would be split for the emulation of its plain part (its plain half
+// m x n x k is eligible, one matrix, emulation scratch present) goes whole to its staircase driver
+// of gemm_emul.hip instead: every operand split once, the triangle never loaded.  The driver
+// tiles itself into f.emu_bytes; when it returns 1 (no kernel, nothing written) the recursion
+// below it runs as before.
+static bool tri_routed(const Fact& f, int64_t m, int64_t n, int64_t k) {
+  return f.batch == 1 && f.emu_ws != nullptr && emul_eligible(m, n, k, f.emu_min) &&
+         gemm_emul_tri_enabled();
+}
+
 // C = alpha op(A) op(B) + beta C with the split count of vgposp_gemm_splitk, reduced to what the
 // partials area holds.  In-place operands (C also read as A) are safe: the split kernels only
 // write the partials, the reduction writes C after all of them.
@@ -437,6 +447,10 @@ static int psyrk(const Fact& f, int64_t n, int64_t k, double alpha, const double
   if (n % 2 != 0 || !split_plain(f, h, h, k))
     return pgemm(f, 0, 1, n, n, k, alpha, A, lda, A, lda, beta, C, ldc, VGPOSP_LOWER, 0, 0);
   int rc;
+  if (tri_routed(f, h, h, k) &&
+      (rc = gemm_emulated_tri(VGPOSP_EMUL_SYRK_LOWER, n, n, k, alpha, A, lda, nullptr, 0, beta, C,
+                              ldc, f.emu_ws, f.emu_bytes, f.s)) != 1)
+    return rc;
   if ((rc = psyrk(f, h, k, alpha, A, lda, beta, C, ldc))) return rc;
   if ((rc = pgemm(f, 0, 1, h, h, k, alpha, A + h * lda, lda, A, lda, beta, C + h * ldc, ldc,
                   VGPOSP_FULL, 0, 0)))
@@ -451,6 +465,10 @@ static int ptrmm_b(const Fact& f, int64_t m, int64_t n, double alpha, const doub
   if (n % 2 != 0 || !split_plain(f, m, h, h))
     return pgemm(f, 0, 0, m, n, n, alpha, L, ldl, X, ldx, beta, W, ldw, VGPOSP_FULL, 0, 1);
   int rc;
+  if (tri_routed(f, m, h, h) &&
+      (rc = gemm_emulated_tri(VGPOSP_EMUL_TRMM_B, m, n, n, alpha, L, ldl, X, ldx, beta, W, ldw,
+                              f.emu_ws, f.emu_bytes, f.s)) != 1)
+    return rc;
   // W1 = L1 Xa + L2 Xb,  W2 = L2 Xc
   if ((rc = ptrmm_b(f, m, h, alpha, L, ldl, X, ldx, beta, W, ldw))) return rc;
   if ((rc = pgemm(f, 0, 0, m, h, h, alpha, L + h, ldl, X + h * ldx, ldx, 1.0, W, ldw, VGPOSP_FULL,
@@ -466,6 +484,10 @@ static int ptrmm_a(const Fact& f, int64_t m, int64_t n, double alpha, const doub
   if (m % 2 != 0 || !split_plain(f, h, n, h))
     return pgemm(f, 0, 0, m, n, m, alpha, X, ldx, W, ldw, beta, Y, ldy, VGPOSP_FULL, 1, 0);
   int rc;
+  if (tri_routed(f, h, n, h) &&
+      (rc = gemm_emulated_tri(VGPOSP_EMUL_TRMM_A, m, n, m, alpha, X, ldx, W, ldw, beta, Y, ldy,
+                              f.emu_ws, f.emu_bytes, f.s)) != 1)
+    return rc;
   // Y1 = Xa W1,  Y2 = Xc W2 + Xb W1
   if ((rc = ptrmm_a(f, h, n, alpha, X, ldx, W, ldw, beta, Y, ldy))) return rc;
   if ((rc = ptrmm_a(f, h, n, alpha, X + h * ldx + h, ldx, W + h * ldw, ldw, beta, Y + h * ldy, ldy)))
