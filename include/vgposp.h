@@ -938,6 +938,56 @@ int vgposp_critf_buffers(void* ws, int64_t n, int64_t s, int kmax, double** nom,
                          double** delta, double** W);
 
 /* ---------------------------------------------------------------------------------------------
+ * Mutual-information placement on a factored covariance Sigma = F F^T + D, D = diag(noise) with
+ * noise_i > 0 at EVERY location (D must be invertible): the reference's own criterion, the full
+ * greedy of placement_algorithm2.py:128-145 with the deltas of :371-413, on the reference's own
+ * covariance (main.py:190-199), at site counts where neither Sigma nor its inverse can be stored.
+ * Woodbury:
+ *   Q = Sigma^-1 = D^-1 - D^-1 F C^-1 F^T D^-1,   C = I_s + F^T D^-1 F   (s x s, SPD, lambda_min >= 1)
+ * With C = L L^T and M = L^-1 (vgposp_potrf_lower's recursion, invert = 1) the rounds of
+ * vgposp_greedy_step read three closed forms on F:
+ *   Q_yy = 1 / d_y - |M f_y|^2 / d_y^2                    once, O(n s^2) through vgposp_gemm's kernels
+ *   column a of Sigma:  s_i = f_i . f_a, dg_a at i = a
+ *   column a of Q:      q_i = [i = a] / d_a - (f_i . u_a) / d_i,   u_a = C^-1 f_a / d_a
+ * and then do greedy_update_kernel's arithmetic with jitter 0: s and q downdated by the earlier
+ * rows of W and V through the pick's pivots, w = s / sqrt(nom_a) (0 unless nom_a >= threshold and
+ * > 0), v = q / sqrt(prec_a) (0 unless prec_a > 0), nom -= w^2, prec -= v^2, and
+ * delta = nom / (1 / prec), 0 where |nom| or |1 / prec| is below the threshold.
+ * Selection: the arg-max over the FRESH delta of every free candidate, ties to the lower index
+ * (the full greedy, vgposp_greedy_step with lazy = 0).  The lazy cache of vgposp_greedy_step, its
+ * default, exists to save evaluations; here every delta is fresh after the one stream over F a
+ * round needs anyway, so it is not emulated and there is no `evals`.  Masked locations (`allowed`)
+ * are never picked and stay in every denominator; forced rounds as in vgposp_crit_step; no
+ * candidate left -> selected[round] = -1 and the round changes nothing.
+ *   vgposp_fmi_init   dg, C (the moment-matrix loop of vgposp_factor_symv_sq with x = 1 / d),
+ *                     M, C^-1 = M^T M, prec = Q_yy, nom = dg, the masks.  info (device int32):
+ *                     the factorization's status, 0 whenever d > 0.
+ *   vgposp_fmi_step   four launches: score, select (+ the pick's pivots), u_a (a wave per row of
+ *                     C^-1, fixed order), and one stream over F that forms f_i . f_a and f_i . u_a
+ *                     from a single read of each row (16-byte loads when ldf is even and F is
+ *                     16-byte aligned, else 8-byte) and applies both downdates: 8 n s +
+ *                     8 n (2 round + 6) bytes.  No float atomics, two runs are bit-identical, no
+ *                     host synchronisation.
+ *   vgposp_fmi_buffers  device pointers into ws, each output optional: nom [n], prec [n],
+ *                     delta [n] (as scored by the last round, before its pick), W and V
+ *                     [kmax][n].
+ *   vgposp_fmi_workspace_bytes(n, s, kmax): 2 kmax n + O(n) + 2 s^2 doubles, the chunk area of
+ *                     vgposp_factor_symv_workspace_bytes and the s x s factorization's
+ *                     workspace; 0 when n <= 0, s <= 0 or kmax <= 0.
+ * Limits and argument groups are those of vgposp_critf_*: 1 <= s <= 4,096, n <= 2^21, ldf >= s,
+ * 1 <= kmax <= n; noise must not be NULL.  Argument errors return -(position) before any device
+ * work, a short workspace VGPOSP_E_WS. */
+size_t vgposp_fmi_workspace_bytes(int64_t n, int64_t s, int kmax);
+int vgposp_fmi_init(const double* F, int64_t n, int64_t s, int64_t ldf, const double* noise,
+                    int kmax, double threshold, const unsigned char* allowed, int* info,
+                    void* ws, size_t ws_bytes, void* stream);
+int vgposp_fmi_step(const double* F, int64_t n, int64_t s, int64_t ldf, const double* noise,
+                    int kmax, int round, const int64_t* forced, int64_t j, int64_t* selected,
+                    double* sel_delta, void* ws, size_t ws_bytes, void* stream);
+int vgposp_fmi_buffers(void* ws, int64_t n, int64_t s, int kmax, double** nom, double** prec,
+                       double** delta, double** W, double** V);
+
+/* ---------------------------------------------------------------------------------------------
  * Exact algorithm 3 at grid sizes where cov_vv cannot be dense (config C4, 128^3): the beta-decay
  * tapered covariance (main_architecture_2_sampledistribution.py:355-421) is a sparse SPD stencil
  * matrix, and snippets_a3.sparse_placement_algorithm_3 (snippets_a3.py:43-364) with tf_nominator /

@@ -334,6 +334,13 @@ SIGNATURES = {
                                          _c_void_p, _size, _c_void_p]),
     "vgposp_critf_buffers": (_i32, [_c_void_p, _i64, _i64, _i32]
                              + [ctypes.POINTER(_c_void_p)] * 4),
+    "vgposp_fmi_workspace_bytes": (_size, [_i64, _i64, _i32]),
+    "vgposp_fmi_init": (_i32, _SFAC + [_i32, _f64, _c_void_p, _c_void_p, _c_void_p, _size,
+                                       _c_void_p]),
+    "vgposp_fmi_step": (_i32, _SFAC + [_i32, _i32, _c_void_p, _i64, _c_void_p, _c_void_p,
+                                       _c_void_p, _size, _c_void_p]),
+    "vgposp_fmi_buffers": (_i32, [_c_void_p, _i64, _i64, _i32]
+                           + [ctypes.POINTER(_c_void_p)] * 5),
 }
 
 _lock = threading.Lock()
@@ -402,6 +409,7 @@ KERNEL_SOURCES = {
     "criteria_symv": ["criteria.hip", "common.h", "Makefile"],
     "criteria_fsymv": ["criteria.hip", "common.h", "Makefile"],
     "criteria_fsymv_sq": ["criteria.hip", "common.h", "Makefile"],
+    "criteria_fmi_row": ["criteria.hip", "common.h", "Makefile"],
     "criteria_gemv_t": ["criteria.hip", "common.h", "Makefile"],
     "criteria_gemv_t_sq": ["criteria.hip", "common.h", "Makefile"],
     "criteria_kgemv_t": ["criteria.hip", "psd.h", "common.h", "Makefile"],

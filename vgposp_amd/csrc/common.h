@@ -248,6 +248,14 @@ __device__ __forceinline__ void wave_keymax(double& v, long long& i) {
   i = key_index(k);
 }
 
+// The mutual-information delta (greedy.hip, and criteria.hip's rounds on a factor).
+// denom = conditional variance of y given V \ (A u {y}) with eps on that block's diagonal:
+// 1 / [(Sigma_SS + eps I)^-1]_yy - eps (Sherman-Morrison on the y entry of the jitter).
+__device__ __forceinline__ double delta_of(double nom, double prec, double eps, double thr) {
+  const double den = 1.0 / prec - eps;
+  if (fabs(den) < thr || fabs(nom) < thr) return 0.0;  // :198 / snippets_a2.py:440-487
+  return nom / den;
+}
 
 }  // namespace vgposp
 

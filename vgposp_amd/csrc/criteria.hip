@@ -31,7 +31,8 @@
 // entries).  The third source is a factor: Sigma = F F^T + diag(noise) with F [n][S] the centred
 // samples of an empirical covariance (SFactor, the critf entries): a pass is two tall-skinny
 // streams over F.  The targets may lie outside V, with their cross-covariance R stored
-// (CrossStored) or generated (KGen).
+// (CrossStored) or generated (KGen).  On a factor with noise > 0 everywhere the mutual-information
+// rule runs too, through Woodbury's identity (FmiWS, the fmi entries at the end of the namespace).
 //
 // The host side is written once: one start (crit_init_run) and one round (crit_step_run), both
 // templates on where Sigma comes from (SigmaStored, SGen, SFactor) and on where the targets are
@@ -1372,14 +1373,11 @@ __global__ __launch_bounds__(256) void factor_scale_kernel(const double* __restr
   tmp[e] = x[i] * F[i * ldf + j];
 }
 
-// y_j = sum_i x_i Sigma_ij^2 through the moment matrix M = F^T diag(x) F, both products in row
-// chunks of w.rc rows through the fp64 MFMA GEMM (split-K for the S x S result of a long chunk).
-// dg must hold the diagonal.
-static int factor_symv_sq_launch(const SFactor& f, int64_t n, const double* x, double* y,
-                                 const FacWS& w, hipStream_t s) {
+// w.M = F^T diag(x) F (S x S, full) in row chunks of w.rc rows through the fp64 MFMA GEMM (split-K
+// for the S x S result of a long chunk).
+static int factor_moment_launch(const SFactor& f, int64_t n, const double* x, const FacWS& w,
+                                hipStream_t s) {
   const int64_t S = f.S;
-  const double ns = (double)n * (double)S;
-  ProfScope ps("criteria_fsymv_sq", s, 4.0 * ns * (double)S, 8.0 * 5.0 * ns);
   for (int64_t c0 = 0; c0 < n; c0 += w.rc) {
     const int64_t rc = std::min(w.rc, n - c0);
     const double* Fc = f.F + c0 * f.ldf;
@@ -1391,6 +1389,17 @@ static int factor_symv_sq_launch(const SFactor& f, int64_t n, const double* x, d
                                     s))
       return rc2;
   }
+  return 0;
+}
+
+// y_j = sum_i x_i Sigma_ij^2 through the moment matrix M = F^T diag(x) F and the rows of F M, both
+// in chunks through the GEMM.  dg must hold the diagonal.
+static int factor_symv_sq_launch(const SFactor& f, int64_t n, const double* x, double* y,
+                                 const FacWS& w, hipStream_t s) {
+  const int64_t S = f.S;
+  const double ns = (double)n * (double)S;
+  ProfScope ps("criteria_fsymv_sq", s, 4.0 * ns * (double)S, 8.0 * 5.0 * ns);
+  if (int rc2 = factor_moment_launch(f, n, x, w, s)) return rc2;
   for (int64_t c0 = 0; c0 < n; c0 += w.rc) {
     const int64_t rc = std::min(w.rc, n - c0);
     const SFactor fc{f.F + c0 * f.ldf, S, f.ldf, nullptr};
@@ -1716,6 +1725,317 @@ static void critx_outputs(const CritXWS& w, double** nom, double** score, double
                           double** W, double** U) {
   crit_outputs(w.c, nom, score, delta, W);
   if (U) *U = w.U;
+}
+
+// ---- mutual information on a factor: Sigma = F F^T + D, D = diag(noise) > 0 (Woodbury) ----
+// The rounds of greedy.hip need Q = Sigma^-1, which at n S doubles cannot be stored either:
+//   Q = D^-1 - D^-1 F C^-1 F^T D^-1,   C = I_S + F^T D^-1 F   (S x S, SPD, lambda_min >= 1)
+// With C = L L^T and M = L^-1 (potrf_one, invert = 1) everything the rounds read is a closed form
+// on F, d = noise and dg_i = f_i . f_i + d_i:
+//   Q_yy          = 1 / d_y - |M f_y|^2 / d_y^2                         once, O(n S^2)
+//   Sigma e_a     : s_i = f_i . f_a, dg_a at i = a
+//   Q e_a         : q_i = [i = a] / d_a - (f_i . u_a) / d_i,   u_a = C^-1 f_a / d_a   (an S-vector)
+// The rest is greedy_update_kernel's arithmetic with jitter 0: s and q downdated by the earlier
+// rows of W and V through the pick's pivots, w = s / sqrt(nom_a), v = q / sqrt(prec_a), nom -= w^2,
+// prec -= v^2, delta = delta_of(nom, prec, 0, thr).  A round scores and selects first, then updates
+// for its pick (crit_step_run's order); the arg-max runs over the fresh delta of every free
+// candidate, ties to the lower index: the full greedy.  Every delta is fresh after the one stream
+// over F a round needs anyway, so there is no lazy cache to save evaluations.  Masked locations
+// stay in every denominator.  Four launches a round, F read once, no float atomics.
+// piv: [0] nom_a, [1] prec_a, [2 + t] W_t[a], [2 + kmax + t] V_t[a].
+struct FmiWS {
+  double *prm, *nom, *prec, *delta, *W, *V, *piv, *u, *Cinv, *fval;
+  long long* fidx;
+  unsigned char* selmask;
+  void *fac, *potrf;  // fac_layout's area: dg kept; M, the chunk and its partials at init only
+  bool compact;       // the layout of the factorization's workspace
+  size_t bytes;
+};
+
+static FmiWS fmi_layout(void* base, int64_t n, int64_t S, int kmax) {
+  FmiWS w{};
+  const int64_t nch = ceil_div(n, CR_CH);
+  char* p = static_cast<char*>(base);
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char* r = p ? p + off : nullptr;
+    off += cr_align(bytes);
+    return r;
+  };
+  w.prm = (double*)take(8 * 8);
+  w.nom = (double*)take(n * 8);
+  w.prec = (double*)take(n * 8);
+  w.delta = (double*)take(n * 8);
+  w.W = (double*)take((size_t)kmax * n * 8);
+  w.V = (double*)take((size_t)kmax * n * 8);
+  w.piv = (double*)take((2 + 2 * (size_t)kmax) * 8);
+  w.u = (double*)take((size_t)S * 8);
+  w.Cinv = (double*)take((size_t)S * S * 8);
+  w.fval = (double*)take(nch * 8);
+  w.fidx = (long long*)take(nch * 8);
+  w.selmask = (unsigned char*)take(n);
+  w.fac = take(fac_layout(nullptr, n, S).bytes);
+  w.compact = potrf_ws_bytes_compact(S) < potrf_ws_bytes(S);
+  w.potrf = take(potrf_ws_bytes_compact(S));
+  w.bytes = off;
+  return w;
+}
+
+__global__ void fmi_recip_kernel(int64_t n, const double* __restrict__ noise,
+                                 double* __restrict__ x) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) x[i] = 1.0 / noise[i];
+}
+
+// C = M + I on the diagonal (before the factorization); after it, zeros above the diagonal of
+// M = L^-1, which the factorization never writes.
+__global__ void fmi_square_kernel(int64_t S, double* __restrict__ M, int after) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= S * S) return;
+  const int64_t i = e / S, j = e - i * S;
+  if (!after && i == j) M[e] += 1.0;
+  if (after && j > i) M[e] = 0.0;
+}
+
+// nom = dg, prec = Q_yy from tsq_y = |M f_y|^2 (held in prec), the masks and prm.
+__global__ void fmi_init_kernel(int64_t n, const double* __restrict__ dg,
+                                const double* __restrict__ noise, double thr,
+                                const unsigned char* allowed, FmiWS w) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {
+    const double d = noise[i];
+    w.nom[i] = dg[i];
+    w.prec[i] = 1.0 / d - w.prec[i] / (d * d);
+    w.delta[i] = 0.0;
+    w.selmask[i] = (allowed && !allowed[i]) ? 1 : 0;
+  }
+  if (i == 0) w.prm[0] = thr;
+}
+
+// delta for every location, and the best key of the workgroup over the free candidates.
+__global__ __launch_bounds__(CR_CH) void fmi_score_kernel(int64_t n, FmiWS w) {
+  const int64_t i = (int64_t)blockIdx.x * CR_CH + threadIdx.x;
+  const double thr = w.prm[0];
+  double bv = -DBL_MAX;
+  long long bi = -1;
+  if (i < n) {
+    const double d = delta_of(w.nom[i], w.prec[i], 0.0, thr);
+    w.delta[i] = d;
+    if (!w.selmask[i]) {
+      bv = d;
+      bi = i;
+    }
+  }
+  crit_block_keymax(bv, bi);
+  if (threadIdx.x == 0) {
+    w.fval[blockIdx.x] = bv;
+    w.fidx[blockIdx.x] = bi;
+  }
+}
+
+// crit_select_kernel with the pivots of both sides.  No candidate left: selected[round] = -1, and
+// the rest of the round does nothing.
+__global__ __launch_bounds__(CR_CH) void fmi_select_kernel(int64_t n, int kmax, int round,
+                                                           const int64_t* forced, int64_t j,
+                                                           int64_t* selected, double* sel_delta,
+                                                           FmiWS w) {
+  const int64_t nch = (n + CR_CH - 1) / CR_CH;
+  double v = -DBL_MAX;
+  long long y = -1;
+  if (forced) {
+    y = min(max(forced[j], (int64_t)0), n - 1);  // validated by the host; never outside
+  } else {
+    for (int64_t e = threadIdx.x; e < nch; e += blockDim.x) {
+      if (w.fidx[e] >= 0 && key_gt(w.fval[e], w.fidx[e], v, y)) {
+        v = w.fval[e];
+        y = w.fidx[e];
+      }
+    }
+    crit_block_keymax(v, y);
+  }
+  if (threadIdx.x == 0) {
+    selected[round] = y;
+    if (sel_delta) sel_delta[round] = y >= 0 ? w.delta[y] : 0.0;
+    if (y >= 0) {
+      w.selmask[y] = 1;
+      w.piv[0] = w.nom[y];
+      w.piv[1] = w.prec[y];
+    }
+  }
+  if (y >= 0)
+    for (int t = threadIdx.x; t < round; t += blockDim.x) {
+      w.piv[2 + t] = w.W[(int64_t)t * n + y];
+      w.piv[2 + kmax + t] = w.V[(int64_t)t * n + y];
+    }
+}
+
+// u_a = C^-1 f_a / d_a: a wave per row of C^-1, lane l the columns l + 64 q in ascending q, then
+// the wave's butterfly.
+__global__ __launch_bounds__(FC_TH) void fmi_u_kernel(const double* __restrict__ F, int64_t S,
+                                                      int64_t ldf,
+                                                      const double* __restrict__ noise,
+                                                      const int64_t* __restrict__ selected,
+                                                      int round, FmiWS w) {
+  const int64_t a = selected[round];
+  if (a < 0) return;
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * (FC_TH / 64) + (threadIdx.x >> 6);
+  if (r >= S) return;  // whole waves
+  const double* fa = F + a * ldf;
+  const double* c = w.Cinv + r * S;
+  double s = 0.0;
+  for (int64_t k = lane; k < S; k += 64) s = fma(c[k], fa[k], s);
+  s = wave_sum(s);
+  if (lane == 0) w.u[r] = s / noise[a];
+}
+
+// factor_row_kernel's stream with two right-hand sides: f_i . f_a and f_i . u_a from one read of
+// the row, f_a staged in LDS and u_a beside it (ULDS) or read through L2 where 2 S doubles are
+// more LDS than a workgroup is given by default.  Then one lane per row: the columns of Sigma and
+// of Q, their downdates, the two new rows and the nom and prec downdates.  w = 0 unless
+// nom_a >= thr and > 0 (crit_row_kernel), v = 0 unless prec_a > 0 (greedy_update_kernel).
+constexpr int64_t FMI_ULDS_SMAX = 2048;  // 2 S doubles = 32 KiB
+
+template <bool VEC, bool ULDS>
+__global__ __launch_bounds__(FC_TH) void fmi_row_kernel(
+    const double* __restrict__ F, int64_t n, int64_t S, int64_t ldf,
+    const double* __restrict__ noise, const double* __restrict__ dg,
+    const int64_t* __restrict__ selected, int kmax, int round, FmiWS w) {
+  extern __shared__ double zs[];  // f_a [S], then u_a [S] (ULDS)
+  const int64_t a = selected[round];
+  if (a < 0) return;  // workgroup-uniform
+  const double* __restrict__ ug = w.u;
+  for (int64_t i = threadIdx.x; i < S; i += FC_TH) {
+    zs[i] = F[a * ldf + i];
+    if (ULDS) zs[S + i] = ug[i];
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t base = (int64_t)blockIdx.x * FC_TH + 64 * wv;
+  if (base >= n) return;
+  double mine = 0.0, mineu = 0.0;
+  for (int k = 0; k < 64 && base + k < n; k += 4) {
+    double s[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0};
+    int64_t row[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) row[u] = min(base + k + u, n - 1);  // clamped: loaded, not kept
+    for (int64_t cq = 0; cq < S; cq += 128) {
+      const int64_t c = cq + 2 * lane;
+      fc_d2 m[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) m[u] = fc_pair<VEC>(F + row[u] * ldf + c, c, S);
+      const fc_d2 zz = {c < S ? zs[c] : 0.0, c + 1 < S ? zs[c + 1] : 0.0};
+      const fc_d2 uu = {c < S ? (ULDS ? zs[S + c] : ug[c]) : 0.0,
+                        c + 1 < S ? (ULDS ? zs[S + c + 1] : ug[c + 1]) : 0.0};
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        s[u] = fma(m[u].x, zz.x, s[u]);
+        s[u] = fma(m[u].y, zz.y, s[u]);
+        q[u] = fma(m[u].x, uu.x, q[u]);
+        q[u] = fma(m[u].y, uu.y, q[u]);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const double vs = wave_sum(s[u]), vq = wave_sum(q[u]);
+      if (lane == k + u) {
+        mine = vs;
+        mineu = vq;
+      }
+    }
+  }
+  const int64_t i = base + lane;
+  if (i >= n) return;
+  double sc = i == a ? dg[a] : mine;
+  double qc = (i == a ? 1.0 / noise[a] : 0.0) - mineu / noise[i];
+  for (int t = 0; t < round; ++t) {
+    sc -= w.piv[2 + t] * w.W[(int64_t)t * n + i];
+    qc -= w.piv[2 + kmax + t] * w.V[(int64_t)t * n + i];
+  }
+  const double noma = w.piv[0], preca = w.piv[1];
+  const double wy = noma >= w.prm[0] && noma > 0.0 ? sc / sqrt(noma) : 0.0;
+  const double vy = preca > 0.0 ? qc / sqrt(preca) : 0.0;
+  w.W[(int64_t)round * n + i] = wy;
+  w.V[(int64_t)round * n + i] = vy;
+  w.nom[i] -= wy * wy;
+  w.prec[i] -= vy * vy;
+}
+
+static void fmi_row_launch(const SFactor& f, int64_t n, const double* dg, const int64_t* selected,
+                           int kmax, int round, const FmiWS& w, hipStream_t s) {
+  const dim3 grid((unsigned)ceil_div(n, FC_TH));
+  const bool ulds = f.S <= FMI_ULDS_SMAX;
+  const size_t lds = (size_t)f.S * 8 * (ulds ? 2 : 1);
+#define FMI_ROW(VEC, ULDS)                                                                      \
+  hipLaunchKernelGGL((fmi_row_kernel<VEC, ULDS>), grid, dim3(FC_TH), lds, s, f.F, n, f.S, f.ldf, \
+                     f.noise, dg, selected, kmax, round, w)
+  if (symv_vec(f.F, f.ldf)) {
+    if (ulds) FMI_ROW(true, true); else FMI_ROW(true, false);
+  } else {
+    if (ulds) FMI_ROW(false, true); else FMI_ROW(false, false);
+  }
+#undef FMI_ROW
+}
+
+// The start: dg, C = I + F^T D^-1 F (factor_symv_sq's moment loop with x = 1 / d), M = L^-1,
+// C^-1 = M^T M, and per chunk T = F_c M^T with its row sums of squares.  info: the
+// factorization's status (device int32).
+static int fmi_init_run(const SFactor& f, int64_t n, int kmax, double threshold,
+                        const unsigned char* allowed, int* info, const FmiWS& w, hipStream_t s) {
+  const int64_t S = f.S;
+  const FacWS fw = fac_layout(w.fac, n, S);
+  const double ns = (double)n * (double)S;
+  ProfScope ps("criteria_fmi_init", s, 4.0 * ns * (double)S, 8.0 * 4.0 * ns);
+  VG_TRY(factor_diag_launch(f, n, fw.dg, s));
+  const unsigned nb = (unsigned)ceil_div(n, 256), sb = (unsigned)ceil_div(S * S, 256);
+  hipLaunchKernelGGL(fmi_recip_kernel, dim3(nb), dim3(256), 0, s, n, f.noise, w.delta);
+  VG_LAUNCH_CHECK();
+  VG_TRY(factor_moment_launch(f, n, w.delta, fw, s));
+  hipLaunchKernelGGL(fmi_square_kernel, dim3(sb), dim3(256), 0, s, S, fw.M, 0);
+  VG_LAUNCH_CHECK();
+  VG_HIP(vg_memset(info, 0, sizeof(int), s));
+  VG_TRY(potrf_one(fw.M, S, S, 1, nullptr, info, w.potrf, s, false, true, w.compact));
+  hipLaunchKernelGGL(fmi_square_kernel, dim3(sb), dim3(256), 0, s, S, fw.M, 1);
+  VG_LAUNCH_CHECK();
+  VG_TRY(gemm_launch(1, 0, S, S, S, 1.0, fw.M, S, fw.M, S, 0.0, w.Cinv, S, VGPOSP_FULL, 0, 0, s));
+  for (int64_t c0 = 0; c0 < n; c0 += fw.rc) {
+    const int64_t rc = std::min(fw.rc, n - c0);
+    VG_TRY(gemm_launch(0, 1, rc, S, S, 1.0, f.F + c0 * f.ldf, f.ldf, fw.M, S, 0.0, fw.tmp, S,
+                       VGPOSP_FULL, 0, 0, s));
+    VG_TRY(vgposp_row_sumsq(fw.tmp, rc, S, S, 1.0, 0.0, w.prec + c0, s));
+  }
+  hipLaunchKernelGGL(fmi_init_kernel, dim3(nb), dim3(256), 0, s, n, fw.dg, f.noise, threshold,
+                     allowed, w);
+  VG_LAUNCH_CHECK();
+  return 0;
+}
+
+static int fmi_step_run(const SFactor& f, int64_t n, int kmax, int round, const int64_t* forced,
+                        int64_t j, int64_t* selected, double* sel_delta, const FmiWS& w,
+                        hipStream_t s) {
+  const double* dg = fac_layout(w.fac, n, f.S).dg;
+  {
+    ProfScope ps("criteria_fmi_select", s, 0.0, 8.0 * 4.0 * n);
+    hipLaunchKernelGGL(fmi_score_kernel, dim3((unsigned)ceil_div(n, CR_CH)), dim3(CR_CH), 0, s, n,
+                       w);
+    hipLaunchKernelGGL(fmi_select_kernel, dim3(1), dim3(CR_CH), 0, s, n, kmax, round, forced, j,
+                       selected, sel_delta, w);
+    VG_LAUNCH_CHECK();
+  }
+  {
+    ProfScope ps("criteria_fmi_u", s, 2.0 * (double)f.S * f.S, 8.0 * (double)f.S * (f.S + 2));
+    hipLaunchKernelGGL(fmi_u_kernel, dim3((unsigned)ceil_div(f.S, FC_TH / 64)), dim3(FC_TH), 0, s,
+                       f.F, f.S, f.ldf, f.noise, selected, round, w);
+    VG_LAUNCH_CHECK();
+  }
+  {
+    const double ns = (double)n * (double)f.S;
+    ProfScope ps("criteria_fmi_row", s, 4.0 * ns, 8.0 * ns + 8.0 * (double)n * (2 * round + 6));
+    fmi_row_launch(f, n, dg, selected, kmax, round, w, s);
+    VG_LAUNCH_CHECK();
+  }
+  return 0;
 }
 
 }  // namespace vgposp
@@ -2172,5 +2492,63 @@ extern "C" int vgposp_critf_buffers(void* ws, int64_t n, int64_t s, int kmax, do
   clear_error();
   VG_TRY(check_buffers(__func__, ws, n, &s, kmax));
   crit_outputs(critf_layout(ws, n, s, kmax), nom, score, delta, W);
+  return 0;
+}
+
+// ---- mutual information on a factor (Woodbury): the full greedy of placement_algorithm2.py:128-145
+// with the deltas of :371-413, on main.py:190-199's covariance ----
+static int check_noise(const char* fn, const SFactor& f) {
+  VG_ARG(f.noise != nullptr, 5);
+  return 0;
+}
+
+extern "C" size_t vgposp_fmi_workspace_bytes(int64_t n, int64_t s, int kmax) {
+  if (n <= 0 || s <= 0 || kmax <= 0) return 0;
+  if (s > FC_SMAX) s = FC_SMAX;  // the entries refuse it; the query stays finite
+  return fmi_layout(nullptr, n, s, kmax).bytes;
+}
+
+extern "C" int vgposp_fmi_init(const double* F, int64_t n, int64_t s, int64_t ldf,
+                               const double* noise, int kmax, double threshold,
+                               const unsigned char* allowed, int* info, void* ws, size_t ws_bytes,
+                               void* stream) {
+  clear_error();
+  const SFactor sg{F, s, ldf, noise};
+  VG_TRY(check_sigma(__func__, 1, sg, n));
+  VG_TRY(check_noise(__func__, sg));
+  VG_TRY(check_rule(__func__, 6, kmax, n, nullptr, threshold));
+  VG_CHECK_ARG(info != nullptr, 9);
+  VG_CHECK_ARG(ws != nullptr, 10);
+  const FmiWS w = fmi_layout(ws, n, s, kmax);
+  VG_CHECK_WS(ws_bytes, w.bytes);
+  return fmi_init_run(sg, n, kmax, threshold, allowed, info, w, as_stream(stream));
+}
+
+extern "C" int vgposp_fmi_step(const double* F, int64_t n, int64_t s, int64_t ldf,
+                               const double* noise, int kmax, int round, const int64_t* forced,
+                               int64_t j, int64_t* selected, double* sel_delta, void* ws,
+                               size_t ws_bytes, void* stream) {
+  clear_error();
+  const SFactor sg{F, s, ldf, noise};
+  VG_TRY(check_sigma(__func__, 1, sg, n));
+  VG_TRY(check_noise(__func__, sg));
+  VG_TRY(check_round(__func__, 6, kmax, n, round, forced, j, selected));
+  VG_CHECK_ARG(ws != nullptr, 12);
+  const FmiWS w = fmi_layout(ws, n, s, kmax);
+  VG_CHECK_WS(ws_bytes, w.bytes);
+  return fmi_step_run(sg, n, kmax, round, forced, j, selected, sel_delta, w, as_stream(stream));
+}
+
+extern "C" int vgposp_fmi_buffers(void* ws, int64_t n, int64_t s, int kmax, double** nom,
+                                  double** prec, double** delta, double** W, double** V) {
+  clear_error();
+  VG_TRY(check_buffers(__func__, ws, n, &s, kmax));
+  VG_CHECK_ARG(s <= FC_SMAX, 3);
+  const FmiWS w = fmi_layout(ws, n, s, kmax);
+  if (nom) *nom = w.nom;
+  if (prec) *prec = w.prec;
+  if (delta) *delta = w.delta;
+  if (W) *W = w.W;
+  if (V) *V = w.V;
   return 0;
 }

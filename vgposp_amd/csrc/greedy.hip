@@ -440,14 +440,6 @@ __global__ __launch_bounds__(CH) void greedy_spec_reduce_kernel(int64_t n, Greed
   w.qc[slot * n + i] = q;
 }
 
-// denom = conditional variance of y given V \ (A u {y}) with eps on that block's diagonal:
-// 1 / [(Sigma_SS + eps I)^-1]_yy - eps (Sherman-Morrison on the y entry of the jitter).
-__device__ __forceinline__ double delta_of(double nom, double prec, double eps, double thr) {
-  const double den = 1.0 / prec - eps;
-  if (fabs(den) < thr || fabs(nom) < thr) return 0.0;  // :198 / snippets_a2.py:440-487
-  return nom / den;
-}
-
 // Round 0: nom = diag(Sigma), prec = Q_ii.  Round t>0: rank-1 updates with a = selected[t-1].
 // spec: a round of vgposp_greedy_step with speculation, whose q comes from the cache on a hit.
 // Then delta for every unselected candidate and per-workgroup best fresh key.

@@ -390,19 +390,28 @@ def placement_from_samples(samples, k, criterion="variance", noise=0.0, tr_stdev
 
     ``cov``: ``"factored"`` (the default) never forms the N x N matrix and runs the rounds on the
     centred samples themselves (placement_criteria.FactoredCovariance.from_samples): N S doubles
-    on the device instead of N^2.  It is for ``"variance"`` and ``"entropy"``.  ``"dense"``
-    assembles ``covariance.empirical_cov(samples) + diag(noise)`` and runs the existing paths,
-    ``"mi"`` included.  ``noise`` is a scalar or [N], ``targets`` belongs to ``"variance"``."""
+    on the device instead of N^2.  ``"variance"`` and ``"entropy"`` take any noise >= 0.  ``"mi"``
+    (placement_criteria.FactoredMIPlacement) inverts Sigma through Woodbury's identity, so it needs
+    noise > 0 at every location (ValueError otherwise, before any device work), and it is the
+    full greedy on fresh deltas: every delta is fresh after the one stream over the samples a
+    round needs anyway, so the lazy cache of ``placement_algorithm_2`` is not emulated.
+    ``"dense"`` assembles ``covariance.empirical_cov(samples) + diag(noise)`` and runs the existing
+    paths; its ``"mi"`` is the lazy ``placement_algorithm_2`` and takes noise = 0 (a singular Sigma
+    is retried with jitter).  ``noise`` is a scalar or [N], ``targets`` belongs to ``"variance"``."""
     if cov not in ("dense", "factored"):
         raise ValueError(f"unknown cov {cov!r}; expected 'dense' or 'factored'")
     if criterion == "mi":
-        if cov == "factored":
-            raise ValueError("cov='factored' applies to criterion='variance' and 'entropy': the "
-                             "mutual-information placement factors the stored Sigma (on a factor "
-                             "it needs a Woodbury form that is not built); use cov='dense'")
         if targets is not None:
             raise ValueError("targets apply to criterion='variance'; the mutual-information "
                              "placement has no target set")
+        if cov == "factored":
+            from .placement_criteria import (FactoredCovariance, placement_mutual_information,
+                                             require_positive_noise)
+            shape = tuple(np.shape(samples))
+            if len(shape) == 2 and shape[0] >= 1:   # (from_samples reports any other shape)
+                require_positive_noise(FactoredCovariance._noise_vector(noise, shape[0]))
+            fac = FactoredCovariance.from_samples(samples, noise=noise, tr_stdev=tr_stdev)
+            return placement_mutual_information(fac, k, candidates=candidates, placed=placed)
     else:
         from .placement_criteria import CRITERIA
         if criterion not in CRITERIA:

@@ -41,6 +41,11 @@ A covariance estimated from samples: a ``FactoredCovariance(F, noise=0.0)`` in t
 reference's empirical covariance of S samples per location (``covariance.empirical_cov``) without
 the N x N matrix.  A pass is two streams over F (``vgposp_factor_symv``), the column of a round one,
 so the device holds N S doubles instead of N^2.
+
+Mutual information on that factor: where its noise is positive at every location,
+``FactoredMIPlacement`` / ``placement_mutual_information`` run the reference's own criterion
+(placement_algorithm2.py:371-413) through Woodbury's identity on an S x S matrix, O(N S) per round
+and one stream over F (``vgposp_fmi_*``), as the full greedy on fresh deltas.
 """
 from __future__ import annotations
 
@@ -211,6 +216,13 @@ class FactoredCovariance:
         """The noise on the device, [N] float64, or None when it is zero everywhere."""
         self._upload()
         return self._noise
+
+    def noise_is_positive(self):
+        """Whether the noise is positive at every location (D = diag(noise) invertible).  Before
+        the first use of F or noise this looks at host data only."""
+        if self._noise is None:
+            return False
+        return bool((self._noise > 0.0).all())
 
     @classmethod
     def from_samples(cls, samples, noise=0.0, tr_stdev=1.0):
@@ -511,6 +523,130 @@ class CriterionPlacement:
         if (sel < 0).any():
             raise RuntimeError("greedy placement found no candidate (all deltas NaN?)")
         return [np.int64(s) for s in sel], self.sel_delta[new].cpu().numpy()
+
+
+def require_positive_noise(fac):
+    """ValueError unless the noise of the ``FactoredCovariance`` (or a host noise vector; None:
+    zero everywhere) is positive at every location: Woodbury needs an invertible D."""
+    ok = (fac.noise_is_positive() if isinstance(fac, FactoredCovariance)
+          else fac is not None and bool((np.asarray(fac) > 0.0).all()))
+    if not ok:
+        raise ValueError("the noise must be positive at every location: the mutual-information "
+                         "placement factors Sigma, and on a factor that is Woodbury's identity, "
+                         "for which D = diag(noise) must be invertible; with noise = 0 anywhere "
+                         "use cov='dense'")
+
+
+class FactoredMIPlacement:
+    """Device-resident greedy mutual-information placement on a ``FactoredCovariance``
+    Sigma = F F^T + diag(noise) whose noise is positive at every location (``vgposp_fmi_*``,
+    csrc/criteria.hip): the reference's criterion (placement_algorithm2.py:371-413) on the
+    reference's covariance (main.py:190-199) without Sigma or its inverse, O(N S) per round.
+
+    Selection is the full greedy (``placement_algorithm_1``, ``GreedyPlacement.step(lazy=False)``):
+    the arg-max over the fresh delta of every free candidate, ties to the lowest index.  The dense
+    path's default is the lazy policy, whose cache exists to save evaluations; here every delta is
+    fresh after the one stream over F a round needs anyway, so the cache is not emulated and there
+    are no ``evals``.  ``candidates`` / ``placed`` as in ``GreedyPlacement``: blocked locations
+    stay in every denominator, ``placed`` runs as forced rounds in ``init()``; ``kmax``,
+    ``rounds`` and ``result()`` count the new picks only.  Jitter is 0."""
+
+    def __init__(self, fac, kmax, candidates=None, placed=None, threshold=1e-8):
+        if not isinstance(fac, FactoredCovariance):
+            raise ValueError("FactoredMIPlacement needs a placement_criteria.FactoredCovariance")
+        self.fac = fac
+        self.N = self.n = fac.N
+        require_positive_noise(fac)                 # before any device work
+        if not (1 <= kmax <= self.N):
+            raise ValueError(f"k must be in [1, {self.N}], got {kmax}")
+        self.allowed, self.placed = normalize_constraints(self.N, kmax, candidates, placed)
+        if not threshold >= 0.0:
+            raise ValueError(f"threshold must not be negative, got {threshold}")
+        self.threshold = float(threshold)
+        self.m = len(self.placed)
+        self.k = int(kmax)
+        self.kmax = self.k + self.m
+        dev = fac.F.device
+        self._allowed_dev = (None if self.allowed is None
+                             else torch.as_tensor(self.allowed.astype(np.uint8), device=dev))
+        self._placed_dev = (torch.as_tensor(self.placed, dtype=torch.int64, device=dev)
+                            if self.m else None)
+        self._sizes = (self.n, fac.S, self.kmax)
+        self.ws = linalg.workspace(query("vgposp_fmi_workspace_bytes", *self._sizes))
+        self.info = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.selected = torch.full((self.kmax,), -1, dtype=torch.int64, device=dev)
+        self.sel_delta = torch.zeros(self.kmax, dtype=torch.float64, device=dev)
+        self.rounds = 0
+
+    def _step(self, r, forced=None, j=0):
+        call("vgposp_fmi_step", *self.fac.args(), self.kmax, r, _p(forced), j, _p(self.selected),
+             _p(self.sel_delta), _p(self.ws), self.ws.numel(), _stream())
+
+    def init(self):
+        call("vgposp_fmi_init", *self.fac.args(), self.kmax, self.threshold,
+             _p(self._allowed_dev), _p(self.info), _p(self.ws), self.ws.numel(), _stream())
+        for j in range(self.m):
+            self._step(j, self._placed_dev, j)
+        self.rounds = 0
+        return self
+
+    def check(self):
+        """Synchronise on the status of the S x S factorization; raise CholeskyError if C was not
+        positive definite (it is whenever the noise is positive and F is finite)."""
+        linalg.check_info(self.info)
+
+    def step(self):
+        if self.rounds >= self.k:
+            raise RuntimeError("all k sensors already placed")
+        self._step(self.m + self.rounds)
+        self.rounds += 1
+
+    def run(self, k=None):
+        k = self.k if k is None else k
+        self.init()
+        for _ in range(k):
+            self.step()
+        return self
+
+    def state(self):
+        """Device views into the workspace: ``nom`` [N] and ``prec`` [N] (conditioned on every
+        pick so far), ``delta`` [N] (as scored by the last round, before its pick), ``W`` and
+        ``V`` [placed + rounds, N]."""
+        ptr = [ctypes.c_void_p() for _ in range(5)]
+        call("vgposp_fmi_buffers", _p(self.ws), *self._sizes, *map(ctypes.byref, ptr))
+
+        def view(p, count):
+            off = p.value - self.ws.data_ptr()
+            return self.ws[off:off + 8 * count].view(torch.float64)
+        rows = self.m + self.rounds
+        st = {name: view(p, self.N) for name, p in zip(("nom", "prec", "delta"), ptr)}
+        st["W"] = view(ptr[3], rows * self.N).view(rows, self.N)
+        st["V"] = view(ptr[4], rows * self.N).view(rows, self.N)
+        return st
+
+    def result(self):
+        """``(picks, deltas)``: the new picks (host list of np.int64; ``placed`` is not part of
+        them) and the delta each had when it was picked.  Raises CholeskyError from ``info``."""
+        self.check()
+        new = slice(self.m, self.m + self.rounds)
+        sel = self.selected[new].cpu().numpy()
+        if (sel < 0).any():
+            raise RuntimeError("greedy placement found no candidate (all deltas NaN?)")
+        return [np.int64(s) for s in sel], self.sel_delta[new].cpu().numpy()
+
+
+def placement_mutual_information(fac, k, candidates=None, placed=None):
+    """k sensors by greedy mutual information on a ``FactoredCovariance`` whose noise is positive
+    everywhere (``FactoredMIPlacement``: the full greedy on fresh deltas, where the dense
+    ``placement_algorithm_2`` is lazy).  Returns a list of ``np.int64``."""
+    if not isinstance(fac, FactoredCovariance):
+        raise ValueError("placement_mutual_information needs a placement_criteria."
+                         "FactoredCovariance")
+    if k < 1:
+        require_positive_noise(fac)
+        normalize_constraints(fac.N, max(int(k), 0), candidates, placed)
+        return []
+    return FactoredMIPlacement(fac, k, candidates=candidates, placed=placed).run(k).result()[0]
 
 
 def _place(cov_vv, k, criterion, candidates, placed, targets, cross_cov=None,
