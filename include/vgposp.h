@@ -988,6 +988,53 @@ int vgposp_fmi_buffers(void* ws, int64_t n, int64_t s, int kmax, double** nom, d
                        double** delta, double** W, double** V);
 
 /* ---------------------------------------------------------------------------------------------
+ * Field reconstruction from k placed sensors on a factored covariance Sigma = F F^T + D: the
+ * posterior mean at all n sites from the sensors' readings and the variance that is left, on the
+ * reference's own covariance (main.py:190-199) without Sigma, Sigma_VA or any n x k array.
+ * A = `sensors` (k distinct sites, pos(a) the position of a in it), sigma2 = obs_noise >= 0 a scalar
+ * measurement-error variance on the sensors' own covariance only, dg_i = f_i . f_i + d_i:
+ *   G = F_A F_A^T + diag(d_A + sigma2) = L L^T   (k x k),   M = L^-1
+ *   c_i = F_A f_i + [i in A] d_i e_pos(i)
+ *   var_i = dg_i - |M c_i|^2,   mean_i,b = mu_i + c_i . alpha_b,   alpha = G^-1 (Y - mu_A)
+ * With W = M F_A (k x s) and Z = F_A^T alpha (s x nrhs) a site outside A needs the row
+ * f_i . [W^T | Z] alone; the k sensor rows take the term in d_a from a second, small launch.
+ *   vgposp_fpost_init   (main.py:190-199 conditioned on the picks of placement_algorithm2.py:
+ *                     128-145) dg, the gathered F_A and d_A, G through vgposp_gemm's kernels,
+ *                     M by vgposp_potrf_lower's recursion (invert = 1), W^T.  info (device int32):
+ *                     the factorization's status; > 0 when G is not positive definite (noise NULL,
+ *                     sigma2 = 0 and F_A rank-deficient).  It is kept in ws: after a non-zero
+ *                     status every launch of vgposp_fpost_apply that writes var or out is a
+ *                     no-op.  Bytes: 8 n s (dg) + O(k s).
+ *   vgposp_fpost_apply  (main.py:190-199, the prediction the reference stops short of) var [n]
+ *                     (or NULL: not computed), and with Y [k][ldy] (or NULL) the nrhs columns of
+ *                     readings: out [n][ldo] = the posterior means; mu [n] the prior mean (NULL:
+ *                     zeros).  alpha = M^T (M (Y - mu_A)) and Z through vgposp_gemm's kernels, then
+ *                     one stream over F per panel of 64 columns of [W^T | Z] (k and nrhs each
+ *                     padded to a multiple of 16; only the columns asked for) on the fp64 matrix
+ *                     cores, reduced per row as it leaves the accumulators, then the k sensor rows.
+ *                     Byte model: 8 n s per panel + 8 n (1 + nrhs).  Any number of calls after
+ *                     one init; F, noise, n, s, ldf, k as given to init.  That is NOT checked:
+ *                     the status word and the layout live in ws, so an apply on a workspace no
+ *                     init has run on, or with another n, s or k, reads an undefined status and
+ *                     undefined factors.  No float atomics, two runs are bit-identical, no host
+ *                     synchronisation.
+ *   vgposp_fpost_workspace_bytes(n, s, k, nrhs_max)  (main.py:190-199) n + 2 k s + k^2 +
+ *                     (3 k + s) nrhs_max doubles with k and nrhs_max padded to 16, and the k x k
+ *                     factorization's workspace; 0 when n <= 0, s <= 0 or k <= 0.  apply needs
+ *                     the bytes of its own nrhs only.
+ * Limits: 1 <= s <= 4,096, n <= 2^22, ldf >= s, 1 <= k <= min(n, 1,024), 0 <= nrhs <= 1,024,
+ * ldy >= nrhs, ldo >= nrhs; noise may be NULL.  Argument errors return -(position) before any
+ * device work, a short workspace VGPOSP_E_WS. */
+size_t vgposp_fpost_workspace_bytes(int64_t n, int64_t s, int k, int nrhs_max);
+int vgposp_fpost_init(const double* F, int64_t n, int64_t s, int64_t ldf, const double* noise,
+                      const int64_t* sensors, int k, double obs_noise, int* info, void* ws,
+                      size_t ws_bytes, void* stream);
+int vgposp_fpost_apply(const double* F, int64_t n, int64_t s, int64_t ldf, const double* noise,
+                       int k, double* var, const double* Y, int64_t ldy, int nrhs,
+                       const double* mu, double* out, int64_t ldo, void* ws, size_t ws_bytes,
+                       void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Exact algorithm 3 at grid sizes where cov_vv cannot be dense (config C4, 128^3): the beta-decay
  * tapered covariance (main_architecture_2_sampledistribution.py:355-421) is a sparse SPD stencil
  * matrix, and snippets_a3.sparse_placement_algorithm_3 (snippets_a3.py:43-364) with tf_nominator /

@@ -341,6 +341,11 @@ SIGNATURES = {
                                        _c_void_p, _size, _c_void_p]),
     "vgposp_fmi_buffers": (_i32, [_c_void_p, _i64, _i64, _i32]
                            + [ctypes.POINTER(_c_void_p)] * 5),
+    "vgposp_fpost_workspace_bytes": (_size, [_i64, _i64, _i32, _i32]),
+    "vgposp_fpost_init": (_i32, _SFAC + [_c_void_p, _i32, _f64, _c_void_p, _c_void_p, _size,
+                                         _c_void_p]),
+    "vgposp_fpost_apply": (_i32, _SFAC + [_i32, _c_void_p, _c_void_p, _i64, _i32, _c_void_p,
+                                          _c_void_p, _i64, _c_void_p, _size, _c_void_p]),
 }
 
 _lock = threading.Lock()
@@ -410,6 +415,9 @@ KERNEL_SOURCES = {
     "criteria_fsymv": ["criteria.hip", "common.h", "Makefile"],
     "criteria_fsymv_sq": ["criteria.hip", "common.h", "Makefile"],
     "criteria_fmi_row": ["criteria.hip", "common.h", "Makefile"],
+    "criteria_fpost_init": ["criteria.hip", "gemm.hip", "potrf.hip", "common.h", "Makefile"],
+    "criteria_fpost_rhs": ["criteria.hip", "gemm.hip", "common.h", "Makefile"],
+    "criteria_fpost_stream": ["criteria.hip", "common.h", "Makefile"],
     "criteria_gemv_t": ["criteria.hip", "common.h", "Makefile"],
     "criteria_gemv_t_sq": ["criteria.hip", "common.h", "Makefile"],
     "criteria_kgemv_t": ["criteria.hip", "psd.h", "common.h", "Makefile"],

@@ -2038,6 +2038,367 @@ static int fmi_step_run(const SFactor& f, int64_t n, int kmax, int round, const 
   return 0;
 }
 
+// ---- field reconstruction from placed sensors on a factor: the posterior mean and variance ----
+// A: k distinct sensors, sigma2 = obs_noise on the sensors' own covariance only:
+//   G = F_A F_A^T + diag(d_A + sigma2) = L L^T,  M = L^-1,  c_i = F_A f_i + [i in A] d_i e_pos(i)
+//   var_i = dg_i - |M c_i|^2,   mean_i,b = mu_i + c_i . alpha_b,   alpha = G^-1 (Y - mu_A)
+// With W = M F_A (k x S) and Z = F_A^T alpha (S x B) a site outside A needs the row
+// f_i . [W^T | Z] alone: var_i = dg_i - the sum of squares of its first k numbers, mean_i,b = mu_i +
+// number k + b.  P = [W^T | Z] is kept as its two column blocks, Wt [S][kp] (written once by
+// init) and Z [S][bp] (written by every apply, bp from that call's nrhs), kp and bp the next
+// multiples of 16 with zero columns between: a zero column adds nothing to a sum of squares.
+// fpost_stream_kernel is the tall-skinny product F . P on the fp64 matrix cores whose n x (k + B)
+// result is never stored; fpost_sensor_kernel rewrites the k sensor rows with the term in d_a.
+constexpr int FP_KMAX = 1024;  // sensors
+constexpr int FP_BMAX = 1024;  // right-hand sides of one apply
+constexpr int FP_KT = 32;      // columns of F, rows of P, per K-tile
+constexpr int FP_LDP = 72;     // pitch of a staged row of P (doubles): rows 2 g and 2 g + 1 of the
+                               // four lane groups g fall into disjoint banks
+constexpr int FP_ROWS = 128;   // rows of F per workgroup: four waves of two 16-row blocks
+constexpr int FP_NF = 4;       // 16-column fragments of a panel
+
+// What the small kernels read of the workspace, and the rest of its layout for the host.
+struct FpostDev {
+  double *dA, *FA, *M, *Wt, *R, *alpha, *Z;
+  int64_t* sens;
+  int* status;  // the factorization's status, kept for every apply
+  int kp, bp;   // k and nrhs padded to whole 16-column fragments
+};
+struct FpostWS : FpostDev {
+  double *dg, *T;
+  void* potrf;
+  bool compact;
+  size_t bytes;
+};
+
+static FpostWS fpost_layout(void* base, int64_t n, int64_t S, int k, int nrhs) {
+  FpostWS w{};
+  w.kp = (int)ceil_div(k, 16) * 16;
+  w.bp = (int)ceil_div(nrhs, 16) * 16;
+  char* p = static_cast<char*>(base);
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char* r = p ? p + off : nullptr;
+    off += cr_align(bytes);
+    return r;
+  };
+  w.dg = (double*)take((size_t)n * 8);
+  w.sens = (int64_t*)take((size_t)k * 8);
+  w.status = (int*)take(sizeof(int));
+  w.dA = (double*)take((size_t)k * 8);
+  w.FA = (double*)take((size_t)k * S * 8);
+  w.M = (double*)take((size_t)k * k * 8);
+  w.compact = potrf_ws_bytes_compact(k) < potrf_ws_bytes(k);
+  w.potrf = take(potrf_ws_bytes_compact(k));
+  w.Wt = (double*)take((size_t)S * w.kp * 8);
+  w.R = (double*)take((size_t)k * w.bp * 8);
+  w.T = (double*)take((size_t)k * w.bp * 8);
+  w.alpha = (double*)take((size_t)k * w.bp * 8);
+  w.Z = (double*)take((size_t)S * w.bp * 8);
+  w.bytes = off;
+  return w;
+}
+
+typedef double fp_d4 __attribute__((ext_vector_type(4)));
+
+// One pass over F for a panel of NF 16-column fragments of P: the first nvf from Wt (variance),
+// the rest from Z (mean).  A wave owns 32 rows as two 16-row blocks and accumulates 32 x 16 NF
+// outputs.  Lane l (fr = l & 15, fk = l >> 4) loads the column pairs 8 q + 2 fk (q < 4) of row fr
+// of each block straight from global memory, 16 bytes where VEC; a pair feeds two MFMAs, whose K
+// index is then the even (odd) columns 8 q + 2 g (+ 1) over the lane groups g, and the B fragments
+// follow that permutation: P[8 q + 2 fk (+ 1)][16 j + fr] from the K-tile of P staged in LDS, two
+// buffers, one barrier a tile; the next tile of both operands is in registers while one is
+// multiplied.  Rows past n are clamped for loading and dropped for storing; columns past S read
+// zeros on both sides, and the last column of an odd S is never read as a pair (fc_pair).
+// The epilogue runs from the accumulators (C/D map: col = fr, row = fk + 4 reg): the 16 lanes of a
+// group hold the 16 columns of a row, so the squares of the variance fragments are summed in the
+// lane over ascending j and across the group by the xor butterfly 8, 4, 2, 1, and
+// var_i = (first ? dg_i : var_i) - that sum; a mean fragment is written to out[i][b0 + ...], 16
+// consecutive lanes 128 contiguous bytes.  No atomics; gate != 0 (the factorization's status)
+// makes the launch a workgroup-uniform no-op before any barrier.
+template <bool VEC, int NF>
+__global__ __launch_bounds__(FC_TH) void fpost_stream_kernel(
+    const double* __restrict__ F, int64_t n, int64_t S, int64_t ldf,
+    const double* __restrict__ Pv, int64_t ldv, int nvf, const double* __restrict__ Pz,
+    int64_t ldz, int first, const double* __restrict__ dg, double* __restrict__ var,
+    const double* __restrict__ mu, double* __restrict__ out, int64_t ldo, int b0, int nrhs,
+    const int* __restrict__ gate) {
+  __shared__ double ps[2][FP_KT * FP_LDP];
+  if (gate && *gate != 0) return;
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int fr = lane & 15, fk = lane >> 4;
+  const int64_t base = (int64_t)blockIdx.x * FP_ROWS + 32 * wv;
+  const double* frow[2];
+#pragma unroll
+  for (int rb = 0; rb < 2; ++rb) frow[rb] = F + min(base + 16 * rb + fr, n - 1) * ldf;
+
+  // this thread's NF pairs of a K-tile of P: pair e = tid + 256 u is row e / (8 NF), pair e % (8 NF)
+  constexpr int PR = 8 * NF;
+  const double* psrc[NF];
+  int prow[NF], pdst[NF];
+  int64_t pld[NF];
+#pragma unroll
+  for (int u = 0; u < NF; ++u) {
+    const int e = threadIdx.x + FC_TH * u, row = e / PR, pc = e % PR, j = pc >> 3;
+    prow[u] = row;
+    pdst[u] = row * FP_LDP + 2 * pc;
+    pld[u] = j < nvf ? ldv : ldz;
+    psrc[u] = (j < nvf ? Pv + 16 * j : Pz + 16 * (j - nvf)) + 2 * (pc & 7) + row * pld[u];
+  }
+
+  fp_d4 acc[2][NF];
+#pragma unroll
+  for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+    for (int j = 0; j < NF; ++j) acc[rb][j] = fp_d4{0.0, 0.0, 0.0, 0.0};
+
+  fc_d2 a[2][4], an[2][4], pp[NF];
+  auto load_a = [&](int64_t k0, fc_d2 (&dst)[2][4]) {
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int64_t c = k0 + 8 * q + 2 * fk;
+        dst[rb][q] = fc_pair<VEC>(frow[rb] + c, c, S);
+      }
+  };
+  auto load_p = [&](int64_t k0) {
+#pragma unroll
+    for (int u = 0; u < NF; ++u)
+      pp[u] = k0 + prow[u] < S ? *reinterpret_cast<const fc_d2*>(psrc[u] + k0 * pld[u])
+                               : fc_d2{0.0, 0.0};
+  };
+  auto store_p = [&](int buf) {
+#pragma unroll
+    for (int u = 0; u < NF; ++u) *reinterpret_cast<fc_d2*>(&ps[buf][pdst[u]]) = pp[u];
+  };
+
+  load_a(0, a);
+  load_p(0);
+  store_p(0);
+  __syncthreads();
+  int buf = 0;
+  for (int64_t k0 = 0; k0 < S; k0 += FP_KT) {
+    const bool more = k0 + FP_KT < S;  // workgroup-uniform
+    if (more) {
+      load_a(k0 + FP_KT, an);
+      load_p(k0 + FP_KT);
+    }
+    const double* pb = ps[buf] + 2 * fk * FP_LDP + fr;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      double be[NF], bo[NF];
+#pragma unroll
+      for (int j = 0; j < NF; ++j) {
+        be[j] = pb[8 * q * FP_LDP + 16 * j];
+        bo[j] = pb[(8 * q + 1) * FP_LDP + 16 * j];
+      }
+#pragma unroll
+      for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int j = 0; j < NF; ++j) {
+          acc[rb][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[rb][q].x, be[j], acc[rb][j], 0, 0, 0);
+          acc[rb][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[rb][q].y, bo[j], acc[rb][j], 0, 0, 0);
+        }
+    }
+    if (more) {
+      store_p(buf ^ 1);
+#pragma unroll
+      for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) a[rb][q] = an[rb][q];
+    }
+    __syncthreads();
+    buf ^= 1;
+  }
+
+  const auto add = [](double x, double y) { return x + y; };
+  if (nvf > 0) {
+    double keep = 0.0;
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        double ss = 0.0;
+#pragma unroll
+        for (int j = 0; j < NF; ++j)
+          if (j < nvf) ss = fma(acc[rb][j][r], acc[rb][j][r], ss);
+        ss = wave_step<8>(ss, add);
+        ss = wave_step<4>(ss, add);
+        ss = wave_step<2>(ss, add);
+        ss = wave_step<1>(ss, add);
+        if (fr == 4 * rb + r) keep = ss;
+      }
+    const int64_t row = base + 16 * (fr >> 2) + fk + 4 * (fr & 3);
+    if (fr < 8 && row < n) var[row] = (first ? dg[row] : var[row]) - keep;
+  }
+#pragma unroll
+  for (int j = 0; j < NF; ++j) {
+    const int b = b0 + 16 * (j - nvf) + fr;
+    if (j >= nvf && b < nrhs) {
+#pragma unroll
+      for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int64_t row = base + 16 * rb + fk + 4 * r;
+          if (row < n) out[row * ldo + b] = (mu ? mu[row] : 0.0) + acc[rb][j][r];
+        }
+    }
+  }
+}
+
+// One workgroup per sensor a = sens[p]: its row of var and of the mean with the term the stream
+// leaves out, t_a = W f_a + d_a M[:, p] and mean_a,b = mu_a + f_a . Z[:, b] + d_a alpha[p][b].
+// Thread j sums over S in ascending order; the squares are added over the threads in a fixed order.
+__global__ __launch_bounds__(CR_B) void fpost_sensor_kernel(
+    const double* __restrict__ F, int64_t S, int64_t ldf, const double* __restrict__ noise, int k,
+    FpostDev w, const double* __restrict__ dg, double* __restrict__ var,
+    const double* __restrict__ mu, double* __restrict__ out, int64_t ldo, int nrhs,
+    const int* __restrict__ gate) {
+  if (gate && *gate != 0) return;
+  const int p = blockIdx.x;
+  const int64_t a = w.sens[p];
+  const double* __restrict__ fa = F + a * ldf;
+  const double d = noise ? noise[a] : 0.0;
+  if (var) {
+    double ss = 0.0;
+    for (int j = threadIdx.x; j < k; j += CR_B) {
+      double t = 0.0;
+      for (int64_t s = 0; s < S; ++s) t = fma(w.Wt[s * w.kp + j], fa[s], t);
+      t = fma(d, w.M[(int64_t)j * k + p], t);
+      ss = fma(t, t, ss);
+    }
+    ss = crit_block_sum(ss);
+    if (threadIdx.x == 0) var[a] = dg[a] - ss;
+  }
+  if (out) {
+    for (int b = threadIdx.x; b < nrhs; b += CR_B) {
+      double t = 0.0;
+      for (int64_t s = 0; s < S; ++s) t = fma(w.Z[s * w.bp + b], fa[s], t);
+      out[a * ldo + b] = ((mu ? mu[a] : 0.0) + t) + d * w.alpha[(int64_t)p * w.bp + b];
+    }
+  }
+}
+
+// F_A [k][S], d_A + sigma2, and the sensors kept for every apply
+__global__ __launch_bounds__(CR_B) void fpost_gather_kernel(const double* __restrict__ F, int64_t S,
+                                                            int64_t ldf,
+                                                            const double* __restrict__ noise,
+                                                            const int64_t* __restrict__ sensors,
+                                                            double sigma2, FpostDev w) {
+  const int p = blockIdx.x;
+  const int64_t a = sensors[p];
+  for (int64_t s = threadIdx.x; s < S; s += CR_B) w.FA[p * S + s] = F[a * ldf + s];
+  if (threadIdx.x == 0) {
+    w.sens[p] = a;
+    w.dA[p] = (noise ? noise[a] : 0.0) + sigma2;
+  }
+}
+
+// before the factorization: G += diag(d_A + sigma2); after it: zeros above the diagonal of M, and
+// the status where apply finds it
+__global__ void fpost_square_kernel(int k, FpostDev w, int after, const int* __restrict__ info) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (after && e == 0) *w.status = *info;
+  if (e >= (int64_t)k * k) return;
+  const int64_t i = e / k, j = e - i * k;
+  if (!after && i == j) w.M[e] += w.dA[i];
+  if (after && j > i) w.M[e] = 0.0;
+}
+
+// R [k][bp] = Y - mu_A, zero in the columns past nrhs (so are T, alpha and Z then)
+__global__ void fpost_rhs_kernel(int k, int nrhs, const double* __restrict__ Y, int64_t ldy,
+                                 const double* __restrict__ mu, FpostDev w) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (int64_t)k * w.bp) return;
+  const int64_t p = e / w.bp, b = e - p * w.bp;
+  w.R[e] = b < nrhs ? Y[p * ldy + b] - (mu ? mu[w.sens[p]] : 0.0) : 0.0;
+}
+
+static int fpost_init_run(const SFactor& f, int64_t n, const int64_t* sensors, int k,
+                          double sigma2, int* info, const FpostWS& w, hipStream_t s) {
+  const int64_t S = f.S;
+  ProfScope ps("criteria_fpost_init", s, 2.0 * (double)k * k * (S + S + k / 3.0),
+               8.0 * ((double)n * S + 3.0 * k * S));
+  VG_TRY(factor_diag_launch(f, n, w.dg, s));
+  hipLaunchKernelGGL(fpost_gather_kernel, dim3((unsigned)k), dim3(CR_B), 0, s, f.F, S, f.ldf,
+                     f.noise, sensors, sigma2, w);
+  VG_LAUNCH_CHECK();
+  VG_TRY(gemm_launch(0, 1, k, k, S, 1.0, w.FA, S, w.FA, S, 0.0, w.M, k, VGPOSP_FULL, 0, 0, s));
+  const unsigned kb = (unsigned)ceil_div((int64_t)k * k, 256);
+  hipLaunchKernelGGL(fpost_square_kernel, dim3(kb), dim3(256), 0, s, k, w, 0, info);
+  VG_LAUNCH_CHECK();
+  VG_HIP(vg_memset(info, 0, sizeof(int), s));
+  VG_TRY(potrf_one(w.M, k, k, 1, nullptr, info, w.potrf, s, false, true, w.compact));
+  hipLaunchKernelGGL(fpost_square_kernel, dim3(kb), dim3(256), 0, s, k, w, 1, info);
+  VG_LAUNCH_CHECK();
+  // Wt = (M F_A)^T = F_A^T M^T, the columns k .. kp zero
+  VG_HIP(vg_memset(w.Wt, 0, (size_t)S * w.kp * 8, s));
+  VG_TRY(gemm_launch(1, 1, S, k, k, 1.0, w.FA, S, w.M, k, 0.0, w.Wt, w.kp, VGPOSP_FULL, 0, 0, s));
+  return 0;
+}
+
+static void fpost_stream_launch(const SFactor& f, int64_t n, int nf, const double* Pv, int64_t ldv,
+                                int nvf, const double* Pz, int64_t ldz, int first,
+                                const double* dg, double* var, const double* mu, double* out,
+                                int64_t ldo, int b0, int nrhs, const int* gate, hipStream_t s) {
+  const dim3 grid((unsigned)ceil_div(n, FP_ROWS));
+  const bool vec = symv_vec(f.F, f.ldf);
+#define FP_STREAM(VEC, NF)                                                                      \
+  hipLaunchKernelGGL((fpost_stream_kernel<VEC, NF>), grid, dim3(FC_TH), 0, s, f.F, n, f.S,      \
+                     f.ldf, Pv, ldv, nvf, Pz, ldz, first, dg, var, mu, out, ldo, b0, nrhs, gate)
+#define FP_STREAM_NF(NF) \
+  if (vec) FP_STREAM(true, NF); else FP_STREAM(false, NF)
+  switch (nf) {
+    case 1: FP_STREAM_NF(1); break;
+    case 2: FP_STREAM_NF(2); break;
+    case 3: FP_STREAM_NF(3); break;
+    default: FP_STREAM_NF(4); break;
+  }
+#undef FP_STREAM_NF
+#undef FP_STREAM
+}
+
+static int fpost_apply_run(const SFactor& f, int64_t n, int k, double* var, const double* Y,
+                           int64_t ldy, int nrhs, const double* mu, double* out, int64_t ldo,
+                           const FpostWS& w, hipStream_t s) {
+  const int64_t S = f.S;
+  const int* info = w.status;
+  const bool mean = Y != nullptr && nrhs > 0;
+  if (mean) {
+    ProfScope ps("criteria_fpost_rhs", s, 2.0 * w.bp * k * (2.0 * k + S),
+                 8.0 * ((double)k * k + (double)k * S + 2.0 * S * w.bp));
+    hipLaunchKernelGGL(fpost_rhs_kernel, dim3((unsigned)ceil_div((int64_t)k * w.bp, 256)),
+                       dim3(256), 0, s, k, nrhs, Y, ldy, mu, w);
+    VG_LAUNCH_CHECK();
+    VG_TRY(gemm_launch(0, 0, k, w.bp, k, 1.0, w.M, k, w.R, w.bp, 0.0, w.T, w.bp, VGPOSP_FULL, 0, 0,
+                       s));
+    VG_TRY(gemm_launch(1, 0, k, w.bp, k, 1.0, w.M, k, w.T, w.bp, 0.0, w.alpha, w.bp, VGPOSP_FULL,
+                       0, 0, s));
+    VG_TRY(gemm_launch(1, 0, S, w.bp, k, 1.0, w.FA, S, w.alpha, w.bp, 0.0, w.Z, w.bp, VGPOSP_FULL,
+                       0, 0, s));
+  }
+  // the fragments asked for: the variance's first, then the mean's, four to a panel
+  const int nv = var ? w.kp / 16 : 0, nm = mean ? w.bp / 16 : 0;
+  for (int f0 = 0; f0 < nv + nm; f0 += FP_NF) {
+    const int nf = std::min(FP_NF, nv + nm - f0);
+    const int nvf = std::max(0, std::min(nv - f0, nf)), m0 = std::max(0, f0 - nv);
+    const double ns = (double)n * (double)S;
+    ProfScope ps("criteria_fpost_stream", s, 2.0 * ns * 16.0 * nf,
+                 8.0 * ns + 8.0 * (double)n * ((nvf ? 1 : 0) + std::min(16 * (nf - nvf), nrhs)));
+    fpost_stream_launch(f, n, nf, w.Wt + 16 * f0, w.kp, nvf, w.Z + 16 * m0, w.bp, f0 == 0, w.dg,
+                        var, mu, out, ldo, 16 * m0, nrhs, info, s);
+    VG_LAUNCH_CHECK();
+  }
+  if (var || mean) {
+    hipLaunchKernelGGL(fpost_sensor_kernel, dim3((unsigned)k), dim3(CR_B), 0, s, f.F, S, f.ldf,
+                       f.noise, k, w, w.dg, var, mu, mean ? out : nullptr, ldo, nrhs, info);
+    VG_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
 }  // namespace vgposp
 
 using namespace vgposp;
@@ -2551,4 +2912,54 @@ extern "C" int vgposp_fmi_buffers(void* ws, int64_t n, int64_t s, int kmax, doub
   if (W) *W = w.W;
   if (V) *V = w.V;
   return 0;
+}
+
+// ---- field reconstruction on a factor: main.py:190-199's covariance, conditioned on the picks ----
+// (F, n, s, ldf, noise) at 1, k at `at`
+static int check_fpost(const char* fn, const SFactor& f, int64_t n, int k, int at) {
+  VG_TRY(check_sigma(fn, 1, f, n, FC_NMAX));
+  VG_ARG(k >= 1 && k <= FP_KMAX && k <= n, at);
+  return 0;
+}
+
+extern "C" size_t vgposp_fpost_workspace_bytes(int64_t n, int64_t s, int k, int nrhs_max) {
+  if (n <= 0 || s <= 0 || k <= 0) return 0;
+  if (s > FC_SMAX) s = FC_SMAX;  // the entries refuse these; the query stays finite
+  if (k > FP_KMAX) k = FP_KMAX;
+  nrhs_max = std::max(0, std::min(nrhs_max, FP_BMAX));
+  return fpost_layout(nullptr, n, s, k, nrhs_max).bytes;
+}
+
+extern "C" int vgposp_fpost_init(const double* F, int64_t n, int64_t s, int64_t ldf,
+                                 const double* noise, const int64_t* sensors, int k,
+                                 double obs_noise, int* info, void* ws, size_t ws_bytes,
+                                 void* stream) {
+  clear_error();
+  const SFactor sg{F, s, ldf, noise};
+  VG_TRY(check_fpost(__func__, sg, n, k, 7));
+  VG_CHECK_ARG(sensors != nullptr, 6);
+  VG_CHECK_ARG(obs_noise >= 0.0 && obs_noise <= DBL_MAX, 8);
+  VG_CHECK_ARG(info != nullptr, 9);
+  VG_CHECK_ARG(ws != nullptr, 10);
+  const FpostWS w = fpost_layout(ws, n, s, k, 0);
+  VG_CHECK_WS(ws_bytes, w.bytes);
+  return fpost_init_run(sg, n, sensors, k, obs_noise, info, w, as_stream(stream));
+}
+
+extern "C" int vgposp_fpost_apply(const double* F, int64_t n, int64_t s, int64_t ldf,
+                                  const double* noise, int k, double* var, const double* Y,
+                                  int64_t ldy, int nrhs, const double* mu, double* out,
+                                  int64_t ldo, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  const SFactor sg{F, s, ldf, noise};
+  VG_TRY(check_fpost(__func__, sg, n, k, 6));
+  VG_CHECK_ARG(Y == nullptr || nrhs <= 0 || ldy >= nrhs, 9);
+  VG_CHECK_ARG(nrhs >= 0 && nrhs <= FP_BMAX, 10);
+  if (Y == nullptr) nrhs = 0;
+  VG_CHECK_ARG(nrhs == 0 || out != nullptr, 12);
+  VG_CHECK_ARG(nrhs == 0 || ldo >= nrhs, 13);
+  VG_CHECK_ARG(ws != nullptr, 14);
+  const FpostWS w = fpost_layout(ws, n, s, k, nrhs);
+  VG_CHECK_WS(ws_bytes, w.bytes);
+  return fpost_apply_run(sg, n, k, var, Y, ldy, nrhs, mu, out, ldo, w, as_stream(stream));
 }

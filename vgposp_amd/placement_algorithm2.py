@@ -440,3 +440,14 @@ def placement_from_samples(samples, k, criterion="variance", noise=0.0, tr_stdev
     g = CriterionPlacement(Sigma, k, criterion, candidates=candidates, placed=placed,
                            targets=targets).run(k)
     return g.result()[0]
+
+
+def reconstruct_from_samples(samples, sensors, readings, noise=0.0, obs_noise=0.0, tr_stdev=1.0):
+    """What follows ``placement_from_samples``: ``(mean, variance)`` of the field at all N
+    locations given ``readings`` [k] or [k, B] at ``sensors``, under the same covariance (the
+    empirical covariance of ``samples`` plus diag(``noise``), main.py:190-199) with the samples'
+    mean per location as the prior mean, never forming an N x N or N x k array
+    (placement_criteria.FieldReconstruction).  ``obs_noise`` >= 0 is a scalar measurement-error
+    variance on the sensors' own covariance."""
+    from .placement_criteria import reconstruct_from_samples as run
+    return run(samples, sensors, readings, noise=noise, obs_noise=obs_noise, tr_stdev=tr_stdev)

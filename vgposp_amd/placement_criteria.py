@@ -687,3 +687,141 @@ def placement_entropy(cov_vv, k, candidates=None, placed=None):
     """k sensors by the entropy rule: each pick has the largest conditional variance given the
     sensors so far (the pivots of a diagonal-pivoted Cholesky of ``cov_vv``)."""
     return _place(cov_vv, k, "entropy", candidates, placed, None)
+
+
+class FieldReconstruction:
+    """What the sensors say about the whole field, on a ``FactoredCovariance``
+    Sigma = F F^T + diag(noise) (``vgposp_fpost_*``, csrc/criteria.hip): the posterior mean at all
+    N sites from the readings at ``sensors`` and the variance that is left, without Sigma, Sigma_VA
+    or any N x k array.  ``obs_noise`` >= 0 is a scalar measurement-error variance added to the
+    sensors' own covariance only.  With A = ``sensors`` and G = Sigma_AA + obs_noise I:
+
+        var_i  = Sigma_ii - Sigma_iA G^-1 Sigma_Ai
+        mean_i = mu_i + Sigma_iA G^-1 (y - mu_A)
+
+    One k x k factorization in ``__init__``, then one stream over F per 64 columns of work
+    (k variance columns, one mean column per reading).  Everything is validated on the host before
+    any device work: distinct in-range sensors, 1 <= k <= 1,024, ``obs_noise`` finite and >= 0, and,
+    where both noises are zero, k <= S (G = F_A F_A^T is singular beyond that).  ``info`` is the
+    device status of the factorization; nothing synchronises the host until ``check()``."""
+
+    K_MAX = 1024
+    B_MAX = 1024
+
+    def __init__(self, fac, sensors, obs_noise=0.0, max_readings=64):
+        if not isinstance(fac, FactoredCovariance):
+            raise ValueError("FieldReconstruction needs a placement_criteria.FactoredCovariance")
+        self.fac = fac
+        self.N = self.n = fac.N
+        self.sensors = _index_array("sensors", sensors, self.N)
+        self.k = int(self.sensors.size)
+        if not 1 <= self.k <= self.K_MAX:
+            raise ValueError(f"the number of sensors must be in [1, {self.K_MAX}], got {self.k}")
+        if not (np.ndim(obs_noise) == 0 and np.isfinite(float(obs_noise))
+                and float(obs_noise) >= 0.0):
+            raise ValueError(f"obs_noise must be a finite scalar >= 0, got {obs_noise!r}")
+        self.obs_noise = float(obs_noise)
+        if fac._noise is None and self.obs_noise == 0.0 and self.k > fac.S:
+            raise ValueError(f"{self.k} sensors on a factor of {fac.S} columns with zero noise "
+                             "and obs_noise = 0: the sensors' covariance F_A F_A^T is singular; "
+                             "give a noise or an obs_noise > 0")
+        if not (isinstance(max_readings, (int, np.integer)) and 1 <= max_readings <= self.B_MAX):
+            raise ValueError(f"max_readings must be an integer in [1, {self.B_MAX}], got "
+                             f"{max_readings!r}")
+        self.max_readings = int(max_readings)
+        self._ready = False
+
+    def _init(self):
+        # on first use, so that the arguments are validated without a device
+        if self._ready:
+            return
+        dev = self.fac.F.device
+        self._sensors_dev = torch.as_tensor(self.sensors, dtype=torch.int64, device=dev)
+        self.ws = linalg.workspace(query("vgposp_fpost_workspace_bytes", self.n, self.fac.S,
+                                         self.k, self.max_readings))
+        self._info = torch.zeros(1, dtype=torch.int32, device=dev)
+        call("vgposp_fpost_init", *self.fac.args(), _p(self._sensors_dev), self.k, self.obs_noise,
+             _p(self._info), _p(self.ws), self.ws.numel(), _stream())
+        self._ready = True
+
+    @property
+    def info(self):
+        """The device status of the k x k factorization ([1] int32; 0: positive definite)."""
+        self._init()
+        return self._info
+
+    def check(self):
+        """Synchronise on the status of the factorization; raise CholeskyError if the sensors'
+        covariance was not positive definite (then no output was written)."""
+        linalg.check_info(self.info)
+
+    def _apply(self, var, Y, mu, out):
+        nrhs = 0 if Y is None else int(Y.shape[1])
+        call("vgposp_fpost_apply", *self.fac.args(), self.k, _p(var), _p(Y),
+             0 if Y is None else Y.stride(0), nrhs, _p(mu), _p(out),
+             0 if out is None else out.stride(0), _p(self.ws), self.ws.numel(), _stream())
+
+    def variance(self, out=None):
+        """[N] device tensor: the posterior variance of every site as computed (a sensor's own is
+        0 up to rounding when both noises are zero there; tiny negatives are not clamped)."""
+        self._init()
+        var = (torch.empty(self.N, dtype=torch.float64, device=self.fac.F.device)
+               if out is None else out)
+        self._apply(var, None, None, None)
+        return var
+
+    def stddev(self):
+        """[N] device tensor: the square root of the variance clamped at 0."""
+        return self.variance().clamp_(min=0.0).sqrt_()
+
+    def _mean(self, readings, mean, out, var):
+        """``mean()``; ``var`` [N] (or None) is filled in the first slice's pass over F."""
+        Y = readings.detach() if isinstance(readings, torch.Tensor) else np.asarray(readings)
+        shape = tuple(Y.shape)
+        if len(shape) not in (1, 2) or shape[0] != self.k:
+            raise ValueError(f"readings must be [{self.k}] or [{self.k}, B], got {shape}")
+        if mean is not None and tuple(np.shape(mean)) != (self.N,):
+            raise ValueError(f"mean must have length {self.N}, got shape "
+                             f"{tuple(np.shape(mean))}")
+        self._init()
+        mu = None if mean is None else linalg.as_device(mean).reshape(-1).contiguous()
+        Y = linalg.as_device(Y).reshape(self.k, -1).contiguous()
+        B = int(Y.shape[1])
+        res = (torch.empty((self.N, B), dtype=torch.float64, device=Y.device)
+               if out is None else out)
+        if var is not None and B == 0:
+            self._apply(var, None, None, None)
+        for b0 in range(0, B, self.max_readings):
+            b1 = min(B, b0 + self.max_readings)
+            self._apply(var if b0 == 0 else None, Y[:, b0:b1], mu, res[:, b0:b1])
+        return res.reshape(self.N) if len(shape) == 1 else res
+
+    def mean(self, readings, mean=None, out=None):
+        """The posterior mean of the field given ``readings`` at the sensors, in their order: [k]
+        -> [N], or [k, B] (B sets of readings) -> [N, B].  ``mean`` [N] is the prior mean (default
+        zeros).  Works in slices of ``max_readings`` columns."""
+        return self._mean(readings, mean, out, None)
+
+    def mean_and_variance(self, readings, mean=None):
+        """``(mean(readings, mean), variance())`` with the variance taken in the first slice's
+        pass over F: the two share every 64-column panel that has room for both."""
+        var = torch.empty(self.N, dtype=torch.float64, device=linalg.device())
+        return self._mean(readings, mean, None, var), var
+
+
+def reconstruct_from_samples(samples, sensors, readings, noise=0.0, obs_noise=0.0, tr_stdev=1.0):
+    """``(mean, variance)`` of the field given ``readings`` at ``sensors``, under the empirical
+    covariance of ``samples`` [N locations, S samples] plus diag(``noise``) (the reference's
+    placement covariance, main.py:190-199) with the samples' mean per location as the prior mean.
+    ``readings`` [k] or [k, B]; ``mean`` is [N] or [N, B], ``variance`` [N]."""
+    shape = tuple(np.shape(samples))
+    if len(shape) != 2 or shape[0] < 1:
+        raise ValueError(f"samples must be [N, S] with N >= 1, got {shape}")
+    _index_array("sensors", sensors, shape[0])
+    T = linalg.as_device(samples)
+    mu = T.mean(1)                      # before from_samples centres its copy
+    fac = FactoredCovariance.from_samples(T, noise=noise, tr_stdev=tr_stdev)
+    rec = FieldReconstruction(fac, sensors, obs_noise=obs_noise)
+    mean, var = rec.mean_and_variance(readings, mean=mu)
+    rec.check()
+    return mean, var
